@@ -4,11 +4,17 @@
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 16] [--version xl]      (N > 1: starts its N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py ... --full                   # also the per-kernel / roofline figures, power, the other plans and configs, the CPU baseline
+    python bench.py ... --dump-outputs DIR       # after the timed steps: what the last step returned, as DIR/<name>.npy (float32)
 
 A step = one UNet forward over one batch of `--batch` synthetic 1024x1024 images' pre-noised latents
 (already resident in HBM) with the `config_xl_practical` hooks written to HBM.  One process per GPU, the
 image batch is sharded (weak scaling: every rank runs its own `--batch`), weights are generated on rank 0
 and broadcast once over RCCL, no collective in the hot loop.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps (hipGraph replay, the product path) and prints the line; everything
+else it can measure (the synchronising per-op pass, event nodes around the dominant kernel, hook-write rate, power,
+the hipgraph / eager legs, other operand plans and configurations, the CPU baseline) runs only under --full.
 """
 import argparse
 import json
@@ -239,6 +245,30 @@ def csrc_sha():
     return h.hexdigest()[:16]
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(outdir, arrays, limit_bytes=DUMP_LIMIT_BYTES):
+    """Write every tensor of `arrays` ({name: tensor}) as <outdir>/<name>.npy in float32, at most `limit_bytes` in all.  A tensor of
+    more elements than its even share of the limit is written as a fixed sample of its flattened (row-major) elements: sorted indices
+    drawn from a generator seeded with the name, so every run and every build writes the same positions.  Returns {name: (shape, kept)}."""
+    import zlib
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    share = limit_bytes // 4 // max(1, len(arrays))
+    info = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n > share:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, size=share, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.float().cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), a if n > share else a.reshape(tuple(t.shape)))
+        info[name] = (tuple(t.shape), min(n, share))
+    return info
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -255,15 +285,24 @@ def main():
     ap.add_argument("--precise", nargs="?", const="precise", default=None,
                     help="operand plan of the measured step: absent = 'auto' (chosen from the requested hooks: plain fp16 operands for the headline's "
                          "four); --precise = every operand class split (fp16 hi + lo, K doubled); --precise selective | plain | stream,attn_out ...")
-    ap.add_argument("--no-extras", action="store_true", help="skip the plans / other_configs / e2e legs (N = 1 only run them)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: per-op pass, live roofline of the dominant kernel (event nodes in the timed graphs), hook-write "
+                         "rate, power, hipgraph / eager legs, plans / e2e / other_configs (N = 1, unless --no-extras), CPU baseline (unless "
+                         "--no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned (noise_pred and every hook) as DIR/<name>.npy, float32, "
+                         "at most 64 MB in all (larger tensors: a fixed seeded sample of their elements)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the plans / other_configs / e2e legs (N = 1 only run them)")
     ap.add_argument("--profile-ops", action="store_true", help="print a per-op time table (extra synchronising pass)")
     ap.add_argument("--e2e", action="store_true",
                     help="N = 1: time FeatureExtractor.extract(image_type='tensors') instead of the UNet step — VAE encode + sample + noise-add + "
                          "UNet + hooks on synthetic 1024^2 images resident in HBM, --steps batches; prints its own JSON line (the default line "
                          "carries the same measurement as its `e2e` block)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.e2e or args.version == "flux"):
+        sys.exit("--dump-outputs covers the UNet step (--version xl / 1-5)")
 
-    if args.e2e:                                    # the product call end to end; not BASELINE.json's metric: a separate line
+    if args.e2e:                                   # the product call end to end; not BASELINE.json's metric: a separate line
         if int(os.environ.get("WORLD_SIZE", "1")) != 1 or args.gpus != 1 or args.version != "xl":
             sys.exit("--e2e is a single-GPU SDXL measurement")
         sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -280,7 +319,7 @@ def main():
 
     if args.version == "flux":                    # BASELINE configs[4]: same JSON schema, single GPU (tools/bench_flux.py)
         sys.argv = [sys.argv[0], "--steps", str(args.steps), "--warmup", str(args.warmup)] + (["--dtype", args.flux_dtype]) + \
-                   (["--batch", str(args.batch)] if args.batch != 16 else []) + (["--no-cpu-baseline"] if args.no_cpu_baseline else [])
+                   (["--batch", str(args.batch)] if args.batch != 16 else []) + (["--no-cpu-baseline"] if args.no_cpu_baseline or not args.full else [])
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_flux
         return bench_flux.main()
@@ -380,46 +419,52 @@ def main():
         return unet.forward_raw(x, t, ctx, txt, tid, hook_ids=ids, shared_ctx=True)   # one prompt repeated
 
     prof = None
-    for w in range(max(1, args.warmup)):
+    # (a plan's first forward runs eagerly and its second builds the hipGraph: a plain run warms up with at least two, so that no graph is
+    # built inside the timed region; under --full the timing graphs below are built before the clock as well)
+    for w in range(max(1 if args.full else 2, args.warmup)):
         step()
     torch.cuda.synchronize()
-    # pick the dominant kernel from a synchronising per-op pass (untimed), then time it live with HIP events
-    _, _, prof = unet.forward_raw(x, t, ctx, txt, tid, hook_ids=ids, profile=True, shared_ctx=True)
     lib = unet.lib
     plan = unet._plan(B, lat, lat, 77, ids, True)
-    by_label = {}
-    for name, ms, fl, lab in prof:
-        d = by_label.setdefault(lab, [0.0, 0.0, 0])
-        d[0] += ms; d[1] += fl; d[2] += 1
-    # the kernel that carries the most time AMONG those that carry algorithmic FLOPs (the roofline below is an MFMA roofline; on a tiny workload under
-    # contention — the share-GPU tests — a bandwidth-bound norm kernel can top the list by a hair, and 0 FLOP / time is not a rate)
-    flop_labels = [k for k in by_label if by_label[k][1] > 0]
-    dominant = max(flop_labels or by_label, key=lambda k: by_label[k][0])
-    TIMING_STRIDE = 8        # every 8th launch of the dominant kernel carries an event pair (an event node costs ~3.5 us inside a graph)
-    rc = lib.gdf_plan_set_timing_stride(plan.handle, TIMING_STRIDE)
-    assert rc == 0, lib.gdf_last_error()
-    rc = lib.gdf_plan_set_timing(plan.handle, dominant.encode())
-    assert rc == 0, lib.gdf_last_error()
-    # The timed region below is the PRODUCT path: one hipGraphLaunch per step.  With timing switched on the library replays graphs
-    # that carry event-record nodes around every launch of the dominant kernel (gdf.h gdf_plan_set_timing; one graph per timing
-    # event set), so `roofline.achieved` is measured live inside the same K steps that give `value`.  Those graphs are built
-    # here, before the clock starts; then the accumulators are reset.  (Results are dropped before each step so that the plan
-    # reuses one hook-buffer set: a stable binding, no graph construction inside the timed region — asserted below.)
+    if args.full or args.profile_ops:
+        # a synchronising per-op pass (untimed): the per-kernel figures, and under --full the dominant kernel, timed live below with HIP events
+        _, _, prof = unet.forward_raw(x, t, ctx, txt, tid, hook_ids=ids, profile=True, shared_ctx=True)
     out = None
-    for _ in range(4):
-        out = None
-        out = step()
-    torch.cuda.synchronize()
-    rc = lib.gdf_plan_set_timing(plan.handle, dominant.encode())
-    assert rc == 0, lib.gdf_last_error()
+    if args.full:
+        by_label = {}
+        for name, ms, fl, lab in prof:
+            d = by_label.setdefault(lab, [0.0, 0.0, 0])
+            d[0] += ms; d[1] += fl; d[2] += 1
+        # the kernel that carries the most time AMONG those that carry algorithmic FLOPs (the roofline below is an MFMA roofline; on a tiny workload under
+        # contention — the share-GPU tests — a bandwidth-bound norm kernel can top the list by a hair, and 0 FLOP / time is not a rate)
+        flop_labels = [k for k in by_label if by_label[k][1] > 0]
+        dominant = max(flop_labels or by_label, key=lambda k: by_label[k][0])
+        TIMING_STRIDE = 8        # every 8th launch of the dominant kernel carries an event pair (an event node costs ~3.5 us inside a graph)
+        rc = lib.gdf_plan_set_timing_stride(plan.handle, TIMING_STRIDE)
+        assert rc == 0, lib.gdf_last_error()
+        rc = lib.gdf_plan_set_timing(plan.handle, dominant.encode())
+        assert rc == 0, lib.gdf_last_error()
+        # The timed region below is the PRODUCT path: one hipGraphLaunch per step.  With timing switched on the library replays graphs
+        # that carry event-record nodes around every launch of the dominant kernel (gdf.h gdf_plan_set_timing; one graph per timing
+        # event set), so `roofline.achieved` is measured live inside the same K steps that give `value`.  Those graphs are built
+        # here, before the clock starts; then the accumulators are reset.  (Results are dropped before each step so that the plan
+        # reuses one hook-buffer set: a stable binding, no graph construction inside the timed region — asserted below.)
+        for _ in range(4):
+            out = None
+            out = step()
+        torch.cuda.synchronize()
+        rc = lib.gdf_plan_set_timing(plan.handle, dominant.encode())
+        assert rc == 0, lib.gdf_last_error()
     st_before = plan.graph_stats()
 
     def barrier():
         if multi:
             dist.barrier()
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import bench_extra as BX
-    sampler = BX.PowerSampler(local) if rank == 0 else None
+    sampler = None
+    if args.full:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import bench_extra as BX
+        sampler = BX.PowerSampler(local) if rank == 0 else None
     if sampler is not None:
         sampler.start()
     barrier(); torch.cuda.synchronize()
@@ -445,46 +490,54 @@ def main():
         torch.cuda.synchronize()
         dist.barrier()
         dist.destroy_process_group()
-    ms_tot = C.c_double(); launches = C.c_long(); fl_tot = C.c_double()
-    lib.gdf_plan_read_timing(plan.handle, C.byref(ms_tot), C.byref(launches), C.byref(fl_tot))
-    lib.gdf_plan_set_timing(plan.handle, None)
+    if args.full:
+        ms_tot = C.c_double(); launches = C.c_long(); fl_tot = C.c_double()
+        lib.gdf_plan_read_timing(plan.handle, C.byref(ms_tot), C.byref(launches), C.byref(fl_tot))
+        lib.gdf_plan_set_timing(plan.handle, None)
     hook_bytes = sum(v.numel() * 2 for v in out[1].values())
     for v in out[1].values():
         assert torch.isfinite(v.float()).all()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: noise_pred (B, 4, H, W) and every requested hook
+        dumped = dump_outputs(args.dump_outputs, {"noise_pred": out[0], **out[1]})
+        print("[bench] wrote %d arrays to %s: %s" % (len(dumped), args.dump_outputs, ", ".join(
+            f"{k} {s} ({n} values)" for k, (s, n) in dumped.items())), file=sys.stderr)
 
     if rank == 0:
         fl = unet_flops_per_image(cfg, lat)
         fl_img = sum(fl.values())
-        kv_img = 0.0
-        for name, ms, f_, lab in prof:
-            if name == "attn2_kv":
-                kv_img += f_                                       # (shared_ctx: the op's FLOPs are those of ONE prompt)
+        if args.full:
+            kv_img = 0.0
+            for name, ms, f_, lab in prof:
+                if name == "attn2_kv":
+                    kv_img += f_                                       # (shared_ctx: the op's FLOPs are those of ONE prompt)
         ips = world * B * args.steps / dt
-        # HBM bytes/launch of the dominant kernel from the rocprofv3 --pmc passes of THIS command (tools/final_profile.sh ->
-        # profiles/pmc_traffic_current.json).  The file is stamped with a hash of the kernel sources it was measured on: a
-        # stamp that does not match the sources being benchmarked means the number is stale, and `traffic` is null.
-        traffic, traffic_stale = None, None
-        try:
-            tj = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic_current.json")))
-            if args.version == "xl" and B == 16 and dominant in tj:
-                if tj.get("_meta", {}).get("csrc_sha") == csrc_sha():
-                    traffic, traffic_stale = tj[dominant]["hbm_bytes_per_launch"], False
-                else:                                              # measured on other kernel sources than the ones benchmarked: say so
-                    traffic_stale = True
-        except Exception:
-            traffic = None
-        achieved = (fl_tot.value / 1e12) / (ms_tot.value / 1e3) if ms_tot.value > 0 else 0.0
-        dom_ops = {}
-        for name, ms, f_, lab in prof:
-            if lab == dominant:
-                d_ = dom_ops.setdefault(name, [0.0, 0.0]); d_[0] += ms; d_[1] += f_
+        if args.full:
+            # HBM bytes/launch of the dominant kernel from the rocprofv3 --pmc passes of THIS command (tools/final_profile.sh ->
+            # profiles/pmc_traffic_current.json).  The file is stamped with a hash of the kernel sources it was measured on: a
+            # stamp that does not match the sources being benchmarked means the number is stale, and `traffic` is null.
+            traffic, traffic_stale = None, None
+            try:
+                tj = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic_current.json")))
+                if args.version == "xl" and B == 16 and dominant in tj:
+                    if tj.get("_meta", {}).get("csrc_sha") == csrc_sha():
+                        traffic, traffic_stale = tj[dominant]["hbm_bytes_per_launch"], False
+                    else:                                              # measured on other kernel sources than the ones benchmarked: say so
+                        traffic_stale = True
+            except Exception:
+                traffic = None
+            achieved = (fl_tot.value / 1e12) / (ms_tot.value / 1e3) if ms_tot.value > 0 else 0.0
+            dom_ops = {}
+            for name, ms, f_, lab in prof:
+                if lab == dominant:
+                    d_ = dom_ops.setdefault(name, [0.0, 0.0]); d_[0] += ms; d_[1] += f_
         res = {
             "metric": "images/sec feature-extract, SDXL 1024^2 single-timestep" if args.version == "xl"
                       else "images/sec feature-extract, SD1.5 512^2 single-timestep",
             "value": round(ips, 3), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f16", "data": "synthetic", "rccl": group,
-            "timed_region": {"path": ("hipGraph replay (product default), event-record nodes around the dominant kernel"
+            "timed_region": {"path": ("hipGraph replay (product default)" + (", event-record nodes around the dominant kernel" if args.full else "")
                                       if (plan.graph and launches_in_region == args.steps and fails_in_region == 0) else
                                       "eager launches (GDF_HIP_GRAPH=0)" if not plan.graph else
                                       f"MIXED: {launches_in_region} graph launches, {fails_in_region} eager fallbacks in {args.steps} steps"),
@@ -502,8 +555,8 @@ def main():
                        "tflop_per_image": round(fl_img / 1e12, 3),
                        # EXECUTED FLOPs: with one prompt repeated over the batch (reference diffusion_feature.py:272) the text K/V
                        # projections run once per batch (shared_ctx), not once per image
-                       "model_tflops_per_s": round(ips * (fl_img - kv_img * (B - 1) / B) / 1e12, 1),
-                       "shared_ctx_kv_gflop_per_image_not_executed": round(kv_img * (B - 1) / B / 1e9, 1),
+                       **({"model_tflops_per_s": round(ips * (fl_img - kv_img * (B - 1) / B) / 1e12, 1),
+                           "shared_ctx_kv_gflop_per_image_not_executed": round(kv_img * (B - 1) / B / 1e9, 1)} if args.full else {}),
                        "weights_init_s": round(t_init, 1), "weights_broadcast_s": round(t_bcast, 3),
                        "weights_broadcast_gb_per_s": round(unet.weight_blob().numel() / 1e9 / t_bcast, 1) if multi and t_bcast > 0 else None,
                        "launched_by": ("bench.py itself (components/dist.py self_launch)" if os.environ.get("GDF_SELF_LAUNCHED") == "1" else
@@ -511,123 +564,126 @@ def main():
                        "max_inflight_forwards": int(os.environ.get("GDF_MAX_INFLIGHT", "4" if world > 1 else "0")),
                        "per_rank_ms_per_step": {"min": round(per_rank_ms[0], 3), "max": round(per_rank_ms[-1], 3)},
                        "rank_cpu_affinity": {"rank0_cpus": len(pinned), "first": pinned[0], "last": pinned[-1]} if pinned else None},
-            "roofline": {"bound": "mfma", "kernel": dominant, "achieved": round(achieved, 1), "peak": MFMA_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_stale": traffic_stale,
-                         "frac_of_random_operand_mfma_ceiling": round(achieved / MFMA_RANDOM_DATA_CEILING_TFLOPS, 4),
-                         "random_operand_mfma_ceiling": MFMA_RANDOM_DATA_CEILING_TFLOPS,
-                         "launches": int(launches.value), "avg_launch_ms": round(ms_tot.value / max(1, launches.value), 4),
-                         "sampling": f"HIP events around every {TIMING_STRIDE}th launch of the kernel in program order, all K steps "
-                                     f"({int(launches.value)} of {TIMING_STRIDE * int(launches.value)} launches)",
-                         "flops_per_launch_g": round(fl_tot.value / max(1, launches.value) / 1e9, 2),
-                         "share_of_step_time": round(by_label[dominant][0] / sum(v[0] for v in by_label.values()), 3),
-                         # the same kernel symbol serves several op classes of the plan: TFLOP/s and ms per class (synchronising
-                         # per-op pass).  Since round 2 the fp32-residual attention out-projections (HBM-bound epilogue, 0.27 of
-                         # the peak on the 128x160 ring in round 1) run on this kernel too, which lowers its AVERAGE rate while
-                         # every class and the step got faster.
-                         "by_op": {n: {"tflops": round(v[1] / 1e9 / max(v[0], 1e-9), 1), "ms": round(v[0], 3)}
-                                   for n, v in sorted(dom_ops.items(), key=lambda kv: -kv[1][0])}},
-            "kernel_time_share": {k: round(v[0] / sum(x[0] for x in by_label.values()), 3)
-                                  for k, v in sorted(by_label.items(), key=lambda kv: -kv[1][0])[:8]},
-            "kernel_tflops": {k: round(v[1] / 1e9 / v[0], 1) for k, v in by_label.items() if v[1] > 0 and v[0] > 0},
         }
-        # ---- the rooflines BASELINE.json's north_star names, from the synchronising per-op pass (one forward) ----
-        # attention-MFMA: self-attention QK^T + PV FLOPs / time of those launches; conv: 3x3 conv FLOPs / time (MFMA) and the
-        # ResBlock activation bytes of SURVEY.md §8d (2 Cin + 3 Cout per pixel, fp16) / time of all ResBlock ops (HBM);
-        # hook writes: bytes of the hooks stored by copy2d_kernel / its time.
-        grp = {}
-        for name, ms, f_, _k in prof:
-            g_ = grp.setdefault(name, [0.0, 0.0]); g_[0] += ms; g_[1] += f_
-        def tsum(names):
-            return sum(grp[n][0] for n in names if n in grp), sum(grp[n][1] for n in names if n in grp)
-        a_ms, a_fl = tsum(["attn1"])
-        c_ms, c_fl = tsum(["res_conv1", "res_conv2", "upsample", "downsample"])
-        r_ms, _ = tsum(["res_conv1", "res_conv2", "res_shortcut", "gn_stats", "gn_apply_silu"])
-        res_bytes = B * (610.8e6 if args.version == "xl" and lat == 128 else 152.9e6 if args.version == "1-5" and lat == 64 else 0.0)
-        h_ms, _ = tsum(["hook_store"])
-        # only the hooks the plan routes through hook_store (copy2d_kernel); the others are written by their producer's epilogue
-        copied = sum(nbytes for i, (_hid, _shp, _str, nbytes) in enumerate(plan.hooks) if lib.gdf_plan_hook_copied(plan.handle, i))
-        res["rooflines"] = {
-            "attention_mfma": {"kernel": "attn_kernel", "achieved": round(a_fl / 1e9 / max(a_ms, 1e-9), 1), "peak": MFMA_PEAK_TFLOPS,
-                               "unit": "TFLOP/s", "frac": round(a_fl / 1e9 / max(a_ms, 1e-9) / MFMA_PEAK_TFLOPS, 4),
-                               "ms_per_step": round(a_ms, 3)},
-            "conv_mfma": {"achieved": round(c_fl / 1e9 / max(c_ms, 1e-9), 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                          "frac": round(c_fl / 1e9 / max(c_ms, 1e-9) / MFMA_PEAK_TFLOPS, 4), "ms_per_step": round(c_ms, 3)},
-            "conv_hbm": {"achieved": round(res_bytes / 1e6 / max(r_ms, 1e-9), 1) if res_bytes else None, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(res_bytes / 1e6 / max(r_ms, 1e-9) / HBM_PEAK_GBS, 4) if res_bytes else None,
-                         "note": "ResBlock activation bytes (2 Cin + 3 Cout per pixel, fp16) / time of conv + GroupNorm + shortcut ops: "
-                                 "the fused block is MFMA-bound, so this fraction is far below 1 by construction",
-                         "ms_per_step": round(r_ms, 3)},
-            "hook_writes": {"kernel": "copy2d_kernel", "achieved": round(2 * copied / 1e6 / max(h_ms, 1e-9), 1) if h_ms > 0 else None,
-                            "peak": HBM_PEAK_GBS, "unit": "GB/s (read + write)",
-                            "frac": round(2 * copied / 1e6 / max(h_ms, 1e-9) / HBM_PEAK_GBS, 4) if h_ms > 0 else None,
-                            "bytes_per_step": copied, "ms_per_step": round(h_ms, 4)},
-        }
-        # hook writes as rocprofv3 sees them: HIP events around every copy2d_kernel launch inside the replayed graph (the
-        # synchronising per-op pass above includes ~5 us of launch + sync latency per 20-us kernel)
-        if h_ms > 0 and copied:
-            lib.gdf_plan_set_timing_stride(plan.handle, 1)
-            if lib.gdf_plan_set_timing(plan.handle, b"copy2d_kernel") == 0:
-                o2 = None
-                for _ in range(6):
+        if args.full:
+            res.update({
+                "roofline": {"bound": "mfma", "kernel": dominant, "achieved": round(achieved, 1), "peak": MFMA_PEAK_TFLOPS,
+                             "unit": "TFLOP/s", "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_stale": traffic_stale,
+                             "frac_of_random_operand_mfma_ceiling": round(achieved / MFMA_RANDOM_DATA_CEILING_TFLOPS, 4),
+                             "random_operand_mfma_ceiling": MFMA_RANDOM_DATA_CEILING_TFLOPS,
+                             "launches": int(launches.value), "avg_launch_ms": round(ms_tot.value / max(1, launches.value), 4),
+                             "sampling": f"HIP events around every {TIMING_STRIDE}th launch of the kernel in program order, all K steps "
+                                         f"({int(launches.value)} of {TIMING_STRIDE * int(launches.value)} launches)",
+                             "flops_per_launch_g": round(fl_tot.value / max(1, launches.value) / 1e9, 2),
+                             "share_of_step_time": round(by_label[dominant][0] / sum(v[0] for v in by_label.values()), 3),
+                             # the same kernel symbol serves several op classes of the plan: TFLOP/s and ms per class (synchronising
+                             # per-op pass).  Since round 2 the fp32-residual attention out-projections (HBM-bound epilogue, 0.27 of
+                             # the peak on the 128x160 ring in round 1) run on this kernel too, which lowers its AVERAGE rate while
+                             # every class and the step got faster.
+                             "by_op": {n: {"tflops": round(v[1] / 1e9 / max(v[0], 1e-9), 1), "ms": round(v[0], 3)}
+                                       for n, v in sorted(dom_ops.items(), key=lambda kv: -kv[1][0])}},
+                "kernel_time_share": {k: round(v[0] / sum(x[0] for x in by_label.values()), 3)
+                                      for k, v in sorted(by_label.items(), key=lambda kv: -kv[1][0])[:8]},
+                "kernel_tflops": {k: round(v[1] / 1e9 / v[0], 1) for k, v in by_label.items() if v[1] > 0 and v[0] > 0},
+            })
+            # ---- the rooflines BASELINE.json's north_star names, from the synchronising per-op pass (one forward) ----
+            # attention-MFMA: self-attention QK^T + PV FLOPs / time of those launches; conv: 3x3 conv FLOPs / time (MFMA) and the
+            # ResBlock activation bytes of SURVEY.md §8d (2 Cin + 3 Cout per pixel, fp16) / time of all ResBlock ops (HBM);
+            # hook writes: bytes of the hooks stored by copy2d_kernel / its time.
+            grp = {}
+            for name, ms, f_, _k in prof:
+                g_ = grp.setdefault(name, [0.0, 0.0]); g_[0] += ms; g_[1] += f_
+            def tsum(names):
+                return sum(grp[n][0] for n in names if n in grp), sum(grp[n][1] for n in names if n in grp)
+            a_ms, a_fl = tsum(["attn1"])
+            c_ms, c_fl = tsum(["res_conv1", "res_conv2", "upsample", "downsample"])
+            r_ms, _ = tsum(["res_conv1", "res_conv2", "res_shortcut", "gn_stats", "gn_apply_silu"])
+            res_bytes = B * (610.8e6 if args.version == "xl" and lat == 128 else 152.9e6 if args.version == "1-5" and lat == 64 else 0.0)
+            h_ms, _ = tsum(["hook_store"])
+            # only the hooks the plan routes through hook_store (copy2d_kernel); the others are written by their producer's epilogue
+            copied = sum(nbytes for i, (_hid, _shp, _str, nbytes) in enumerate(plan.hooks) if lib.gdf_plan_hook_copied(plan.handle, i))
+            res["rooflines"] = {
+                "attention_mfma": {"kernel": "attn_kernel", "achieved": round(a_fl / 1e9 / max(a_ms, 1e-9), 1), "peak": MFMA_PEAK_TFLOPS,
+                                   "unit": "TFLOP/s", "frac": round(a_fl / 1e9 / max(a_ms, 1e-9) / MFMA_PEAK_TFLOPS, 4),
+                                   "ms_per_step": round(a_ms, 3)},
+                "conv_mfma": {"achieved": round(c_fl / 1e9 / max(c_ms, 1e-9), 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                              "frac": round(c_fl / 1e9 / max(c_ms, 1e-9) / MFMA_PEAK_TFLOPS, 4), "ms_per_step": round(c_ms, 3)},
+                "conv_hbm": {"achieved": round(res_bytes / 1e6 / max(r_ms, 1e-9), 1) if res_bytes else None, "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(res_bytes / 1e6 / max(r_ms, 1e-9) / HBM_PEAK_GBS, 4) if res_bytes else None,
+                             "note": "ResBlock activation bytes (2 Cin + 3 Cout per pixel, fp16) / time of conv + GroupNorm + shortcut ops: "
+                                     "the fused block is MFMA-bound, so this fraction is far below 1 by construction",
+                             "ms_per_step": round(r_ms, 3)},
+                "hook_writes": {"kernel": "copy2d_kernel", "achieved": round(2 * copied / 1e6 / max(h_ms, 1e-9), 1) if h_ms > 0 else None,
+                                "peak": HBM_PEAK_GBS, "unit": "GB/s (read + write)",
+                                "frac": round(2 * copied / 1e6 / max(h_ms, 1e-9) / HBM_PEAK_GBS, 4) if h_ms > 0 else None,
+                                "bytes_per_step": copied, "ms_per_step": round(h_ms, 4)},
+            }
+            # hook writes as rocprofv3 sees them: HIP events around every copy2d_kernel launch inside the replayed graph (the
+            # synchronising per-op pass above includes ~5 us of launch + sync latency per 20-us kernel)
+            if h_ms > 0 and copied:
+                lib.gdf_plan_set_timing_stride(plan.handle, 1)
+                if lib.gdf_plan_set_timing(plan.handle, b"copy2d_kernel") == 0:
                     o2 = None
-                    o2 = step()
-                torch.cuda.synchronize()
-                hm = C.c_double(); hl = C.c_long(); hf = C.c_double()
-                lib.gdf_plan_read_timing(plan.handle, C.byref(hm), C.byref(hl), C.byref(hf))
-                lib.gdf_plan_set_timing(plan.handle, None)
-                o2 = None
-                n_copy = sum(1 for name, *_r in prof if name == "hook_store")
-                if hl.value >= n_copy > 0 and hm.value > 0:
-                    steps_t = hl.value / n_copy
-                    ev_ms = hm.value / steps_t
-                    hw = res["rooflines"]["hook_writes"]
-                    hw.update({"achieved": round(2 * copied / 1e6 / ev_ms, 1), "frac": round(2 * copied / 1e6 / ev_ms / HBM_PEAK_GBS, 4),
-                               "ms_per_step": round(ev_ms, 4), "timing": "HIP events around every copy2d_kernel launch inside the graph replay",
-                               "sync_pass_gbs": hw["achieved"]})
-        # ---- extra legs (N = 1): the same steps WITHOUT the timing nodes (`hipgraph.value`: what FeatureExtractor.extract runs) and
-        # eagerly launched (`eager_host_cpu_ms_per_step`: the host cost the graph removes)
-        if world == 1:
-            def leg():
-                for _ in range(3):
-                    step()
-                torch.cuda.synchronize()
-                capw = plan.graph_stats()[0]
-                c0 = time.process_time(); t1 = time.perf_counter()
-                for _ in range(args.steps):
-                    step()
-                c1 = time.process_time()
-                torch.cuda.synchronize()
-                return time.perf_counter() - t1, (c1 - c0) / args.steps * 1e3, capw
-            dt2, cpu_graph, cap0 = leg()
-            cap1, lau1, _f1 = plan.graph_stats()
-            lib.gdf_plan_set_graph(plan.handle, 0); plan.graph = False
-            _, cpu_eager, _ = leg()
-            lib.gdf_plan_set_graph(plan.handle, 1); plan.graph = True
-            res["hipgraph"] = {"value": round(B * args.steps / dt2, 3), "unit": "images/s",
-                               "host_cpu_ms_per_step": round(cpu_graph, 2), "eager_host_cpu_ms_per_step": round(cpu_eager, 2),
-                               "captures_total": cap1, "captures_in_timed_steps": cap1 - cap0,
-                               "graph_launches": lau1, "ops_per_step": lib.gdf_plan_num_ops(plan.handle)}
-        if power:
-            res["power"] = power
-        if world == 1 and not args.no_extras and args.precise is None and not args.early_exit and not args.fp16_stream:
-            try:
-                res["plans"] = BX.plans_block(unet, step, B, res["hipgraph"]["value"])
-            except Exception as e:
-                res["plans"] = {"error": repr(e)[:300]}
-            unet._plans.clear(); torch.cuda.empty_cache()
-            if args.version == "xl" and B == 16 and not args.img:
+                    for _ in range(6):
+                        o2 = None
+                        o2 = step()
+                    torch.cuda.synchronize()
+                    hm = C.c_double(); hl = C.c_long(); hf = C.c_double()
+                    lib.gdf_plan_read_timing(plan.handle, C.byref(hm), C.byref(hl), C.byref(hf))
+                    lib.gdf_plan_set_timing(plan.handle, None)
+                    o2 = None
+                    n_copy = sum(1 for name, *_r in prof if name == "hook_store")
+                    if hl.value >= n_copy > 0 and hm.value > 0:
+                        steps_t = hl.value / n_copy
+                        ev_ms = hm.value / steps_t
+                        hw = res["rooflines"]["hook_writes"]
+                        hw.update({"achieved": round(2 * copied / 1e6 / ev_ms, 1), "frac": round(2 * copied / 1e6 / ev_ms / HBM_PEAK_GBS, 4),
+                                   "ms_per_step": round(ev_ms, 4), "timing": "HIP events around every copy2d_kernel launch inside the graph replay",
+                                   "sync_pass_gbs": hw["achieved"]})
+            # ---- extra legs (N = 1): the same steps WITHOUT the timing nodes (`hipgraph.value`: what FeatureExtractor.extract runs) and
+            # eagerly launched (`eager_host_cpu_ms_per_step`: the host cost the graph removes)
+            if world == 1:
+                def leg():
+                    for _ in range(3):
+                        step()
+                    torch.cuda.synchronize()
+                    capw = plan.graph_stats()[0]
+                    c0 = time.process_time(); t1 = time.perf_counter()
+                    for _ in range(args.steps):
+                        step()
+                    c1 = time.process_time()
+                    torch.cuda.synchronize()
+                    return time.perf_counter() - t1, (c1 - c0) / args.steps * 1e3, capw
+                dt2, cpu_graph, cap0 = leg()
+                cap1, lau1, _f1 = plan.graph_stats()
+                lib.gdf_plan_set_graph(plan.handle, 0); plan.graph = False
+                _, cpu_eager, _ = leg()
+                lib.gdf_plan_set_graph(plan.handle, 1); plan.graph = True
+                res["hipgraph"] = {"value": round(B * args.steps / dt2, 3), "unit": "images/s",
+                                   "host_cpu_ms_per_step": round(cpu_graph, 2), "eager_host_cpu_ms_per_step": round(cpu_eager, 2),
+                                   "captures_total": cap1, "captures_in_timed_steps": cap1 - cap0,
+                                   "graph_launches": lau1, "ops_per_step": lib.gdf_plan_num_ops(plan.handle)}
+            if power:
+                res["power"] = power
+            if world == 1 and not args.no_extras and args.precise is None and not args.early_exit and not args.fp16_stream:
                 try:
-                    res["e2e"] = BX.e2e_block(dev, args.version, B, img, ids)
+                    res["plans"] = BX.plans_block(unet, step, B, res["hipgraph"]["value"])
                 except Exception as e:
-                    res["e2e"] = {"error": repr(e)[:300]}
-                res["other_configs"] = BX.other_configs_block(dev, unet_flops_per_image, PRACTICAL)
+                    res["plans"] = {"error": repr(e)[:300]}
+                unet._plans.clear(); torch.cuda.empty_cache()
+                if args.version == "xl" and B == 16 and not args.img:
+                    try:
+                        res["e2e"] = BX.e2e_block(dev, args.version, B, img, ids)
+                    except Exception as e:
+                        res["e2e"] = {"error": repr(e)[:300]}
+                    res["other_configs"] = BX.other_configs_block(dev, unet_flops_per_image, PRACTICAL)
         if args.profile_ops:
             rows = {}
             for name, ms, f_, _k in prof:
                 r = rows.setdefault(name, [0.0, 0.0, 0]); r[0] += ms; r[1] += f_; r[2] += 1
             for name, r in sorted(rows.items(), key=lambda kv: -kv[1][0]):
                 print(f"# {name:16s} n={r[2]:4d} {r[0]:9.3f} ms  {r[1] / 1e9 / max(r[0], 1e-9):8.1f} TFLOP/s", file=sys.stderr)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # (any N: rank 0 times it after the process group is gone, on its own share of the host cores)
             res["cpu_baseline"] = cpu_baseline(args.version, lat)
             res["cpu_baseline"]["host"] = {"cpus": os.cpu_count(), "rank0_affinity_cpus": len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else None,

@@ -48,5 +48,24 @@ def main():
     print({k: v.shape for k, v in arrs.items() if k.startswith("out:")}, os.path.getsize(path) // 1024, "KiB")
 
 
+def main_store_cat():
+    """tests/golden/attn_store_cat.npz: the reference AttentionStore fed the maps test_aggregate_attention_matches_reference_attention_store
+    draws (torch.Generator seed 0, in the same order), aggregated over ["up_cross", "down_self"] and resized to 16 x 16."""
+    RB.attn_store_processor()
+    AttentionStore = sys.modules["gdf_ref_attention"].AttentionStore
+    g = torch.Generator().manual_seed(0)
+    store = AttentionStore(min_size=4, max_size=8)
+    for place, cross, q, k in (("up", True, 16, 77), ("up", True, 64, 77), ("up", True, 16, 77), ("down", False, 64, 64)):
+        probs = torch.softmax(torch.randn(2, 4, q, k, generator=g), -1)
+        store(probs.mean(1), cross, place)
+    sel = ["up_cross", "down_self"]
+    ref = store.aggregate_attention(sel)
+    out = torch.cat([F.interpolate(a, size=(16, 16)) for c in sel for a in ref[c].values()], dim=-3)
+    path = os.path.join(HERE, "attn_store_cat.npz")
+    np.savez_compressed(path, out=out.numpy(), sel=np.array(repr(sel)))
+    print(tuple(out.shape), os.path.getsize(path) // 1024, "KiB")
+
+
 if __name__ == "__main__":
     main()
+    main_store_cat()

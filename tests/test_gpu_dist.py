@@ -65,7 +65,7 @@ def test_two_rank_bench_line():
     env = dict(os.environ, GDF_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--version", "1-5", "--batch", "4", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--version", "1-5", "--batch", "4", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["config"]["global_batch"] == 8 and line["value"] > 0
@@ -97,6 +97,33 @@ def test_rccl_one_rank_group_runs_the_n_rank_bench_path():
     assert line["config"]["weights_broadcast_gb_per_s"] is not None and line["config"]["weights_broadcast_gb_per_s"] > 0     # the broadcast ran
     pr = line["config"]["per_rank_ms_per_step"]
     assert pr["min"] == pr["max"] > 0                                                                                   # MAX all_reduce of (dt, -dt) over one rank
+
+
+def test_plain_bench_line_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps graph replays, none of which builds a graph, prints the headline fields and nothing
+    that needs a pass of its own; --dump-outputs writes what the last timed step returned (noise_pred + every hook) as float32 .npy."""
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--version", "1-5", "--batch", "4",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["metric"].startswith("images/sec") and line["unit"] == "images/s" and line["higher_is_better"] is True and line["dtype"] == "f16"
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and abs(line["value"] - 4 * 1e3 / line["ms_per_step"]) < 0.01 * line["value"]
+    tr = line["timed_region"]
+    assert tr["graph_launches_inside"] == 3 and tr["graph_captures_inside"] == 0 and tr["eager_fallbacks_inside"] == 0, tr
+    assert not {"roofline", "rooflines", "kernel_time_share", "hipgraph", "power", "plans", "e2e", "other_configs", "cpu_baseline"} & set(line)
+    sys.path.insert(0, ROOT)
+    import bench
+    names = sorted(os.listdir(out))
+    assert names == sorted(["noise_pred.npy"] + [h + ".npy" for h in bench.PRACTICAL["1-5"]]), names
+    total = 0
+    for n in names:
+        a = np.load(out / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.abs(a).max() > 0, n
+        total += a.nbytes
+    assert np.load(out / "noise_pred.npy").shape == (4, 4, 64, 64) and total <= 64e6
 
 
 def test_rccl_one_rank_group_cli_same_files(tmp_path):
@@ -212,7 +239,7 @@ def test_four_rank_bench_line():
     env = {k: v for k, v in env.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     # the command shape the driver uses: PLAIN python3 bench.py --gpus N (no torchrun) — bench.py starts its four ranks itself
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-                        "--version", "1-5", "--batch", "2"], env=env, capture_output=True, text=True, timeout=1200)
+                        "--version", "1-5", "--batch", "2", "--full"], env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1                                                   # ONE JSON line on stdout: rank 0's

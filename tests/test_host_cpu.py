@@ -118,6 +118,25 @@ def test_model_registry_error_behaviour(monkeypatch):
         models.get_diffusion_model("pixart-alpha", "float16")
 
 
+def test_bench_dump_outputs_fixed_sample_within_limit(tmp_path):
+    """bench.py --dump-outputs: float32 .npy per output, the whole tensor when it fits its share of the limit, else the same seeded
+    sample of its flattened elements on every run (whatever else is dumped beside it)."""
+    import zlib
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(0)
+    big, small = torch.randn(3, 1000, generator=g).half(), torch.randn(2, 5, generator=g)
+    info = bench.dump_outputs(str(tmp_path / "a"), {"big": big, "small": small}, limit_bytes=8000)
+    assert info == {"big": ((3, 1000), 1000), "small": ((2, 5), 10)}
+    a, s = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "a" / "small.npy")
+    assert a.dtype == s.dtype == np.float32 and a.nbytes + s.nbytes <= 8000
+    assert np.array_equal(s, small.numpy())
+    idx = np.sort(np.random.default_rng(zlib.crc32(b"big")).choice(3000, size=1000, replace=False))
+    assert np.array_equal(a, big.float().numpy().reshape(-1)[idx])
+    bench.dump_outputs(str(tmp_path / "b"), {"small": small.t(), "big": big}, limit_bytes=8000)
+    assert np.array_equal(np.load(tmp_path / "b" / "big.npy"), a) and np.load(tmp_path / "b" / "small.npy").shape == (5, 2)
+
+
 def test_bench_flop_model_matches_survey_totals():
     import bench
     from components.native import ARCH_CONFIGS
@@ -129,25 +148,19 @@ def test_bench_flop_model_matches_survey_totals():
 
 def test_aggregate_attention_matches_reference_attention_store():
     """components.feature_extractor.aggregate_attention vs the reference's AttentionStore (components/attention.py:102-161)
-    + the interpolate/cat of diffusion_feature.py:492-500, fed with the same random probability maps."""
-    from oracle import ref_blocks as RB
-    if not RB.available():
-        pytest.skip("reference tree not present (GPU box)")
-    import sys
-    import torch.nn.functional as F
-    RB.attn_store_processor()
-    AttentionStore = sys.modules["gdf_ref_attention"].AttentionStore
+    + the interpolate/cat of diffusion_feature.py:492-500, fed with the same random probability maps (the reference's result for
+    them: tests/golden/attn_store_cat.npz, tests/golden/gen_golden_attn.py main_store_cat)."""
+    import numpy as np
     from components.feature_extractor import aggregate_attention
+    z = np.load(os.path.join(GOLD, "attn_store_cat.npz"))
     g = torch.Generator().manual_seed(0)
-    store = AttentionStore(min_size=4, max_size=8)
     maps = {"up_cross": [], "down_self": []}
     for place, cross, q, k in (("up", True, 16, 77), ("up", True, 64, 77), ("up", True, 16, 77), ("down", False, 64, 64)):
         probs = torch.softmax(torch.randn(2, 4, q, k, generator=g), -1)
-        store(probs.mean(1), cross, place)                            # what AttnStoreProcessor passes (attention.py:241)
-        maps[f"{place}_{'cross' if cross else 'self'}"].append(probs)
+        maps[f"{place}_{'cross' if cross else 'self'}"].append(probs)  # the reference stored probs.mean(1) (attention.py:241)
     sel = ["up_cross", "down_self"]
-    ref = store.aggregate_attention(sel)
-    ref = torch.cat([F.interpolate(a, size=(16, 16)) for c in sel for a in ref[c].values()], dim=-3)
+    assert str(z["sel"]) == repr(sel)
+    ref = torch.from_numpy(z["out"])
     got = aggregate_attention({c: maps[c] for c in sel}, 16)
     assert got.shape == ref.shape == (2, 77 + 77 + 64, 16, 16)
     assert torch.allclose(got.float(), ref, atol=1e-3)
@@ -350,12 +363,13 @@ def test_every_layer_config_of_the_reference_is_served():
             assert len(missing) <= 1, missing                     # one id of that file exists only in the SD1.5 topology
         else:
             assert not missing, (n, missing[:5])
-    # with the reference tree present (this container): identical content
-    ref_dir = "/root/reference/feature/configs"
-    if os.path.isdir(ref_dir):
-        for n in names:
-            assert json.load(open(os.path.join(ref_dir, n))) == json.load(open(os.path.join(cdir, n))), n
-            assert list(json.load(open(os.path.join(ref_dir, n)))) == list(json.load(open(os.path.join(cdir, n)))), n     # key order too
+    # identical content, key order too: the reference's own files as fingerprinted by tests/golden/gen_reference_configs.py
+    import hashlib
+    ref = json.load(open(os.path.join(GOLD, "reference_configs.json")))
+    assert sorted(ref) == names
+    for n in names:
+        cfg = json.load(open(os.path.join(cdir, n)))
+        assert {"sha256": hashlib.sha256(json.dumps(cfg).encode()).hexdigest(), "ids": len(cfg)} == ref[n], n
 
 
 def test_operand_plan_selection_table_and_masks():

@@ -9,7 +9,7 @@ for r in 1 2; do
     if [ $v = prod ]; then cp /tmp/prod.so $D/libgdf.so; else cp $D/libgdf_$v.so $D/libgdf.so; fi
     echo "== $v run $r"
     python tools/bench_attn_quick.py 2>/dev/null | grep sdxl
-    python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
+    python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()

@@ -5,7 +5,7 @@ cp $D/libgdf.so /tmp/new.so
 for r in $(seq 1 $N); do
   for v in prev new; do
     if [ $v = prev ]; then cp $D/libgdf_prev.so $D/libgdf.so; else cp /tmp/new.so $D/libgdf.so; fi
-    python3 bench.py --steps 15 --warmup 3 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
+    python3 bench.py --steps 15 --warmup 3 --full --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()

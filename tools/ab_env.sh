@@ -3,7 +3,7 @@
 VAR=$1; ARGS=${2:-}; N=${3:-3}
 for r in $(seq 1 $N); do
   for v in 0 1; do
-    env $VAR=$v python3 bench.py --steps 15 --warmup 3 --no-cpu-baseline --no-extras $ARGS 2>/dev/null | python3 -c "
+    env $VAR=$v python3 bench.py --steps 15 --warmup 3 --full --no-cpu-baseline --no-extras $ARGS 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()

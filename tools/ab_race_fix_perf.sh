@@ -9,7 +9,7 @@ for r in 1 2 3; do
   for v in oldboth product; do
     if [ $v = product ]; then cp /tmp/keep.so $D/libgdf.so; else cp $D/libgdf_$v.so $D/libgdf.so; fi
     echo "== $v run $r"
-    python3 bench.py --steps 20 --warmup 3 --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('  sdxl B=16      ', d['value'], 'img/s', d['ms_per_step'], 'ms', d['roofline']['achieved'], 'TF dominant')"
+    python3 bench.py --steps 20 --warmup 3 --full --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('  sdxl B=16      ', d['value'], 'img/s', d['ms_per_step'], 'ms', d['roofline']['achieved'], 'TF dominant')"
     for dt in auto fp8-mx; do
       python3 bench.py --version flux --flux-dtype $dt --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('  flux B=8 $dt', d['value'], 'img/s', d['ms_per_step'], 'ms')"
     done

@@ -1,4 +1,4 @@
-"""Extra legs of bench.py's JSON line (N = 1, after the headline's timed region; each is bounded to a few seconds):
+"""Extra legs of bench.py's JSON line (--full, N = 1, after the headline's timed region; each is bounded to a few seconds):
 
   plans           the headline step under each operand-plan level (plain = what the headline's four hooks select / selective / precise)
   other_configs   the other BASELINE.json configs under the driver's eyes: SD1.5 512^2 B = 32 (practical hooks and the full 197-id set of

@@ -29,6 +29,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 out["_meta"] = dict(csrc_sha=bench.csrc_sha(), taken=time.strftime("%Y-%m-%d %H:%M:%S"),
-                    command="rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py --steps 2 --warmup 1",
+                    command="rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 2 --warmup 1",
                     corrections="KiB -> bytes; FETCH_SIZE x2 (gfx950 counts 128-B requests as 64 B: MI355X_MICROARCH.md, HBM)")
 print(json.dumps(out, indent=1))
