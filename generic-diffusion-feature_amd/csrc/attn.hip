@@ -24,9 +24,6 @@ typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
 #define LDS_AS __attribute__((address_space(3)))
 
 static constexpr int KT = 64;     // keys per tile
-#if !defined(GDF_ATTN_PV16_DEFAULT)
-#define GDF_ATTN_PV16_DEFAULT true    // P V on mfma_f32_16x16x32_f16 for D = 40 / 72 / 80 (attn_kernel<..., PV16>): same-box A/B of round 5: D = 40 564 -> 604 (B = 32: 589 -> 640), D = 72 674 -> 715, D = 80 659 -> 703 TFLOP/s (profiles/r05_ab_attn_pv16.txt); GDF_ATTN_PV16=0 restores the 32x32x16 form
-#endif
 
 // ---- element type of q / k / v / o: fp16, or bf16 for a bf16 MMDiT model (BF; the 16-byte fragments are only containers) ----
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -82,34 +79,6 @@ __device__ __forceinline__ size_t seg_row(int b, int j, int per_b, int seg_T, in
   return j < seg_T ? (size_t)b * seg_T + j : (size_t)B * seg_T + (size_t)b * (S_tot - seg_T) + (j - seg_T);
 }
 
-// diagnostics build (tools/ablate_attn.sh, -DGDF_ATTN_TRACE): shader-clock time per loop phase, summed over the tiles of wave 0 of
-// every workgroup: [QK^T, softmax, PV, stage + barrier + next loads, whole kernel]
-#if defined(GDF_ATTN_TRACE)
-__device__ unsigned long long gdf_attn_trace[8192 * 8];
-#define GDF_AT_ENTRY const unsigned long long at_entry = __builtin_readcyclecounter();
-#define GDF_AT_DECL unsigned long long at_acc[4] = {0, 0, 0, 0}; unsigned long long at_t = __builtin_readcyclecounter(); const unsigned long long at_t0 = at_t; \
-    if (threadIdx.x == 0 && blockIdx.x < 8192) gdf_attn_trace[blockIdx.x * 8 + 5] = at_t0 - at_entry;
-#define GDF_AT_EXIT do { if (threadIdx.x == 0 && blockIdx.x < 8192) gdf_attn_trace[blockIdx.x * 8 + 6] = __builtin_readcyclecounter() - at_entry; } while (0)
-#define GDF_AT(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); at_acc[i] += n_ - at_t; at_t = n_; } while (0)
-#define GDF_AT_END do { if (threadIdx.x == 0 && blockIdx.x < 8192) { for (int i_ = 0; i_ < 4; ++i_) gdf_attn_trace[blockIdx.x * 8 + i_] = at_acc[i_]; \
-    gdf_attn_trace[blockIdx.x * 8 + 4] = __builtin_readcyclecounter() - at_t0; } } while (0)
-#else
-#define GDF_AT_ENTRY
-#define GDF_AT_DECL
-#define GDF_AT_EXIT
-#define GDF_AT(i)
-#define GDF_AT_END
-#endif
-#if !defined(GDF_ATTN_PRIO)
-#define GDF_ATTN_PRIO 1
-#endif
-#if GDF_ATTN_PRIO == 1          // MFMA phases at priority 1 (shipped)
-#define GDF_ATTN_PRIO_MFMA(x) __builtin_amdgcn_s_setprio(x)
-#elif GDF_ATTN_PRIO == 2        // experiment: the softmax (VALU) phase at priority 1 instead
-#define GDF_ATTN_PRIO_MFMA(x) __builtin_amdgcn_s_setprio(1 - (x))
-#else                           // experiment: no priorities
-#define GDF_ATTN_PRIO_MFMA(x)
-#endif
 // (Round 4, measured and rejected: v_pk_fma_f32 / v_pk_add_f32 (inline asm: the compiler scalarises a <2 x float> fma whose lanes are extracted) for the
 // softmax's scale-and-shift and row sum, halving those 96 VALU instructions per tile: 731-740 vs 755-760 TFLOP/s at D = 64, 910 vs 957-969 on the Flux joint
 // shape — the opaque asm blocks cost the scheduler more than the issue slots save.)
@@ -124,7 +93,7 @@ __device__ unsigned long long gdf_attn_trace[8192 * 8];
 // 128 v_fma take 533 + 321 cycles whether they come from one wave, interleaved, or from two waves — only transcendentals do
 // (16 MFMAs + 64 v_exp: 727 cycles against 533 and 644 alone).  The loop's bound is therefore MFMA + plain-VALU + LDS-read issue
 // time, and the lever is the instruction count, not the placement.)
-// OCC = workgroups per CU the register budget is sized for (2; 1 only in the GDF_ATTN_QW4 experiment below)
+// OCC = workgroups per CU the register budget is sized for (2; 1 for the split q / k / v pair kernels, QKP below)
 // PV16 (round 5, head dims whose 16-row padding is smaller than their 32-row padding: 40 -> 48 instead of 64, 72 / 80 -> 80 instead of 96): O^T += V^T P^T on
 // mfma_f32_16x16x32_f16.  The S^T accumulator of the 32x32x16 score MFMAs keeps queries 0-15 in lane rows 0 / 2 and queries 16-31 in rows 1 / 3 (a row = 16
 // lanes); one v_permlane16_swap per pair of packed P registers (X = keys {0-3, 8-11} + 4 lh, Y = keys {16-19, 24-27} + 4 lh of a 32-key block) turns them into
@@ -136,7 +105,6 @@ __device__ unsigned long long gdf_attn_trace[8192 * 8];
 // full split (DESIGN.md 3.9 h: 8.0e-4 on the worst hook by itself).  2.5 x the MFMAs (3 x Q K^T, 2 x P V); K_lo / V_lo tiles are staged like K / V.
 template <int D, int QW, int NW = 4, bool BF = false, int OCC = 2, bool PV16 = false, bool QKP = false>
 __global__ __launch_bounds__(NW * 64, OCC) void attn_kernel(const AttnParams p) {
-  GDF_AT_ENTRY
   static_assert(!PV16 || !BF, "the 16-row P V form is fp16 only");
   static_assert(!QKP || (!PV16 && !BF), "split q / k / v pairs: fp16, 32x32x16 form");
   typedef float f32x4_t __attribute__((ext_vector_type(4)));
@@ -294,7 +262,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kernel(const AttnParams p) 
   // Fast tile load (tiles that lie inside one region and hold KT valid keys): buffer loads with a
   // per-lane byte offset computed ONCE and the tile's row offset in the scalar operand — no per-tile address arithmetic (the
   // generic form above spends ~25 VALU instructions per tile on clamping, region select and 64-bit address math, 10 % of the
-  // loop's VALU work; tools/ablate_attn.py: the K / V global loads cost 12-15 % of the kernel, their LDS stores nothing).
+  // loop's VALU work; profiles/r02_attn_ablation.txt: the K / V global loads cost 12-15 % of the kernel, their LDS stores nothing).
   // Padded head dims (40 / 80) take the same path: a pad chunk's lane re-reads one of the row's own VALID chunks instead of being
   // zero-filled — K's pad columns meet the zero pad columns of the Q fragments, V's pad columns only reach O^T rows d >= D that
   // are never stored — so the loads stay unconditional, in bounds, and finite whenever the row itself is.
@@ -335,13 +303,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kernel(const AttnParams p) 
   load_tile(0);
   lstore(0);
   __syncthreads();
-#if defined(GDF_ATTN_ABLATE) && (GDF_ATTN_ABLATE & 1)
-  lstore(1);                                   // diagnostics (tools/ablate_attn.sh): no K / V traffic inside the loop
-  __syncthreads();
-#else
   if (ntiles > 1) load_tile(1);
-#endif
-  GDF_AT_DECL
   // Fragment addresses = one lane-dependent LDS pointer per operand (opaque to the optimiser, which otherwise rebuilds every
   // fragment address with its own VALU adds: ~30 per tile; VALU issue time adds to MFMA time on this hardware, tools/micro/overlap.hip)
   // + the ring buffer's offset (one add per tile) + compile-time constants (key block, k-step) in the instruction's immediate.
@@ -368,17 +330,14 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kernel(const AttnParams p) 
     LDS_AS const char* const vlt = vl + BUF * (KT * LDV * 2);
     [[maybe_unused]] LDS_AS const char* const kllt = kll + BUF * (KT * LDR * 2);
     [[maybe_unused]] LDS_AS const char* const vllt = vll + BUF * (KT * LDV * 2);
-    GDF_AT(3);
 
     // ---- S^T = K Q^T : two 32-key blocks; every K fragment feeds QW query blocks ----
     // Fragment reads run PD steps ahead of the MFMAs that consume them (round 2: the compiler's order — read, wait, multiply —
-    // exposed the LDS latency at every step; tools/trace_attn.py: QK^T 766 and PV 1622 cycles per tile for 512 cycles of MFMA each)
+    // exposed the LDS latency at every step: a per-phase cycle trace gave QK^T 766 and PV 1622 cycles per tile for 512 cycles of MFMA each;
+    // the same trace after the change: profiles/r02_attn_ablation.txt)
     f32x16 s[QW][2];
     constexpr int NQK = NS * 2 * (QKP ? 2 : 1);  // K fragments per tile, step i -> (st = i / 2, kb = i % 2): the key blocks alternate (QKP: then K_lo's)
     auto rdk = [&](int i) -> f16x8 {
-#if defined(GDF_ATTN_ABLATE) && (GDF_ATTN_ABLATE & 64)
-      return qf[0][i % NS];                              // diagnostics: no K fragment reads
-#endif
       if constexpr (QKP) if (i >= NS * 2) {              // steps NQK0 .. 2 NQK0 - 1: the same fragments of the K_lo tile
         const int j = i - NS * 2;
         return *(LDS_AS const f16x8*)(kllt + ((j & 1) * 32 * LDR + 16 * (j >> 1)) * 2);
@@ -402,9 +361,6 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kernel(const AttnParams p) 
       const bool vlo = QKP && i >= 4 * NDB;      // steps 4 NDB .. 8 NDB - 1: the same fragments of the V_lo tile
       const int i0 = vlo ? i - 4 * NDB : i;
       const int s4 = i0 / NDB, db = i0 - s4 * NDB;
-#if defined(GDF_ATTN_ABLATE) && (GDF_ATTN_ABLATE & 32)
-      return qf[0][(s4 + db) % NS];                      // diagnostics: no V^T fragment reads
-#endif
       // V^T fragment: lane (d = db*32 + lq, lh) needs V[16 s4 + 4 lh + {0..3}][d] and V[16 s4 + 8 + 4 lh + {0..3}][d]
       // (row 4 lh + (i16 >> 2), column 16 ((lane >> 4) & 1) + 4 (i16 & 3) are in `vl`)
       LDS_AS const char* vp = ((QKP && vlo) ? vllt : vlt) + (16 * s4 * LDV + db * 32) * 2;
@@ -414,7 +370,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kernel(const AttnParams p) 
       vf.q[0] = lo; vf.q[1] = hi;
       return vf.h;
     };
-    GDF_ATTN_PRIO_MFMA(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int i = 0; i < NQK; ++i) {
       const bool klo = QKP && i >= NS * 2;       // a K_lo fragment: contracts with Q_hi only (the lo x lo term is 2^-22 relative)
@@ -446,8 +402,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kernel(const AttnParams p) 
     f16x8 vq[PD];
 #pragma unroll
     for (int i = 0; i < PD; ++i) vq[i] = rdv(i);
-    GDF_ATTN_PRIO_MFMA(0);
-    GDF_AT(0);
+    __builtin_amdgcn_s_setprio(0);
     // ---- mask the tail tile, online softmax (per-lane query column) ----
     if ((t + 1) * KT > Sk) {
 #pragma unroll
@@ -464,13 +419,11 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kernel(const AttnParams p) 
 #pragma unroll
     for (int w = 0; w < QW; ++w) {
       float mx = s[w][0][0];
-#if !(defined(GDF_ATTN_ABLATE) && (GDF_ATTN_ABLATE & 2))
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[w][kb][r]);
       mx = half_max(mx) * sl2;
-#endif
       // lazy rescale: the running max only moves when the new one exceeds it by more than 2^8 (probabilities then stay
       // <= 256 in fp16 and the fp32 accumulators never need the per-tile alpha multiply after the first tiles)
       const float m_new = (mx > m_run[w] + 8.0f) ? mx : m_run[w];
@@ -479,18 +432,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kernel(const AttnParams p) 
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
-#if defined(GDF_ATTN_ABLATE) && (GDF_ATTN_ABLATE & 2)
-          const float e0 = s[w][kb][r], e1 = s[w][kb][r + 1];      // diagnostics: no exp / fma / sum
-#else
-#if defined(GDF_ATTN_ABLATE) && (GDF_ATTN_ABLATE & 128)
-          const float e0 = s[w][kb][r] * sl2 - m_new;                  // diagnostics: everything but the v_exp_f32
-          const float e1 = s[w][kb][r + 1] * sl2 - m_new;
-#else
           const float e0 = __builtin_amdgcn_exp2f(s[w][kb][r] * sl2 - m_new);
           const float e1 = __builtin_amdgcn_exp2f(s[w][kb][r + 1] * sl2 - m_new);
-#endif
           psum += e0 + e1;
-#endif
           const f16x2_t h2 = cvt_pair<BF>(e0, e1);
           pf[w][kb * 2 + (r >> 3)][r & 7] = h2[0];
           pf[w][kb * 2 + (r >> 3)][(r & 7) + 1] = h2[1];
@@ -520,8 +464,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kernel(const AttnParams p) 
     }
 
     // ---- O^T += V^T P^T : 4 steps of 16 (relabelled) keys; every V^T fragment feeds QW query blocks ----
-    GDF_AT(1);
-    GDF_ATTN_PRIO_MFMA(1);
+    __builtin_amdgcn_s_setprio(1);
     if constexpr (PV16) {
       // P: S^T layout -> 16x16x32 B operands (one permlane16_swap per packed register pair, see the kernel's header comment)
       f16x8 pa[QW][2], pb[QW][2];                // [key block of 32]: queries 0-15 / 16-31 of the wave's 32-query block
@@ -563,29 +506,13 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kernel(const AttnParams p) 
     }
     }
 
-    GDF_ATTN_PRIO_MFMA(0);
-    GDF_AT(2);
+    __builtin_amdgcn_s_setprio(0);
     // ---- stage tile t+1 into the other buffer (last read during tile t-1, fenced by the previous barrier) ----
-#if defined(GDF_ATTN_ABLATE) && (GDF_ATTN_ABLATE & 1)
-#if !(GDF_ATTN_ABLATE & 4)
-    __syncthreads();
-#endif
-#elif defined(GDF_ATTN_ABLATE) && (GDF_ATTN_ABLATE & 8)
-    if (t + 1 < ntiles) lstore(BUF ^ 1);         // diagnostics: LDS stores of stale registers, no global loads
-    __syncthreads();
-#elif defined(GDF_ATTN_ABLATE) && (GDF_ATTN_ABLATE & 16)
-    __syncthreads();                                 // diagnostics: global loads, no LDS stores
-    if (t + 2 < ntiles) load_tile(t + 2);
-    asm volatile("" :: "v"(kreg[0]), "v"(vreg[0]), "v"(kreg[NCH - 1]), "v"(vreg[NCH - 1]));
-#else
     if (t + 1 < ntiles) lstore(BUF ^ 1);
     __syncthreads();
     if (t + 2 < ntiles) load_tile(t + 2);           // HBM latency hides under the next tile's MFMAs
-#endif
   }
 
-  GDF_AT(3);
-  GDF_AT_END;
   // ---- finalize: O[q][d] = O^T[d][q] / l ----
   // The accumulators hold O^T (lane = query column): stored directly, every lane would write 8 bytes into a different row.
   // Each wave transposes its QBW x D block through the (now idle) K / V staging memory instead, so that the global stores
@@ -687,7 +614,6 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kernel(const AttnParams p) 
           *(f16x8*)(p.o + seg_row(b, q, p.Sq, p.seg_T, p.B, p.Sq) * p.ldo + head * D + oc + p.o_lo) = *(const f16x8*)(stg + r * RSH + oc);
       }
     }
-    GDF_AT_EXIT;
     return;
   }
   if constexpr (PV16) {
@@ -1173,23 +1099,6 @@ static hipError_t launch_d(const AttnParams& p, hipStream_t s) {
     // workgroups: pick by rate x fill of the 512 workgroup slots
     const long nb2 = (long)p.B * p.heads * ((p.Sq + 255) / 256), nb1 = (long)p.B * p.heads * ((p.Sq + 127) / 128);
     auto fill = [](long n, long slots) { const long r = (n + slots - 1) / slots; return (double)n / (double)(r * slots); };
-#if defined(GDF_ATTN_QW4)
-    // experiment (tools/build_variant.sh qw4 -DGDF_ATTN_QW4=4 | =3): ONE wave per SIMD holding 4 (3) query blocks of 32 rows — every K / V fragment
-    // read from LDS feeds 4 (3) MFMAs, all 512 registers to one wave (result in DESIGN.md §3.11)
-#if GDF_ATTN_QW4 == 28       // 8 waves x 2 query blocks, one workgroup per CU: every staged K / V tile serves 512 query rows (half the L2 -> LDS traffic)
-    if (!BF && D == 64 && p.Sq >= 1024) {
-      const int nqb = (p.Sq + 511) / 512;
-      hipLaunchKernelGGL((attn_kernel<D, (D == 64) ? 2 : 1, 8, false, 1>), dim3(p.B * p.heads * nqb), dim3(512), 0, s, p);
-      return hipGetLastError();
-    }
-#endif
-    if (!BF && D == 64 && p.Sq >= 1024) {
-      constexpr int Q4 = (D == 64 && GDF_ATTN_QW4 <= 4) ? GDF_ATTN_QW4 : 1;
-      const int nqb = (p.Sq + 128 * Q4 - 1) / (128 * Q4);
-      hipLaunchKernelGGL((attn_kernel<D, Q4, 4, false, 1>), dim3(p.B * p.heads * nqb), dim3(256), 0, s, p);
-      return hipGetLastError();
-    }
-#endif
     // split q / k / v pairs (AttnParams::q_lo / kv_lo, the full-split UNet plans): 8 waves x 32 query rows share the four staged tiles (K, K_lo, V, V_lo), one
     // workgroup per CU; head dims whose tiles do not fit (160) or do not split evenly over 512 threads use 4 waves / fall through to the hi halves
     if constexpr (!BF && D <= 80 && D >= 40) {
@@ -1200,10 +1109,10 @@ static hipError_t launch_d(const AttnParams& p, hipStream_t s) {
         return hipGetLastError();
       }
     }
-    // round 5: P V on mfma_f32_16x16x32_f16 where the 16-row padding of D is smaller than the 32-row one (40 / 72 / 80); GDF_ATTN_PV16=0 / 1: A/B switch
+    // round 5: P V on mfma_f32_16x16x32_f16 where the 16-row padding of D is smaller than the 32-row one (40 / 72 / 80).  Same-box A/B against
+    // the 32x32x16 form: D = 40 564 -> 604 (B = 32: 589 -> 640), D = 72 674 -> 715, D = 80 659 -> 703 TFLOP/s (profiles/r05_ab_attn_pv16.txt)
     constexpr bool pv16c = !BF && ((D + 15) / 16 * 16 < (D + 31) / 32 * 32);
-    static const bool pv16 = [] { const char* e = getenv("GDF_ATTN_PV16"); return e ? atoi(e) != 0 : GDF_ATTN_PV16_DEFAULT; }();
-    if (pv16c && pv16) {
+    if constexpr (pv16c) {
       if (can2 && p.Sq >= 512 && 1.00 * fill(nb2, 512) >= 0.80 * fill(nb1, 512)) {
         const int nqb = (p.Sq + 255) / 256;
         hipLaunchKernelGGL((attn_kernel<D, can2 ? 2 : 1, 4, false, 2, pv16c>), dim3(p.B * p.heads * nqb), dim3(256), 0, s, p);
@@ -1211,9 +1120,7 @@ static hipError_t launch_d(const AttnParams& p, hipStream_t s) {
         const int nqb = (p.Sq + 127) / 128;
         hipLaunchKernelGGL((attn_kernel<D, 1, 4, false, 2, pv16c>), dim3(p.B * p.heads * nqb), dim3(256), 0, s, p);
       }
-      return hipGetLastError();
-    }
-    if (!BF && can2 && p.Sq >= 512 && 1.00 * fill(nb2, 512) >= 0.80 * fill(nb1, 512)) {
+    } else if (!BF && can2 && p.Sq >= 512 && 1.00 * fill(nb2, 512) >= 0.80 * fill(nb1, 512)) {
       const int nqb = (p.Sq + 255) / 256;
       hipLaunchKernelGGL((attn_kernel<D, can2 ? 2 : 1>), dim3(p.B * p.heads * nqb), dim3(256), 0, s, p);
     } else if (D == 128 && p.Sq >= 1024) {
@@ -1246,9 +1153,3 @@ hipError_t launch_attention(const AttnParams& p, hipStream_t s) {
 }
 
 }  // namespace gdf
-
-#if defined(GDF_ATTN_TRACE)
-extern "C" int gdf_debug_attn_trace(unsigned long long* dst, int n_words) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(gdf::gdf_attn_trace), (size_t)n_words * 8, 0, hipMemcpyDeviceToHost);
-}
-#endif

@@ -52,20 +52,12 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p) {
   // Persistent form: the launcher may start fewer workgroups than tiles (one per CU for the two-group 256x256 kernels); workgroup b
   // then walks the tiles b, b + gridDim.x, ... — with gridDim.x a multiple of 8 these are the tiles the hardware would have given the
   // same XCD round after round, so the super-block order below is unchanged.  Saves the workgroup relaunch between rounds
-  // (tools/trace_gemm.py: 2.6 us from a tile's last instruction to the first of the next tile on that CU, of ~37 us per tile at
+  // (profiles/r02_gemm_tile_trace.txt: 2.6 us from a tile's last instruction to the first of the next tile on that CU, of ~37 us per tile at
   // K = 1280) and the kernel-argument / descriptor setup.  A plain launch has gridDim.x == nblk: one trip.
   // Compiled as a loop only where the register budget has room for the loop-carried lane constants (256x320: 9-11 VGPRs spilled).
   constexpr bool PERSIST = (STAGES == 8);
   int vb = blockIdx.x;
-#if defined(GDF_STAGGER)                                        // diagnostics build (tools/build_variant.sh stagger -DGDF_STAGGER): the de-phasing experiment
-  if (p.stagger > 0 && (int)blockIdx.x < p.stagger_wgs) {      // (kernels.h GemmParams::stagger); uniform per workgroup
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long d = (unsigned long long)(p.stagger & 0xffffff) * (unsigned)((blockIdx.x >> 3) % (unsigned)(p.stagger >> 24));
-    while (__builtin_amdgcn_s_memrealtime() - t0 < d) __builtin_amdgcn_s_sleep(16);
-  }
-#endif
   do {
-  GDF_TR(0); GDF_TR_ID();
   t.locate(vb, tiles_n, nblk);
   f32x4 acc[T::FM][T::FN];
 #pragma unroll
@@ -75,22 +67,8 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p) {
   if constexpr (STAGES == 8) gemm_mainloop_8phase_256(t, acc);
   else if constexpr (STAGES == 9) gemm_mainloop_8phase_320(t, acc);
   else gemm_mainloop_ring(t, acc);
-#if defined(GDF_ABLATE_EPI) && GDF_ABLATE_EPI == 2
-  wait_vmcnt<0>();
-#endif
   __syncthreads();   // all waves finished reading the last tile: LDS is free for epilogue staging
-  GDF_TR(3);
-#if defined(GDF_ABLATE_EPI) && GDF_ABLATE_EPI == 1
-  // diagnostics build (tools/ab_epilogue_bound.sh): NO epilogue — the accumulators are kept alive and dropped.  Results are garbage; the
-  // time per launch is what a PERFECTLY overlapped epilogue would leave (the bound on any deferred-epilogue scheme).
-#pragma unroll
-  for (int i = 0; i < T::FM; ++i)
-#pragma unroll
-    for (int j = 0; j < T::FN; ++j) asm volatile("" ::"v"(acc[i][j]));
-#else
   gemm_epilogue(t, acc);
-#endif   // GDF_ABLATE_EPI == 1
-  GDF_TR(4);
   if constexpr (!PERSIST) break;
   vb += gridDim.x;
   if (vb >= nblk) break;
@@ -170,8 +148,7 @@ static hipError_t launch_t(const GemmParams& p, hipStream_t s) {
   q.sb_gm = q.sb_gn = 0;
   if (!p.no_superblock) {
     const int conc = (p.cus > 0 ? p.cus / 8 : 32) * ((BM == 256) ? 1 : 2);   // workgroups one XCD keeps resident (32 CUs x 1 or 2; a CU partition: cus / 8)
-    static const int gn_max = [] { const char* e = getenv("GDF_SB_GN_MAX"); return e ? atoi(e) : 4; }();   // diagnostics: widest super-block
-    for (int gn = gn_max; gn >= 2; gn >>= 1) {
+    for (int gn = 4; gn >= 2; gn >>= 1) {                                     // widest super-block: 4 tiles
       const int gm = conc / gn;
       if (tiles_n % gn == 0 && tiles_m % gm == 0 && (tiles_m / gm) * (tiles_n / gn) >= 8 && tiles_n > gn) {
         q.sb_gm = gm; q.sb_gn = gn;
@@ -181,15 +158,6 @@ static hipError_t launch_t(const GemmParams& p, hipStream_t s) {
   }
   int gx = tiles_m * tiles_n;
   const int pw = (p.cus > 0 && p.cus < persist_wgs()) ? p.cus : persist_wgs();
-  {
-    // de-phasing experiment (kernels.h GemmParams::stagger): GDF_STAGGER_US = delay in microseconds, applied to launches of >= GDF_STAGGER_MIN_ROUNDS
-    // (default 2) rounds of one-workgroup-per-CU tiles
-    static const float us = [] { const char* e = getenv("GDF_STAGGER_US"); return e ? (float)atof(e) : 0.f; }();
-    static const int min_rounds = [] { const char* e = getenv("GDF_STAGGER_MIN_ROUNDS"); return e ? atoi(e) : 2; }();
-    q.stagger = 0; q.stagger_wgs = 0;
-    static const int groups = [] { const char* e = getenv("GDF_STAGGER_GROUPS"); return e ? atoi(e) : 2; }();   // delay of workgroup b: ((b >> 3) % groups) x us
-    if (us > 0.f && groups > 1 && BM == 256 && pw < (1 << 30) && gx >= min_rounds * pw) { q.stagger = (int)(us * 100.f) | (groups << 24); q.stagger_wgs = pw; }
-  }
   if (STAGES == 8 && gx > pw && !(p.batch > 1)) gx = pw;   // persistent: one workgroup per CU walks the tiles
   const dim3 grid(gx, (STAGES == 2 && p.splitk > 1) ? p.splitk : p.batch > 1 ? p.batch : 1);
   if constexpr (MX) hipLaunchKernelGGL((gemm_mx_kernel<BM, BN, STAGES>), grid, dim3(BM * 2), smem, s, q);
@@ -518,9 +486,3 @@ hipError_t launch_gemm_splitk(const GemmParams& p, int splitk, float* ws, hipStr
 }
 
 }  // namespace gdf
-
-#if defined(GDF_TRACE)
-extern "C" int gdf_debug_trace(unsigned long long* dst, int n_words) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(gdf::gdf_trace), (size_t)n_words * 8, 0, hipMemcpyDeviceToHost);
-}
-#endif

@@ -1,5 +1,5 @@
 // Shared pieces of the MFMA GEMM / implicit-GEMM convolution family for gfx950 (csrc/gemm.hip): vector types, the LDS-DMA primitive,
-// MFMA wrappers, 16-bit store conversions, GELU forms, the XCD-aware tile order, diagnostics macros.
+// MFMA wrappers, 16-bit store conversions, GELU forms, the XCD-aware tile order.
 // Split out of gemm.hip in round 6 together with gemm_tile.h (tile geometry + operand address generators),
 // gemm_mainloop_ring.h / gemm_mainloop_8phase.h (the main loops) and gemm_epilogue.h; every kernel's machine code is unchanged
 // (tools/isa_fingerprint.py, profiles/r06_gemm_split_isa_fingerprint.txt).
@@ -59,7 +59,7 @@ __device__ __forceinline__ void wait_vmcnt() {
 
 // exact (erf) GELU, two values at a time (the GEGLU epilogue evaluates 64 per lane; at 2 waves per SIMD the VALU time of the
 // round-1 form — Abramowitz-Stegun 7.1.26 with one v_rcp_f32 + one v_exp_f32 and ~15 scalar-float ops — was 5.4 us of a 37-us
-// tile, tools/trace_gemm.py).  With u = |x| and q(u) = 1 - Phi(u) = erfc(u / sqrt 2) / 2:
+// tile, profiles/r02_gemm_tile_trace.txt).  With u = |x| and q(u) = 1 - Phi(u) = erfc(u / sqrt 2) / 2:
 //     gelu(x) = x Phi(x) = max(x, 0) - u q(u),        q(u) = 2^P(u),  P = degree-7 fit of log2 q on [0, 5.5], P(0) = -1
 // ONE transcendental, and the Horner chain + the final ops run as packed fp32 (v_pk_fma_f32: two lanes' worth per issue).
 // |gelu - exact| <= 6.5e-7 absolute and <= 5.4e-6 relative on x > -4.5 (fp16 output rounding: 4.9e-4); u is clamped at 5.5,

@@ -7,31 +7,19 @@
 
 namespace gdf {
 
-#if defined(GDF_EXP_OLD_BUNITS)         // diagnostics: the pre-round-6 B staging units (row halves instead of read phases)
-#define GDF_OLD_BUNITS true
-#else
-#define GDF_OLD_BUNITS false
-#endif
 template <class T>
 __device__ __forceinline__ void gemm_mainloop_8phase_256(T& t, f32x4 (&acc)[T::FM][T::FN]) {
   GDF_TILE_GEOMETRY(T);
   GDF_TILE_STATE(t);
   GDF_TILE_OPERANDS(t);
   // ---- 8-phase schedule (256x256 dense tile, 2 K-tile buffers of 64 KiB) ----
-  // The two waves of a SIMD (w, w + 4) belong to two groups that run ONE BARRIER apart: while one group multiplies a
-  // quadrant of its 64x128 wave tile (16 MFMAs) the other reads its next fragments from LDS and issues
-  // its share of the next half-tile DMA, then they swap (2 barriers per phase, 4 phases per K-tile).  The MFMA pipe of
-  // every SIMD therefore always has a wave that is multiplying.  DMA runs 1.5 K-tiles ahead in 16-KiB half-tiles
-  // (A rows 0-127 / 128-255, B rows likewise; every wave issues 2 of a half-tile's 16 instructions), the one counted wait
-  // per K-tile leaves three half-tiles in flight:
-  //   K-tile T (buffer T & 1)   phase 1: read A (all 64 rows) + B cols 0-63     stage B-hi of T+1      MFMA (A0,B0)
-  //                             phase 2:                                        stage A-lo of T+2      MFMA (A1,B0)
-  //                             phase 3: read B cols 64-127, retire the reads   stage A-hi of T+2      MFMA (A1,B1)
-  //                             phase 4: wait vmcnt(6) = tile T+1 has landed    stage B-lo of T+2      MFMA (A0,B1)
-  // Slot lifetimes (why each staging is safe): A slots are last read in phase 1 (A-lo by group 0 only, A-hi by group 1
-  // only), B slots in phase 3 with the reads retired (lgkmcnt) BEFORE the reader's next barrier; a slot is restaged by
-  // a wave that has passed a barrier the last reader arrived at after retiring its reads.  Tiles >= nk are staged too
-  // (garbage or zeros, never read) so that the wait count is the same in every iteration.
+  // The two waves of a SIMD (w, w + 4) belong to two groups that run ONE BARRIER apart: while one group multiplies half of
+  // its 64x128 wave tile (32 MFMAs) the other reads its next fragments from LDS and issues its share of the next half-tile
+  // DMA, then they swap (2 barriers per phase, 2 phases per K-tile: the table at the K loop below).  The MFMA pipe of every
+  // SIMD therefore always has a wave that is multiplying.  DMA runs 1.5 K-tiles ahead in 16-KiB half-tiles (A rows 0-127 /
+  // 128-255, B in the two staging units below; every wave issues 2 of a half-tile's 16 instructions), the one counted wait
+  // per K-tile leaves three half-tiles in flight.  Tiles >= nk are staged too (garbage or zeros, never read) so that the
+  // wait count is the same in every iteration.
   static_assert((MODE == A_DENSE || MODE == A_CONV3) && BM == 256 && (BN == 256 || BN == 320) && FM == 4 && FN == BN / 32, "8-phase schedule: 4x2 waves of 64 x BN/2");
   // A half-tile = 128 rows = 16 DMA instructions, 2 per wave.  B half-tile = BN/2 rows: 16 instructions (2 per wave) at
   // BN = 256; 20 at BN = 320: the group whose turn it is (group 0 for B-lo, group 1 for B-hi) issues 3 per wave, the other 2,
@@ -47,7 +35,7 @@ __device__ __forceinline__ void gemm_mainloop_8phase_256(T& t, f32x4 (&acc)[T::F
   // Until round 6 the units were the row halves 0-127 / 128-255: waves 5 and 7 then restaged rows 80-95 / 112-127 of the current buffer in the very
   // phase in which waves 4 and 6 read them.  With real tiles the DMA needs ~1 us and the reads always won; the tiles staged past the end of K were
   // out-of-range loads (zeros, ~100 cycles) and, with a second stream's waves on the CU, beat the reads about once in 10^3 launches: 64 rows x 16
-  // columns of a tile computed without its last K-tiles (tools/micro/op_race.py, tools/ab_race_variants.sh, profiles/r06_concurrent_streams.txt).
+  // columns of a tile computed without its last K-tiles (tools/micro/op_race.py, profiles/r06_concurrent_streams.txt).
   auto b_unit_row = [&](int unit, int j) { return (wave >> 2) * 128 + unit * 64 + ((wave & 3) * 2 + j) * 8; };
   uint32_t ha[2][2], hb[2][3];                        // ha: DENSE byte offset of (row, chunk); CONV byte offset of filter tap (0, 0)
   uint32_t hm[2][2];                                  // CONV: validity mask of the 9 taps (conv_row)
@@ -68,7 +56,7 @@ __device__ __forceinline__ void gemm_mainloop_8phase_256(T& t, f32x4 (&acc)[T::F
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      const int r = (B3 || GDF_OLD_BUNITS ? h * BHALF + (hbq[h] + j) * 8 : b_unit_row(h, j)) + lrow;
+      const int r = (B3 ? h * BHALF + (hbq[h] + j) * 8 : b_unit_row(h, j)) + lrow;
       hb[h][j] = (n0 + r < p.N) ? (uint32_t)(n0 + r) * ldb + (uint32_t)chunk * 16u : OOB;
     }
   }
@@ -82,7 +70,7 @@ __device__ __forceinline__ void gemm_mainloop_8phase_256(T& t, f32x4 (&acc)[T::F
       }
     } else {
       constexpr int H = W - 2;
-      char* base = smem + 2 * A_TILE + buf * B_TILE + ((B3 || GDF_OLD_BUNITS) ? H * (BHALF * 128) + hbq[H] * 1024 : b_unit_row(H, 0) * 128);
+      char* base = smem + 2 * A_TILE + buf * B_TILE + (B3 ? H * (BHALF * 128) + hbq[H] * 1024 : b_unit_row(H, 0) * 128);
 #pragma unroll
       for (int j = 0; j < 2; ++j) glds16(rsB, base + j * 1024, hb[H][j] + koffB(kt));
       if (B3 && (g1 == (H == 1))) glds16(rsB, base + 2 * 1024, hb[H][2] + koffB(kt));
@@ -127,7 +115,7 @@ __device__ __forceinline__ void gemm_mainloop_8phase_256(T& t, f32x4 (&acc)[T::F
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int jj = 0; jj < FNH; ++jj) {
-          const int j = GDF_SNAKE(i, jj, FNH);
+          const int j = snake(i, jj, FNH);
           acc[AH * 2 + i][BH * FNH + j] = mfma_mx8(a8[AH * 2 + i][0], a8[AH * 2 + i][1], b8[j][0], b8[j][1], acc[AH * 2 + i][BH * FNH + j]);
         }
     } else {
@@ -137,7 +125,7 @@ __device__ __forceinline__ void gemm_mainloop_8phase_256(T& t, f32x4 (&acc)[T::F
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int jj = 0; jj < FNH; ++jj) {
-            const int j = GDF_SNAKE(i + kk, jj, FNH);
+            const int j = snake(i + kk, jj, FNH);
             acc[AH * 2 + i][BH * FNH + j] = mfma16<BF>(a8[AH * 2 + i][kk], b8[j][kk], acc[AH * 2 + i][BH * FNH + j]);
           }
     }
@@ -153,15 +141,12 @@ __device__ __forceinline__ void gemm_mainloop_8phase_256(T& t, f32x4 (&acc)[T::F
 
   stage(0, 0, ALO); stage(0, 0, AHI); stage(0, 0, BLO); stage(0, 0, BHI);
   stage(1, 1, ALO); stage(1, 1, AHI); stage(1, 1, BLO);
-  GDF_TR(1);
   wait_tile();                     // this wave's share of K-tile 0
   bar();                           // ... everyone's
-  GDF_TR(2);
   if (g1) bar();                   // group 1 runs one barrier behind group 0
-#if !defined(GDF_PHASES4)
-  // TWO phases of 32 MFMAs per K-tile (round 2; the round-1 schedule below ran four phases of 16).  Per barrier interval one
+  // TWO phases of 32 MFMAs per K-tile (round 2; the round-1 schedule ran four phases of 16).  Per barrier interval one
   // group multiplies while the other reads fragments / issues DMA; the hand-over itself costs ~115 cycles per interval
-  // (MFMA + barrier skeleton without reads and DMA: 70 % of the MFMA peak with 16-MFMA clusters, tools/ablate_gemm.py), so
+  // (MFMA + barrier skeleton without reads and DMA: 70 % of the MFMA peak with 16-MFMA clusters, profiles/r02_gemm_ablation.txt), so
   // twice as long clusters halve that overhead with the SAME registers (A stays resident, the B halves take turns in b8), the
   // same accumulation order (bit-identical results) and the same prefetch depth (the three youngest half-tiles stay in flight
   // at the one counted wait).  Measured, 4 -> 2 phases: Flux QKV 1285 -> 1357, proj_out 1395 -> 1483, 8192^3 1412 -> 1501
@@ -186,14 +171,9 @@ __device__ __forceinline__ void gemm_mainloop_8phase_256(T& t, f32x4 (&acc)[T::F
     //      the early arriver at this barrier (the other one is multiplying), so the wait is hidden.
     // Tiles past the end of K are still staged (out-of-range loads: zeros, landing ~10x sooner than a real tile — the only DMA that ever won
     // the race), now into slots nobody reads any more; skipping them with a branch costs 24 VGPRs (GEGLU 227 -> 251, fp8 kernel 33 -> 206
-    // spills).  Same accumulation order: bit-identical results.  A/B of the old and new forms under concurrency: tools/ab_race_variants.sh.
-#if defined(GDF_EXP_OLD_LGKM)          // diagnostics (tools/ab_race_variants.sh): the pre-round-6 order, reads retired AFTER the barrier
-    rd_a(cur); rd_b(cur, 0); stage(kt + 1, cur ^ 1, BHI);
-    bar(); lgkm0(); mma_q(Q0, Q0); mma_q(Q1, Q0); bar();
-#else
+    // spills).  Same accumulation order: bit-identical results.  A/B of the old and new forms under concurrency: profiles/r06_concurrent_streams.txt.
     rd_a(cur); rd_b(cur, 0); stage(kt + 1, cur ^ 1, BHI); lgkm0();
     bar(); mma_q(Q0, Q0); mma_q(Q1, Q0); bar();
-#endif
     rd_b(cur, 1); stage(kt + 2, cur, ALO); stage(kt + 2, cur, AHI); stage(kt + 2, cur, BLO); wait_tile(); lgkm0();
     bar(); mma_q(Q1, Q1); mma_q(Q0, Q1); bar();
   };
@@ -206,31 +186,6 @@ __device__ __forceinline__ void gemm_mainloop_8phase_256(T& t, f32x4 (&acc)[T::F
       for (; kt < nk; ++kt) ktile(kt, kt & 1);
     }
   }
-#else
-  auto ktile4 = [&](int kt, const int cur) {
-    // phase 1
-    rd_a(cur); rd_b(cur, 0); stage(kt + 1, cur ^ 1, BHI); lgkm0();
-    bar(); mma_q(Q0, Q0); bar();
-    // phase 2
-    stage(kt + 2, cur, ALO);
-    bar(); mma_q(Q1, Q0); bar();
-    // phase 3
-    rd_b(cur, 1); stage(kt + 2, cur, AHI); lgkm0();
-    bar(); mma_q(Q1, Q1); bar();
-    // phase 4
-    stage(kt + 2, cur, BLO); wait_tile();
-    bar(); mma_q(Q0, Q1); bar();
-  };
-  {
-    int kt = 0;
-    if constexpr (MODE == A_DENSE) {
-      for (; kt + 1 < nk; kt += 2) { ktile4(kt, 0); ktile4(kt + 1, 1); }
-      if (kt < nk) ktile4(kt, 0);
-    } else {
-      for (; kt < nk; ++kt) ktile4(kt, kt & 1);
-    }
-  }
-#endif
   if (!g1) bar();
   wait_vmcnt<0>();                 // the over-staged tiles must not land in the epilogue's staging area
 }
@@ -315,7 +270,7 @@ __device__ __forceinline__ void gemm_mainloop_8phase_320(T& t, f32x4 (&acc)[T::F
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int jj = 0; jj < 5; ++jj) {
-          const int j = GDF_SNAKE(i + kk, jj, 5);
+          const int j = snake(i + kk, jj, 5);
           acc[Q * 2 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a4[i][kk], b10[j][kk], acc[Q * 2 + i][j], 0, 0, 0);
         }
   };
@@ -338,13 +293,8 @@ __device__ __forceinline__ void gemm_mainloop_8phase_320(T& t, f32x4 (&acc)[T::F
   //   phase 1: read B, A rows 0-63 of the wave tile     stage B_2, A_2, A_3 of T+1                        40 MFMAs
   //   phase 2: read A rows 64-127                       stage B_1, A_0, A_1 of T+2, wait vmcnt(5)         40 MFMAs
   // (vmcnt(5): the five instructions just issued may be in flight, everything older — all of tile T+1 — has landed)
-#if defined(GDF_PHASES4) || defined(GDF_ABLATE)
-  constexpr bool TWO_PHASE = false;
-#else
   constexpr bool TWO_PHASE = (MODE == A_DENSE) && !SPLIT;      // (the split-operand form of the two-phase loop spills 139 VGPRs)
-#endif
   stage_b(0, 0, B1); stage_b(0, 0, B2); stage_a(0, 0, 0); stage_a(0, 0, 1); stage_a(0, 0, 2); stage_a(0, 0, 3);
-  GDF_TR(1);
   if constexpr (TWO_PHASE) {
     stage_b(1, 1, B1); stage_a(1, 1, 0); stage_a(1, 1, 1);
     wait_vmcnt<5>();
@@ -353,7 +303,6 @@ __device__ __forceinline__ void gemm_mainloop_8phase_320(T& t, f32x4 (&acc)[T::F
     wait_vmcnt<8>();               // this wave's share of K-tile 0
   }
   bar();                           // ... everyone's
-  GDF_TR(2);
   if (g1) bar();                   // group 1 runs one barrier behind group 0
   if constexpr (TWO_PHASE) {
     f16x8 a8[4][2];
@@ -371,7 +320,7 @@ __device__ __forceinline__ void gemm_mainloop_8phase_320(T& t, f32x4 (&acc)[T::F
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int jj = 0; jj < 5; ++jj) {
-            const int j = GDF_SNAKE(i + kk, jj, 5);
+            const int j = snake(i + kk, jj, 5);
             acc[H * 4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a8[i][kk], b10[j][kk], acc[H * 4 + i][j], 0, 0, 0);
           }
     };
@@ -385,59 +334,23 @@ __device__ __forceinline__ void gemm_mainloop_8phase_320(T& t, f32x4 (&acc)[T::F
     for (; kt + 1 < nk; kt += 2) { ktile(kt, 0); ktile(kt + 1, 1); }
     if (kt < nk) ktile(kt, 0);
   } else {
-#if !defined(GDF_ABLATE)
-  auto ktile4 = [&](int kt, const int cur) {                  // ring [A0][A1][B0][B1]: see STAGES == 8
-    rd_ball(cur); rd_aq(cur, 0); stage_a(kt + 1, cur ^ 1, 3); lgkm0();
-    bar(); mma_q(P0); bar();
-    rd_aq(cur, 1); stage_b(kt + 2, cur, B1); lgkm0();
-    bar(); mma_q(P1); bar();
-    rd_aq(cur, 2); stage_b(kt + 2, cur, B2); stage_a(kt + 2, cur, 0); lgkm0();
-    bar(); mma_q(P2); bar();
-    rd_aq(cur, 3); stage_a(kt + 2, cur, 1); stage_a(kt + 2, cur, 2); wait_vmcnt<8>(); lgkm0();
-    bar(); mma_q(P3); bar();
-  };
-  {
+    auto ktile4 = [&](int kt, const int cur) {                // ring [A0][A1][B0][B1]: see STAGES == 8
+      rd_ball(cur); rd_aq(cur, 0); stage_a(kt + 1, cur ^ 1, 3); lgkm0();
+      bar(); mma_q(P0); bar();
+      rd_aq(cur, 1); stage_b(kt + 2, cur, B1); lgkm0();
+      bar(); mma_q(P1); bar();
+      rd_aq(cur, 2); stage_b(kt + 2, cur, B2); stage_a(kt + 2, cur, 0); lgkm0();
+      bar(); mma_q(P2); bar();
+      rd_aq(cur, 3); stage_a(kt + 2, cur, 1); stage_a(kt + 2, cur, 2); wait_vmcnt<8>(); lgkm0();
+      bar(); mma_q(P3); bar();
+    };
     int kt = 0;
     if constexpr (MODE == A_DENSE) {
       for (; kt + 1 < nk; kt += 2) { ktile4(kt, 0); ktile4(kt + 1, 1); }
       if (kt < nk) ktile4(kt, 0);
-    } else {                                                 // conv: the unrolled form spills 6-7 VGPRs; 4 v_add per K-tile instead
+    } else {                                                   // conv: the unrolled form spills 6-7 VGPRs; 4 v_add per K-tile instead
       for (; kt < nk; ++kt) ktile4(kt, kt & 1);
     }
-  }
-#else
-  // ---- diagnostics build (tools/ablate_gemm.sh): the same loop with parts compiled out; results are garbage, timing is the point ----
-  //   bit 0: no fragment reads   bit 1: no LDS-DMA   bit 2: no workgroup barriers   bit 3: no MFMAs
-  constexpr int ABL = GDF_ABLATE;
-  rd_ball(0); rd_aq(0, 0);
-  auto keep = [&]() {
-#pragma unroll
-    for (int j = 0; j < 5; ++j) { asm volatile("" : "+v"(b10[j][0])); asm volatile("" : "+v"(b10[j][1])); }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) { asm volatile("" : "+v"(a4[i][0])); asm volatile("" : "+v"(a4[i][1])); }
-  };
-  auto xbar = [&]() { if constexpr (!(ABL & 4)) bar(); };
-  auto xmma = [&](auto q) { if constexpr (!(ABL & 8)) mma_q(q); else keep(); };
-  auto ktile_abl = [&](int kt, const int cur) {
-    if constexpr (!(ABL & 1)) { rd_ball(cur); rd_aq(cur, 0); } else keep();
-    if constexpr (!(ABL & 2)) stage_a(kt + 1, cur ^ 1, 3);
-    lgkm0(); xbar(); xmma(P0); xbar();
-    if constexpr (!(ABL & 1)) rd_aq(cur, 1); else keep();
-    if constexpr (!(ABL & 2)) stage_b(kt + 2, cur, B1);
-    lgkm0(); xbar(); xmma(P1); xbar();
-    if constexpr (!(ABL & 1)) rd_aq(cur, 2); else keep();
-    if constexpr (!(ABL & 2)) { stage_b(kt + 2, cur, B2); stage_a(kt + 2, cur, 0); }
-    lgkm0(); xbar(); xmma(P2); xbar();
-    if constexpr (!(ABL & 1)) rd_aq(cur, 3); else keep();
-    if constexpr (!(ABL & 2)) { stage_a(kt + 2, cur, 1); stage_a(kt + 2, cur, 2); wait_vmcnt<8>(); }
-    lgkm0(); xbar(); xmma(P3); xbar();
-  };
-  {
-    int kt = 0;
-    for (; kt + 1 < nk; kt += 2) { ktile_abl(kt, 0); ktile_abl(kt + 1, 1); }
-    if (kt < nk) ktile_abl(kt, 0);
-  }
-#endif
   }
   if (!g1) bar();
   wait_vmcnt<0>();                 // the over-staged tiles must not land in the epilogue's staging area

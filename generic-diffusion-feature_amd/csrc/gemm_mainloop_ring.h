@@ -46,12 +46,7 @@ __device__ __forceinline__ void gemm_mainloop_ring(T& t, f32x4 (&acc)[T::FM][T::
 #pragma unroll
     for (int j = 0; j < A_PER_WAVE; ++j) conv_row(m0 + (wave * A_PER_WAVE + j) * 8 + lrow, a_off[j], a_msk[j]);
   }
-#if defined(GDF_CONV_TAP_MAJOR)
-  const int cpb_ = (MODE == A_CONV3) ? p.Cin / BK : 1;
-  int tap = kt0 / cpb_, cb = kt0 - (kt0 / cpb_) * cpb_;
-#else
   int cb = kt0 / 9, tap = kt0 - (kt0 / 9) * 9;         // channel block / filter tap of the NEXT tile to issue
-#endif
   auto issue = [&](int kt, int buf) {
     char* sA = smem + buf * STAGE;
     char* sB = sA + A_TILE;
@@ -78,11 +73,7 @@ __device__ __forceinline__ void gemm_mainloop_ring(T& t, f32x4 (&acc)[T::FM][T::
         glds16(rsB, sB + (wave * B_PER_WAVE + j) * 1024, off);
       }
     }
-#if defined(GDF_CONV_TAP_MAJOR)
-    if (MODE == A_CONV3) { if (++cb == cpb_) { cb = 0; ++tap; } }
-#else
     if (MODE == A_CONV3) { if (++tap == 9) { tap = 0; ++cb; } }
-#endif
   };
 
 
@@ -115,7 +106,7 @@ __device__ __forceinline__ void gemm_mainloop_ring(T& t, f32x4 (&acc)[T::FM][T::
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
-      for (int jj = 0; jj < FN; ++jj) { const int j = GDF_SNAKE(i, jj, FN); acc[i][j] = mfma16<BF>(af[i], bf[j], acc[i][j]); }
+      for (int jj = 0; jj < FN; ++jj) { const int j = snake(i, jj, FN); acc[i][j] = mfma16<BF>(af[i], bf[j], acc[i][j]); }
   };
   // compile-time off for the 256x320 variant: its 160 accumulator VGPRs leave no room for the second code path
   constexpr bool EARLY_OK = (NW == 8) && (FM * FN <= 16);

@@ -17,17 +17,6 @@ namespace gdf {
 // QKN: compile the fused RMSNorm(q) / RMSNorm(k) + RoPE epilogue (GemmParams::qkn_*; 256x256 MMDiT QKV projections only).  It is
 // its own instantiation because its live state (cos / sin rows, norm gains) on top of the gated-residual operands pushed the
 // one-size-fits-all MMDiT epilogue over 256 VGPRs (9 spilled, 40 B of scratch per lane in EVERY 256x256 MMDiT GEMM).
-// diagnostics build (tools/trace_gemm.sh, -DGDF_TRACE): workgroup time stamps (100 MHz s_memrealtime) at kernel entry, after the
-// prologue's DMA issue, when K-tile 0 has landed, after the main loop and after the epilogue, + the CU the workgroup ran on
-#if defined(GDF_TRACE)
-__device__ unsigned long long gdf_trace[16384 * 8];
-#define GDF_TR(i) do { if (threadIdx.x == 0) gdf_trace[(vb & 16383) * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define GDF_TR_ID() do { if (threadIdx.x == 0) gdf_trace[(vb & 16383) * 8 + 6] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | __builtin_amdgcn_s_getreg(63492); } while (0)
-#else
-#define GDF_TR(i)
-#define GDF_TR_ID()
-#endif
-
 // SPLIT: split fp16 hi + lo operands of the opt-in "precise" plans (GemmParams::k_w / a_lo_bytes / o16_lo, kernels.h).  A compile-time
 // switch with its own instantiations (gemm_split_kernel): compiled into the default kernels, its few extra live values pushed
 // the 256x320 dense kernel from 253 VGPRs to 139 spilled (140 -> 100 img/s on the SDXL step).
@@ -38,12 +27,9 @@ __device__ unsigned long long gdf_trace[16384 * 8];
 // GNS: the epilogue also emits per-channel GroupNorm partial sums of the stored fp16 image (GemmParams::gn_partial; 3x3 convs of the VAE AND, since round 5, of the UNet op programs on the tiles gemm_gn_slab_rows() accepts)
 // Order of the MFMAs of a register tile: "snake" — the column index runs backwards on every other row, so that exactly ONE operand register
 // changes between consecutive MFMAs (row-major changes both at every row change).  At the power cap the rate follows the energy:
-// tools/micro/energy.hip mfma-order: 1930 (snake) vs 1913 (row-major) vs 1849 TFLOP/s (both operands change every time).  -DGDF_MMA_ROWMAJOR: A/B.
-#if defined(GDF_MMA_ROWMAJOR)
-#define GDF_SNAKE(row, j, n) (j)
-#else
-#define GDF_SNAKE(row, j, n) ((((row) & 1) != 0) ? (n) - 1 - (j) : (j))
-#endif
+// tools/micro/energy.hip mfma-order: 1930 (snake) vs 1913 (row-major) vs 1849 TFLOP/s (both operands change every time).
+__device__ __forceinline__ constexpr int snake(int row, int j, int n) { return (row & 1) ? n - 1 - j : j; }
+
 template <int MODE_, int BM_, int BN_, int STAGES_, bool GEGLU_, bool DIT_, bool BF_, bool QKN_, bool SPLIT_, bool MX_, bool GNS_>
 struct GemmTile {
   static constexpr int MODE = MODE_, BM = BM_, BN = BN_, STAGES = STAGES_;
@@ -128,13 +114,7 @@ struct GemmTile {
     lrow = lane >> 3;
     chunk = (lane & 7) ^ lrow;
     ldb = (uint32_t)((SPLIT && p.k_w > 0) ? p.k_w : p.K) * 2u;
-#if defined(GDF_ABLATE_EPI) && GDF_ABLATE_EPI == 2
-    // diagnostics build (tools/ab_epilogue_bound.sh): NO main loop — the prologue / epilogue skeleton with every global load and store of the
-    // epilogue, on zero accumulators.  Results are garbage; the time per launch is the epilogue's (+ launch, prologue) alone.
-    nk = 0;
-#else
     nk = (MODE == A_CONV_SMALLC) ? 2 : p.K / BK;
-#endif
     // split-K (2-stage ring tiles only): this workgroup accumulates the K-tiles [kt0, kt1) and stores raw partial sums
     kt0 = 0; kt1 = nk;
     if (STAGES == 2 && p.splitk > 1) {
@@ -208,13 +188,8 @@ struct GemmTile {
     return (mask & bit) ? off : OOB;
   }
   __device__ __forceinline__ uint32_t conv_off(int kt, uint32_t base, uint32_t mask) const {
-#if defined(GDF_CONV_TAP_MAJOR)                                   // diagnostics build (tools/build_variant.sh): the round-2 K order, for same-box A/Bs
-    const int cpb = p.Cin / BK, tp = kt / cpb;
-    return conv_tap_off(tp < 9 ? tp : 0, kt - tp * cpb, base, mask, tp < 9);
-#else
     const int cbk = kt / 9;                                     // scalar: channel block, then filter tap
     return conv_tap_off(kt - cbk * 9, cbk, base, mask, kt < nk);
-#endif
   };
 };
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build a diagnostics variant of libgdf.so next to the product library (same-box A/Bs with tools/ab_lib.sh):
 #   tools/build_variant.sh <tag> [-DFLAG ...]   ->  generic-diffusion-feature_amd/libgdf_<tag>.so   (git-ignored, travels with gpurun)
-# e.g.  tools/build_variant.sh prev -DGDF_CONV_TAP_MAJOR     (round-2 conv K order)
+# e.g.  tools/build_variant.sh rope -DGDF_EXP_ROPE_FULLWAIT   (csrc/dit.hip's rope-kernel wait experiment)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd); D=$R/generic-diffusion-feature_amd; TAG=$1; shift
 O=$D/build/var_$TAG; mkdir -p $O

@@ -5,10 +5,13 @@ csrc/gemm.hip left every kernel's machine code unchanged:   python tools/isa_fin
 import hashlib, re, sys
 
 
+FIELDS = ("vgpr_count", "vgpr_spill_count", "sgpr_count", "sgpr_spill_count", "group_segment_fixed_size", "private_segment_fixed_size", "agpr_count")
+
+
 def kernels(path):
     out, cur, body = {}, None, []
     meta = {}
-    name = None
+    entry, in_md = None, False
     for line in open(path, errors="replace"):
         s = line.strip()
         m = re.match(r"^(_Z\w+):\s*(;.*)?$", s)
@@ -30,12 +33,17 @@ def kernels(path):
             if s.endswith(":"):
                 continue
             body.append(s)
-        m = re.match(r"\.name:\s+(\S+)", s)
+        # kernel entries of the code-object metadata: "  - .field:" opens an entry, "    .field:" continues it (deeper lines belong to .args).
+        # The fields are listed alphabetically, some before .name, so an entry is bound to its name rather than filled after it.
+        in_md = in_md or s == "amdhsa.kernels:"
+        m = re.match(r"^  (- |  )\.(\w+):\s+(\S+)", line) if in_md else None
         if m:
-            name = m.group(1); meta.setdefault(name, {})
-        m = re.match(r"\.(vgpr_count|vgpr_spill_count|sgpr_count|sgpr_spill_count|group_segment_fixed_size|private_segment_fixed_size|agpr_count):\s+(\d+)", s)
-        if m and name:
-            meta[name][m.group(1)] = int(m.group(2))
+            if m.group(1) == "- ":
+                entry = {}
+            if m.group(2) == "name":
+                meta[m.group(3)] = entry
+            elif m.group(2) in FIELDS:
+                entry[m.group(2)] = int(m.group(3))
     return out, meta
 
 
