@@ -13,6 +13,10 @@
 //     `ds_read_b64_tr_b16` from a row-major V tile.
 //   * head dims 40/64/80/160 (SD1.5: 40,80,160; SDXL: 64) are zero-padded to MFMA granularity in LDS.
 #include "kernels.h"
+#include <cstdio>
+#include <deque>
+#include <mutex>
+#include <string>
 #include <type_traits>
 
 namespace gdf {
@@ -1077,79 +1081,139 @@ __global__ __launch_bounds__(LW ? 320 : 256, OCC) void attn_map_kernel(const Att
   }
 }
 
-template <int D, bool BF = false>
-static hipError_t launch_d(const AttnParams& p, hipStream_t s) {
+// ---- dispatch: select (host arithmetic only, no device call) -> descriptor -> launch / name ----
+// The descriptor spells one instantiation: attn_kernel<D, QW, NW, BF, OCC, PV16, QKP> or, when probabilities are written,
+// attn_map_kernel<D, FULL, OCC, LW, BF>.  launch_attention() launches the instantiation the descriptor names and
+// attention_kernel_name() prints the same descriptor, so what a test or a profile reads is what runs.
+struct AttnSel {
+  bool ok;                 // false: launch_attention rejects these parameters
+  bool map;                // attn_map_kernel
+  int D, QW, NW; bool BF; int OCC; bool PV16, QKP;
+  bool FULL, LW;           // map kernel only
+  int qblk, threads;       // query rows per workgroup, threads per workgroup
+};
+
+static AttnSel attn_select(const AttnParams& p) {
+  AttnSel k{};
+  if ((p.ldq | p.ldk | p.ldv) & 7) return k;     // 16-byte aligned rows
+  if (p.ldo & 3) return k;
+  const int D = p.D;
+  const bool BF = p.bf16 != 0;
+  if (BF ? D != 128 : (D != 32 && D != 40 && D != 64 && D != 72 && D != 80 && D != 128 && D != 160)) return k;   // bf16: the MMDiT head dim only
   const bool maps = p.map || p.map2;
-  if (maps && p.seg_T && (p.seg_T & 7)) return hipErrorInvalidValue;    // an 8-key chunk must not straddle the text / image boundary
+  if (maps && p.seg_T && (p.seg_T & 7)) return k;    // an 8-key chunk must not straddle the text / image boundary
+  k.ok = true; k.D = D; k.BF = BF; k.QW = 1; k.NW = 4; k.OCC = 2;
   if (maps) {
-    const int nqb = (p.Sq + 127) / 128;
-    constexpr bool can3 = D <= 48;   // K trimmed to DQK columns: 3 workgroups per CU fit the 160 KiB of LDS
-    constexpr bool canlw = D <= 48;  // loader-wave variant (two K+V tiles of staging registers must fit 128 VGPRs)
-    const dim3 grid(p.B * p.heads * nqb);
+    const bool can3 = D <= 48;   // K trimmed to DQK columns: 3 workgroups per CU fit the 160 KiB of LDS
+    const bool canlw = D <= 48;  // loader-wave variant (two K+V tiles of staging registers must fit 128 VGPRs)
+    k.map = true;
     if (!BF && p.Sq % 128 == 0 && p.Sk % KT == 0 && !p.seg_T && !p.kv_len) {
-      if (canlw && p.Sk % (2 * KT) == 0) hipLaunchKernelGGL((attn_map_kernel<D, true, can3 ? 3 : 2, canlw>), grid, dim3(320), 0, s, p);
-      else hipLaunchKernelGGL((attn_map_kernel<D, true, can3 ? 3 : 2, false>), grid, dim3(256), 0, s, p);
-    } else hipLaunchKernelGGL((attn_map_kernel<D, false, 2, false, BF>), grid, dim3(256), 0, s, p);
-  } else {
-    // 64 query rows per wave (every K / V fragment feeds two MFMAs) when the sequence is long and the
-    // accumulators fit (D <= 64); 32 rows per wave otherwise
-    // (D = 128 with 64 rows per wave needs all 512 registers, one wave per SIMD: measured 822 vs 886 TFLOP/s on the Flux joint shape)
-    constexpr bool can2 = D <= 64;
-    // 64 rows per wave wins even at 2.5 rounds of the slots (S = 1024, batch 16: 0.125 vs 0.130 ms) but halves the number of
-    // workgroups: pick by rate x fill of the 512 workgroup slots
-    const long nb2 = (long)p.B * p.heads * ((p.Sq + 255) / 256), nb1 = (long)p.B * p.heads * ((p.Sq + 127) / 128);
-    auto fill = [](long n, long slots) { const long r = (n + slots - 1) / slots; return (double)n / (double)(r * slots); };
+      k.FULL = true; k.OCC = can3 ? 3 : 2; k.LW = canlw && p.Sk % (2 * KT) == 0;
+    }
+    k.qblk = 128; k.threads = k.LW ? 320 : 256;
+    return k;
+  }
+  // 64 query rows per wave (every K / V fragment feeds two MFMAs) when the sequence is long and the
+  // accumulators fit (D <= 64); 32 rows per wave otherwise
+  // (D = 128 with 64 rows per wave needs all 512 registers, one wave per SIMD: measured 822 vs 886 TFLOP/s on the Flux joint shape)
+  const bool can2 = D <= 64;
+  // 64 rows per wave wins even at 2.5 rounds of the slots (S = 1024, batch 16: 0.125 vs 0.130 ms) but halves the number of
+  // workgroups: pick by rate x fill of the 512 workgroup slots
+  const long nb2 = (long)p.B * p.heads * ((p.Sq + 255) / 256), nb1 = (long)p.B * p.heads * ((p.Sq + 127) / 128);
+  auto fill = [](long n, long slots) { const long r = (n + slots - 1) / slots; return (double)n / (double)(r * slots); };
+  const bool wide = !BF && can2 && p.Sq >= 512 && 1.00 * fill(nb2, 512) >= 0.80 * fill(nb1, 512);
+  // round 5: P V on mfma_f32_16x16x32_f16 where the 16-row padding of D is smaller than the 32-row one (40 / 72 / 80).  Same-box A/B against
+  // the 32x32x16 form: D = 40 564 -> 604 (B = 32: 589 -> 640), D = 72 674 -> 715, D = 80 659 -> 703 TFLOP/s (profiles/r05_ab_attn_pv16.txt)
+  const bool pv16 = !BF && ((D + 15) / 16 * 16 < (D + 31) / 32 * 32);
+  if (!BF && D <= 80 && D >= 40 && p.q_lo > 0 && p.kv_lo > 0) {
     // split q / k / v pairs (AttnParams::q_lo / kv_lo, the full-split UNet plans): 8 waves x 32 query rows share the four staged tiles (K, K_lo, V, V_lo), one
     // workgroup per CU; head dims whose tiles do not fit (160) or do not split evenly over 512 threads use 4 waves / fall through to the hi halves
-    if constexpr (!BF && D <= 80 && D >= 40) {
-      if (p.q_lo > 0 && p.kv_lo > 0) {
-        constexpr int W8 = (KT * ((D + 31) / 32 * 32 / 8)) % 512 == 0 ? 8 : 4;
-        const int nqb = (p.Sq + 32 * W8 - 1) / (32 * W8);
-        hipLaunchKernelGGL((attn_kernel<D, 1, W8, false, 1, false, true>), dim3(p.B * p.heads * nqb), dim3(64 * W8), 0, s, p);
-        return hipGetLastError();
-      }
-    }
-    // round 5: P V on mfma_f32_16x16x32_f16 where the 16-row padding of D is smaller than the 32-row one (40 / 72 / 80).  Same-box A/B against
-    // the 32x32x16 form: D = 40 564 -> 604 (B = 32: 589 -> 640), D = 72 674 -> 715, D = 80 659 -> 703 TFLOP/s (profiles/r05_ab_attn_pv16.txt)
-    constexpr bool pv16c = !BF && ((D + 15) / 16 * 16 < (D + 31) / 32 * 32);
-    if constexpr (pv16c) {
-      if (can2 && p.Sq >= 512 && 1.00 * fill(nb2, 512) >= 0.80 * fill(nb1, 512)) {
-        const int nqb = (p.Sq + 255) / 256;
-        hipLaunchKernelGGL((attn_kernel<D, can2 ? 2 : 1, 4, false, 2, pv16c>), dim3(p.B * p.heads * nqb), dim3(256), 0, s, p);
-      } else {
-        const int nqb = (p.Sq + 127) / 128;
-        hipLaunchKernelGGL((attn_kernel<D, 1, 4, false, 2, pv16c>), dim3(p.B * p.heads * nqb), dim3(256), 0, s, p);
-      }
-    } else if (!BF && can2 && p.Sq >= 512 && 1.00 * fill(nb2, 512) >= 0.80 * fill(nb1, 512)) {
-      const int nqb = (p.Sq + 255) / 256;
-      hipLaunchKernelGGL((attn_kernel<D, can2 ? 2 : 1>), dim3(p.B * p.heads * nqb), dim3(256), 0, s, p);
-    } else if (D == 128 && p.Sq >= 1024) {
-      // 8 waves share every staged K / V tile (half the L2 -> LDS traffic per query row): 877 -> 917 TFLOP/s on the Flux joint
-      // shape; at D = 72 the 768-chunk tile does not split evenly over 512 threads (690 -> 591), so only D = 128 takes it
-      const int nqb = (p.Sq + 255) / 256;
-      hipLaunchKernelGGL((attn_kernel<D, 1, D == 128 ? 8 : 4, BF>), dim3(p.B * p.heads * nqb), dim3(D == 128 ? 512 : 256), 0, s, p);
-    } else {
-      const int nqb = (p.Sq + 127) / 128;
-      hipLaunchKernelGGL((attn_kernel<D, 1, 4, BF>), dim3(p.B * p.heads * nqb), dim3(256), 0, s, p);
+    k.NW = (KT * ((D + 31) / 32 * 32 / 8)) % 512 == 0 ? 8 : 4; k.OCC = 1; k.QKP = true;
+  } else if (pv16) {
+    k.PV16 = true; k.QW = wide ? 2 : 1;
+  } else if (wide) {
+    k.QW = 2;
+  } else if (D == 128 && p.Sq >= 1024) {
+    // 8 waves share every staged K / V tile (half the L2 -> LDS traffic per query row): 877 -> 917 TFLOP/s on the Flux joint
+    // shape; at D = 72 the 768-chunk tile does not split evenly over 512 threads (690 -> 591), so only D = 128 takes it
+    k.NW = 8;
+  }
+  k.qblk = 32 * k.QW * k.NW; k.threads = 64 * k.NW;
+  return k;
+}
+
+// launch the instantiation if it is the one the descriptor names
+template <int D, int QW, int NW, bool BF, int OCC, bool PV16, bool QKP>
+static bool try_attn(const AttnSel& k, const AttnParams& p, dim3 grid, hipStream_t s) {
+  if (k.map || k.D != D || k.QW != QW || k.NW != NW || k.BF != BF || k.OCC != OCC || k.PV16 != PV16 || k.QKP != QKP) return false;
+  hipLaunchKernelGGL((attn_kernel<D, QW, NW, BF, OCC, PV16, QKP>), grid, dim3(NW * 64), 0, s, p);
+  return true;
+}
+template <int D, bool FULL, int OCC, bool LW, bool BF>
+static bool try_map(const AttnSel& k, const AttnParams& p, dim3 grid, hipStream_t s) {
+  if (!k.map || k.D != D || k.FULL != FULL || k.OCC != OCC || k.LW != LW || k.BF != BF) return false;
+  hipLaunchKernelGGL((attn_map_kernel<D, FULL, OCC, LW, BF>), grid, dim3(LW ? 320 : 256), 0, s, p);
+  return true;
+}
+
+// every instantiation of head dim D / element type BF; a descriptor none of them matches is an error, never another kernel
+template <int D, bool BF = false>
+static hipError_t launch_d(const AttnSel& k, const AttnParams& p, hipStream_t s) {
+  const dim3 grid(p.B * p.heads * ((p.Sq + k.qblk - 1) / k.qblk));
+  constexpr bool can3 = D <= 48, can2 = D <= 64;
+  constexpr bool pv16c = !BF && ((D + 15) / 16 * 16 < (D + 31) / 32 * 32);
+  bool done = false;
+  if constexpr (!BF) {
+    if constexpr (can3) done = done || try_map<D, true, 3, true, false>(k, p, grid, s);
+    done = done || try_map<D, true, can3 ? 3 : 2, false, false>(k, p, grid, s);
+    if constexpr (D <= 80 && D >= 40) {
+      constexpr int W8 = (KT * ((D + 31) / 32 * 32 / 8)) % 512 == 0 ? 8 : 4;
+      done = done || try_attn<D, 1, W8, false, 1, false, true>(k, p, grid, s);
     }
   }
-  return hipGetLastError();
+  done = done || try_map<D, false, 2, false, BF>(k, p, grid, s);
+  if constexpr (pv16c) {
+    if constexpr (can2) done = done || try_attn<D, 2, 4, false, 2, true, false>(k, p, grid, s);
+    done = done || try_attn<D, 1, 4, false, 2, true, false>(k, p, grid, s);
+  } else {
+    if constexpr (!BF && can2) done = done || try_attn<D, 2, 4, false, 2, false, false>(k, p, grid, s);
+    if constexpr (D == 128) done = done || try_attn<D, 1, 8, BF, 2, false, false>(k, p, grid, s);
+    done = done || try_attn<D, 1, 4, BF, 2, false, false>(k, p, grid, s);
+  }
+  return done ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_attention(const AttnParams& p, hipStream_t s) {
-  if ((p.ldq | p.ldk | p.ldv) & 7) return hipErrorInvalidValue;     // 16-byte aligned rows
-  if (p.ldo & 3) return hipErrorInvalidValue;
-  if (p.bf16) return p.D == 128 ? launch_d<128, true>(p, s) : hipErrorInvalidValue;      // bf16: the MMDiT head dim only
-  switch (p.D) {
-    case 32: return launch_d<32>(p, s);
-    case 40: return launch_d<40>(p, s);
-    case 64: return launch_d<64>(p, s);
-    case 72: return launch_d<72>(p, s);
-    case 80: return launch_d<80>(p, s);
-    case 128: return launch_d<128>(p, s);
-    case 160: return launch_d<160>(p, s);
+  const AttnSel k = attn_select(p);
+  if (!k.ok) return hipErrorInvalidValue;
+  if (k.BF) return launch_d<128, true>(k, p, s);
+  switch (k.D) {
+    case 32: return launch_d<32>(k, p, s);
+    case 40: return launch_d<40>(k, p, s);
+    case 64: return launch_d<64>(k, p, s);
+    case 72: return launch_d<72>(k, p, s);
+    case 80: return launch_d<80>(k, p, s);
+    case 128: return launch_d<128>(k, p, s);
+    case 160: return launch_d<160>(k, p, s);
   }
   return hipErrorInvalidValue;
+}
+
+// kernel symbol (as rocprofv3 prints it, all template arguments spelled out) that launch_attention would launch; nullptr where it rejects
+const char* attention_kernel_name(const AttnParams& p) {
+  const AttnSel k = attn_select(p);
+  if (!k.ok) return nullptr;
+  auto tf = [](bool v) { return v ? "true" : "false"; };
+  char tmp[96];
+  if (k.map) snprintf(tmp, sizeof tmp, "attn_map_kernel<%d, %s, %d, %s, %s>", k.D, tf(k.FULL), k.OCC, tf(k.LW), tf(k.BF));
+  else snprintf(tmp, sizeof tmp, "attn_kernel<%d, %d, %d, %s, %d, %s, %s>", k.D, k.QW, k.NW, tf(k.BF), k.OCC, tf(k.PV16), tf(k.QKP));
+  // interned: the returned pointer stays valid for the life of the library
+  static std::mutex mu;
+  static std::deque<std::string> names;
+  std::lock_guard<std::mutex> lk(mu);
+  for (const std::string& n : names) if (n == tmp) return n.c_str();
+  names.emplace_back(tmp);
+  return names.back().c_str();
 }
 
 }  // namespace gdf

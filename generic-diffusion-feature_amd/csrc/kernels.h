@@ -181,6 +181,9 @@ struct AttnParams {
                          // blocks share ONE fp16 range scale, undone on the consuming GEMM's accumulators)
 };
 hipError_t launch_attention(const AttnParams& p, hipStream_t s);
+// kernel symbol launch_attention would pick (host arithmetic only: no pointer is dereferenced, no device call; only whether map / map2 / kv_len are
+// set is read), nullptr for parameters it rejects.  Built from the descriptor the launch itself switches on.
+const char* attention_kernel_name(const AttnParams& p);
 
 // ------------------------------------------------------------------------------------------------
 // normalisation / elementwise

@@ -17,7 +17,26 @@ static int fin(hipError_t e, const char* what) {
   return GDF_ERR_HIP;
 }
 
+static AttnParams attn_params(const gdf_attn_args& g) {
+  AttnParams a{};
+  a.q = (const half_t*)g.q; a.ldq = g.ldq; a.k = (const half_t*)g.k; a.ldk = g.ldk; a.v = (const half_t*)g.v; a.ldv = g.ldv;
+  a.o = (half_t*)g.o; a.ldo = g.ldo; a.B = g.B; a.heads = g.heads; a.Sq = g.Sq; a.Sk = g.Sk; a.D = g.D; a.kv_bstride = g.kv_bstride;
+  a.scale = g.scale != 0.f ? g.scale : 1.0f / sqrtf((float)g.D);
+  a.map = (half_t*)g.map; a.map2 = (half_t*)g.map2; a.kv_len = g.kv_len; a.seg_T = g.seg_T; a.bf16 = g.bf16; a.o_lo = g.o_lo;
+  a.o_pair_bf16 = g.o_pair_bf16; a.q_lo = g.q_lo; a.kv_lo = g.kv_lo; a.o_scale = g.o_scale;
+  return a;
+}
+
 extern "C" {
+
+int gdf_op_attention_ex(const gdf_attn_args* args, void* stream) {
+  if (!args) { set_error("gdf_op_attention_ex: args is NULL"); return GDF_ERR_ARG; }
+  return fin(launch_attention(attn_params(*args), (hipStream_t)stream), "attention_ex");
+}
+
+const char* gdf_op_attention_kernel(const gdf_attn_args* args) {
+  return args ? attention_kernel_name(attn_params(*args)) : nullptr;
+}
 
 int gdf_op_gemm(const void* A, int lda, const void* W, const float* bias, const float* res32, const void* res16,
                 int ldres, void* out16, int ldo16, float* out32, int ldo32, int M, int N, int K, int flags,

@@ -47,7 +47,7 @@ int gdf_op_attention_split(const void* q, int ldq, const void* k, int ldk, const
 
 /* q, k and v as split pairs (hi, lo = fp16(x - hi), lo at +qkv_lo elements in the same row: what a GEMM with o16_lo writes): the softmax sees
  * q k^T contracted over both halves, O accumulates P (v_hi + v_lo) — the full-split UNet plans (attention_processor.py:3311-3313 in fp32 terms).
- * Head dims 40 / 64 / 80; others read the hi halves only. */
+ * Head dims 40 <= D <= 80 (40 / 64 / 72 / 80); others read the hi halves only. */
 int gdf_op_attention_pair(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int qkv_lo, void* o, int ldo, int o_lo, int B,
                           int heads, int Sq, int Sk, int D, void* stream);
 
@@ -71,6 +71,44 @@ int gdf_op_conv_in(const void* x_nchw, int B, int Cin, int H, int W, const void*
  * get_attention_scores+bmm (attention_processor.py:640-685, components/attention.py:232-246).          */
 int gdf_op_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
                      int B, int heads, int Sq, int Sk, int D, void* map, void* stream);
+
+/* The complete attention launch: every field a plan can set (csrc/kernels.h AttnParams), one kernel launch.
+ *   q / k / v / o: rows are tokens, head h at columns [h*D, h*D+D), leading dimensions in elements (ldq / ldk / ldv % 8 == 0, ldo % 4 == 0).
+ *   kv_bstride  rows between consecutive samples' K / V (Sk normally; 0 = all samples share one K / V set).
+ *   scale       softmax scale; 0 = D^-0.5.
+ *   map         optional probabilities (B, heads, Sq, Sk) fp16; with seg_T > 0 the `self-map` (B, heads, Sq - seg_T, Sk - seg_T).
+ *   map2        seg_T > 0 only: the `cross-map` (B, heads, Sq - seg_T, seg_T) (image queries x text keys).  Maps need seg_T % 8 == 0.
+ *   kv_len      optional device int[B]: keys [max(1, min(kv_len[b], Sk)), Sk) of sample b are masked out (probability 0).
+ *   seg_T       > 0: MMDiT joint sequence, rows region-major [B x seg_T text][B x (Sq - seg_T) image], Sq == Sk.
+ *   bf16        D = 128 only: q, k, v, o are bf16; maps stay fp16.
+ *   o_lo        > 0: o is written as a split (hi, lo) pair, lo at +o_lo elements in the same row; o_pair_bf16: the pair is bf16 hi + bf16 lo
+ *               (fp16 q / k / v only).
+ *   q_lo, kv_lo both > 0 (fp16, 40 <= D <= 80): q, k, v are split pairs, lo at +q_lo / +kv_lo elements in the same row.
+ *   o_scale     != 0: o is stored multiplied by this power of two. */
+typedef struct gdf_attn_args {
+  const void* q; int ldq;
+  const void* k; int ldk;
+  const void* v; int ldv;
+  void* o; int ldo;
+  int B, heads, Sq, Sk, D;
+  int kv_bstride;
+  float scale;
+  void* map;
+  void* map2;
+  const int* kv_len;
+  int seg_T;
+  int bf16;
+  int o_lo;
+  int o_pair_bf16;
+  int q_lo, kv_lo;
+  float o_scale;
+} gdf_attn_args;
+int gdf_op_attention_ex(const gdf_attn_args* args, void* stream);
+/* Symbol of the kernel gdf_op_attention_ex launches for these arguments, as a profiler prints it without namespace and signature
+ * ("attn_kernel<64, 2, 4, false, 2, false, false>", "attn_map_kernel<40, true, 3, true, false>").  Host arithmetic only: no device
+ * is touched and no pointer is followed (only whether map / map2 / kv_len are set matters).  NULL for arguments the launch rejects.
+ * The string lives as long as the library. */
+const char* gdf_op_attention_kernel(const gdf_attn_args* args);
 
 /* GroupNorm(G groups, eps) [+SiLU] over NHWC x (fp16, ld) or x32 (fp32, ld); y contiguous fp16 [B*HW][C].
  * scratch: gdf_op_groupnorm_scratch_bytes(B,HW,C).                                                      */

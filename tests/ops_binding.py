@@ -10,6 +10,16 @@ sys.path.insert(0, os.path.join(ROOT, "generic-diffusion-feature_amd"))
 from components import native  # noqa: E402
 
 vp, ci, fp = C.c_void_p, C.c_int, C.c_float
+
+
+class AttnArgs(C.Structure):
+    """gdf_attn_args of include/gdf_ops.h (same field order)"""
+    _fields_ = [("q", vp), ("ldq", ci), ("k", vp), ("ldk", ci), ("v", vp), ("ldv", ci), ("o", vp), ("ldo", ci),
+                ("B", ci), ("heads", ci), ("Sq", ci), ("Sk", ci), ("D", ci), ("kv_bstride", ci), ("scale", fp),
+                ("map", vp), ("map2", vp), ("kv_len", vp), ("seg_T", ci), ("bf16", ci), ("o_lo", ci), ("o_pair_bf16", ci),
+                ("q_lo", ci), ("kv_lo", ci), ("o_scale", fp)]
+
+
 OPS = {
     "gdf_op_gemm": (ci, [vp, ci, vp, vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp]),
     "gdf_op_conv3x3": (ci, [vp, ci, ci, ci, ci, ci, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp]),
@@ -20,6 +30,8 @@ OPS = {
     "gdf_op_groupnorm_split": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, fp, vp, vp, ci, vp, ci, ci, vp, vp]),
     "gdf_op_attention_split": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
     "gdf_op_attention_pair": (ci, [vp, ci, vp, ci, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp]),
+    "gdf_op_attention_ex": (ci, [C.POINTER(AttnArgs), vp]),
+    "gdf_op_attention_kernel": (C.c_char_p, [C.POINTER(AttnArgs)]),
     "gdf_op_attention": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, vp]),
     "gdf_op_groupnorm_scratch_bytes": (C.c_size_t, [ci, ci, ci]),
     "gdf_op_groupnorm": (ci, [vp, vp, ci, ci, ci, ci, ci, fp, vp, vp, ci, vp, vp, vp]),

@@ -162,6 +162,23 @@ def test_joint_attention(B, heads, T, S):
     ref = torch.nn.functional.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B, T + S, C)
     got = torch.cat([o[:B * T].view(B, T, C), o[B * T:].view(B, S, C)], 1)
     assert rel_l2(got, ref) < 2e-3
+    # bf16 leg: the same values rounded to bf16 (three fewer mantissa bits: the fp16 bound x 8), reference on those rounded values
+    qkv_tb, qkv_ib = qkv_t.float().bfloat16(), qkv_i.float().bfloat16()
+    bufb = _region_major(qkv_tb, qkv_ib)
+    ob = torch.zeros(B * (T + S), C, device="cuda", dtype=torch.bfloat16)
+    baseb = bufb.data_ptr()
+    ptrb = lambda col: ctypes.c_void_p(baseb + col * 2)
+    ok(L.gdf_op_set_e16(2), L)
+    try:
+        ok(L.gdf_op_attention_joint(ptrb(0), 3 * C, ptrb(C), 3 * C, ptrb(2 * C), 3 * C, P(ob), C, B, heads, T, S, D, stream()), L)
+        torch.cuda.synchronize()
+    finally:
+        L.gdf_op_set_e16(0)
+    jb = torch.cat([qkv_tb, qkv_ib], 1).float()
+    q, k, v = [jb[..., i * C:(i + 1) * C].view(B, T + S, heads, D).transpose(1, 2) for i in range(3)]
+    refb = torch.nn.functional.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B, T + S, C)
+    gotb = torch.cat([ob[:B * T].view(B, T, C), ob[B * T:].view(B, S, C)], 1)
+    assert rel_l2(gotb, refb) < 1.6e-2
 
 
 def _round(P, I, dt):
