@@ -188,11 +188,15 @@ const char* attention_kernel_name(const AttnParams& p);
 // ------------------------------------------------------------------------------------------------
 // normalisation / elementwise
 // ------------------------------------------------------------------------------------------------
+// Statistics are one-pass fp32 sums of x and x^2 per thread (double across threads / slabs): the error of rstd grows with (mean / std)^2 of a
+// group and stays inside the fp16 output tolerance (1e-3) up to mean / std of about 32 (rstd off by <= 1e-4 there, 2e-3 at 128; DESIGN.md 3.3, tests/test_gpu_groupnorm.py).
 // GroupNorm over NHWC rows x [B][HW][ld] (C channels used, G groups).  Two launches:
 //   gn_stats : per-(sample, channel) affine table ab[b][c] = (rstd*gamma, beta - mean*rstd*gamma)
 //              (`partial` is scratch of gn_partial_floats(B, HW, C) floats)
 //   gn_apply : y = act(x*a + b) as contiguous fp16 [B*HW][C]; silu=1 applies v*sigmoid(v)
 size_t gn_partial_floats(int B, int HW, int C);
+// pixel rows per statistics slab of launch_gn_stats (its `partial` is [B][ceil(HW / slab)][C][2])
+int gn_stats_slab(int B, int HW);
 // split operands ("precise" plans): x_lo > 0 = the fp16 source is a (hi, lo) pair with lo x_lo elements after hi in the row;
 // y_lo > 0 = y is written as such a pair (rows of ldy elements, lo at column offset y_lo); ldy = 0 means C
 hipError_t launch_gn_stats(const half_t* x16, const float* x32, int ld, int B, int HW, int C, int G, float eps,

@@ -52,13 +52,13 @@ int gdf_op_gemm(const void* A, int lda, const void* W, const float* bias, const 
   return fin(launch_gemm(g, (hipStream_t)stream), "gemm");
 }
 
-int gdf_op_conv3x3(const void* x, int ld, int B, int H, int W, int Cin, const void* Wt, int Cout, const float* bias,
-                   const float* rowvec, int stride, int ups, const float* res32, void* aux16, void* out16,
-                   float* out32, int narrow, void* stream) {
+// GemmParams of gdf_op_conv3x3 / gdf_op_conv3x3_gn / gdf_op_conv3x3_gn_info (pointers may be null for the host-only query)
+static GemmParams conv3x3_params(const void* x, int ld, int B, int H, int W, int Cin, const void* Wt, int Cout, const float* bias,
+                                 const float* rowvec, int stride, int ups, const float* res32, void* aux16, void* out16,
+                                 float* out32, int narrow) {
   const int IH = ups ? 2 * H : H, IW = ups ? 2 * W : W;
   const int OH = (IH - 1) / stride + 1, OW = (IW - 1) / stride + 1;
   GemmParams g{};
-  if (!span_ok(((size_t)B * H * W - 1) * ld * 2 + (size_t)Cin * 2, (size_t)Cout * 9 * Cin * 2, "conv3x3")) return GDF_ERR_UNSUPPORTED;
   g.A = (const half_t*)x; g.lda = ld; g.a_bytes = (uint32_t)(((size_t)B * H * W - 1) * ld * 2 + (size_t)Cin * 2);
   g.M = B * OH * OW; g.N = Cout; g.K = 9 * Cin; g.mode = A_CONV3; g.H = H; g.W = W; g.OH = OH; g.OW = OW;
   g.stride = stride; g.ups = ups; g.Cin = Cin;
@@ -68,7 +68,34 @@ int gdf_op_conv3x3(const void* x, int ld, int B, int H, int W, int Cin, const vo
   g.aux16 = (half_t*)aux16; g.ldaux = Cout;
   g.out16 = (half_t*)out16; g.ldo16 = Cout; g.out32 = out32; g.ldo32 = Cout;
   g.bn = (narrow & 1) ? 16 : 128; g.variant = (narrow >> 8) & 0xfff; g.no_early_mma = (narrow >> 20) & 1;
+  return g;
+}
+
+int gdf_op_conv3x3(const void* x, int ld, int B, int H, int W, int Cin, const void* Wt, int Cout, const float* bias,
+                   const float* rowvec, int stride, int ups, const float* res32, void* aux16, void* out16,
+                   float* out32, int narrow, void* stream) {
+  if (!span_ok(((size_t)B * H * W - 1) * ld * 2 + (size_t)Cin * 2, (size_t)Cout * 9 * Cin * 2, "conv3x3")) return GDF_ERR_UNSUPPORTED;
+  const GemmParams g = conv3x3_params(x, ld, B, H, W, Cin, Wt, Cout, bias, rowvec, stride, ups, res32, aux16, out16, out32, narrow);
   return fin(launch_gemm(g, (hipStream_t)stream), "conv3x3");
+}
+
+int gdf_op_conv3x3_gn(const void* x, int ld, int B, int H, int W, int Cin, const void* Wt, int Cout, const float* bias,
+                      const float* rowvec, int stride, int ups, const float* res32, void* aux16, void* out16,
+                      float* out32, int narrow, float out16_scale, float* gn_partial, void* stream) {
+  if (!gn_partial) { set_error("gdf_op_conv3x3_gn: gn_partial is NULL"); return GDF_ERR_ARG; }
+  if (!span_ok(((size_t)B * H * W - 1) * ld * 2 + (size_t)Cin * 2, (size_t)Cout * 9 * Cin * 2, "conv3x3_gn")) return GDF_ERR_UNSUPPORTED;
+  GemmParams g = conv3x3_params(x, ld, B, H, W, Cin, Wt, Cout, bias, rowvec, stride, ups, res32, aux16, out16, out32, narrow);
+  g.out16_scale = out16_scale; g.gn_partial = gn_partial;
+  return fin(launch_gemm(g, (hipStream_t)stream), "conv3x3_gn");
+}
+
+const char* gdf_op_conv3x3_gn_info(int B, int H, int W, int Cin, int Cout, int stride, int ups, int flags, int* slab_rows) {
+  GemmParams g = conv3x3_params(nullptr, Cin, B, H, W, Cin, nullptr, Cout, nullptr, nullptr, stride, ups, nullptr, nullptr, nullptr, nullptr, flags);
+  if (Cin <= 8) { g.mode = A_CONV_SMALLC; g.K = 128; g.Cin = 8; }                     // the conv_in form (gdf_op_conv_in_gn)
+  g.gn_partial = (float*)1;                                                             // label only: never followed
+  const int sr = gemm_gn_slab_rows(g);
+  if (slab_rows) *slab_rows = sr;
+  return sr > 0 ? gemm_kernel_name(g) : nullptr;
 }
 
 // ---- split-operand forms of the "precise" plans (kernels.h GemmParams::k_w / a_lo_bytes / o16_lo) ----
@@ -164,9 +191,8 @@ int gdf_op_splitk_factor(int M, int N, int K, int conv) {
   return gemm_splitk_factor(g);
 }
 
-int gdf_op_conv_in(const void* x_nchw, int B, int Cin, int H, int W, const void* w_oihw, const float* bias, int Cout,
-                   void* out16, void* scratch, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
+static int conv_in_run(const void* x_nchw, int B, int Cin, int H, int W, const void* w_oihw, const float* bias, int Cout,
+                       void* out16, void* scratch, float out16_scale, float* gn_partial, hipStream_t s, const char* what) {
   half_t* lat8 = (half_t*)scratch;
   half_t* w = (half_t*)((char*)scratch + (size_t)B * H * W * 16);
   hipError_t e = launch_pack_latents((const half_t*)x_nchw, B, Cin, H, W, lat8, nullptr, s);
@@ -179,7 +205,19 @@ int gdf_op_conv_in(const void* x_nchw, int B, int Cin, int H, int W, const void*
   g.M = (int)M; g.N = Cout; g.K = 128; g.mode = A_CONV_SMALLC; g.H = H; g.W = W; g.OH = H; g.OW = W; g.stride = 1; g.Cin = 8;
   g.Wt = w; g.w_bytes = (uint32_t)((size_t)Cout * 256);
   g.bias = bias; g.out16 = (half_t*)out16; g.ldo16 = Cout; g.bn = 128; g.rows_per_sample = 1;
-  return fin(launch_gemm(g, s), "conv_in");
+  g.out16_scale = out16_scale; g.gn_partial = gn_partial;
+  return fin(launch_gemm(g, s), what);
+}
+
+int gdf_op_conv_in(const void* x_nchw, int B, int Cin, int H, int W, const void* w_oihw, const float* bias, int Cout,
+                   void* out16, void* scratch, void* stream) {
+  return conv_in_run(x_nchw, B, Cin, H, W, w_oihw, bias, Cout, out16, scratch, 0.f, nullptr, (hipStream_t)stream, "conv_in");
+}
+
+int gdf_op_conv_in_gn(const void* x_nchw, int B, int Cin, int H, int W, const void* w_oihw, const float* bias, int Cout,
+                      void* out16, void* scratch, float out16_scale, float* gn_partial, void* stream) {
+  if (!gn_partial) { set_error("gdf_op_conv_in_gn: gn_partial is NULL"); return GDF_ERR_ARG; }
+  return conv_in_run(x_nchw, B, Cin, H, W, w_oihw, bias, Cout, out16, scratch, out16_scale, gn_partial, (hipStream_t)stream, "conv_in_gn");
 }
 
 int gdf_op_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
@@ -204,6 +242,33 @@ int gdf_op_groupnorm(const void* x16, const float* x32, int ld, int B, int HW, i
   if (e != hipSuccess) return fin(e, "gn_stats");
   return fin(launch_gn_apply((const half_t*)x16, x32, ld, B, HW, C, ab, silu, (half_t*)y, s), "gn_apply");
 }
+
+// ---- the GroupNorm producers one at a time (tests/test_gpu_groupnorm.py) ----
+int gdf_op_gn_path(int B, int HW, int C, int G, int* fused_sc, int* slab_rows, int* nslab) {
+  if (B < 1 || HW < 1 || C < 1 || G < 1) { set_error("gdf_op_gn_path: sizes must be positive"); return GDF_ERR_ARG; }
+  const int slab = gn_stats_slab(B, HW);
+  if (fused_sc) *fused_sc = gn_fused_slab(B, HW, C, G);
+  if (slab_rows) *slab_rows = slab;
+  if (nslab) *nslab = (HW + slab - 1) / slab;
+  return GDF_OK;
+}
+
+int gdf_op_gn_stats(const void* x16, int x_lo, const float* x32, int ld, int B, int HW, int C, int G, float eps, const float* gamma,
+                    const float* beta, float* partial, float* ab, void* stream) {
+  return fin(launch_gn_stats((const half_t*)x16, x32, ld, B, HW, C, G, eps, gamma, beta, partial, ab, (hipStream_t)stream, x_lo), "gn_stats");
+}
+
+int gdf_op_gn_apply(const void* x16, int x_lo, const float* x32, int ld, int B, int HW, int C, const float* ab, int silu, void* y,
+                    int ldy, int y_lo, void* stream) {
+  return fin(launch_gn_apply((const half_t*)x16, x32, ld, B, HW, C, ab, silu, (half_t*)y, (hipStream_t)stream, x_lo, ldy, y_lo), "gn_apply");
+}
+
+int gdf_op_gn_finalize(const float* partial, int nslab, int B, int HW, int C, int G, float eps, const float* gamma, const float* beta,
+                       float* ab, float* fold, void* stream) {
+  return fin(launch_gn_finalize(partial, nslab, B, HW, C, G, eps, gamma, beta, ab, fold, (hipStream_t)stream), "gn_finalize");
+}
+
+size_t gdf_op_gn_fold_floats(int B, int nslab, int C) { return gn_fold_floats(B, nslab, C); }
 
 int gdf_op_layernorm(const void* x16, const float* x32, int ld, int R, int C, float eps, const float* gamma,
                      const float* beta, void* y, void* stream) {

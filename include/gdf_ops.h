@@ -116,6 +116,36 @@ size_t gdf_op_groupnorm_scratch_bytes(int B, int HW, int C);
 int gdf_op_groupnorm(const void* x16, const float* x32, int ld, int B, int HW, int C, int G, float eps,
                      const float* gamma, const float* beta, int silu, void* y, void* scratch, void* stream);
 
+/* The GroupNorm producers one at a time.  The affine table ab[b][c] = (rstd * gamma[c], beta[c] - mean * rstd * gamma[c]) (fp32 pairs) comes
+ * from the single-launch kernel (which keeps it in LDS), from gdf_op_gn_stats, or from a conv epilogue's per-slab channel sums
+ * (gdf_op_conv3x3_gn) through gdf_op_gn_finalize; gdf_op_gn_apply is y = act(x * a + b).
+ *   gdf_op_gn_path        host arithmetic only: *fused_sc = channels per workgroup of the single-launch kernel (0: gdf_op_groupnorm takes the
+ *                         statistics + apply path), *slab_rows / *nslab = pixel rows per slab and slabs per sample of gdf_op_gn_stats.
+ *   gdf_op_gn_stats       partial: scratch of B * nslab * C * 2 floats; x fp16 (x16, ld), a split pair (x_lo > 0) or fp32 (x32, ld).
+ *   gdf_op_gn_apply       y fp16 rows of ldy elements (0 = C); y_lo > 0: a split (hi, lo) pair, lo at column offset y_lo.
+ *   gdf_op_gn_finalize    partial: [B][nslab][C][2] = (sum x, sum x^2) per slab and channel; HW = pixels per sample the sums cover;
+ *                         fold: scratch of gdf_op_gn_fold_floats(B, nslab, C) floats, or NULL (0 floats: no pre-reduction is used). */
+int gdf_op_gn_path(int B, int HW, int C, int G, int* fused_sc, int* slab_rows, int* nslab);
+int gdf_op_gn_stats(const void* x16, int x_lo, const float* x32, int ld, int B, int HW, int C, int G, float eps, const float* gamma,
+                    const float* beta, float* partial, float* ab, void* stream);
+int gdf_op_gn_apply(const void* x16, int x_lo, const float* x32, int ld, int B, int HW, int C, const float* ab, int silu, void* y,
+                    int ldy, int y_lo, void* stream);
+int gdf_op_gn_finalize(const float* partial, int nslab, int B, int HW, int C, int G, float eps, const float* gamma, const float* beta,
+                       float* ab, float* fold, void* stream);
+size_t gdf_op_gn_fold_floats(int B, int nslab, int C);
+
+/* gdf_op_conv3x3 / gdf_op_conv_in whose epilogue also writes the GroupNorm partial sums of the stored image: out16 = fp16(v * out16_scale)
+ * (0 means 1) and gn_partial[row / slab_rows][c] = (sum, sum of squares) of v * out16_scale over that slab's rows, M / slab_rows slabs of
+ * Cout pairs.  An error (nothing is launched) where the tile has no such epilogue or M is not a whole number of slabs.
+ * gdf_op_conv3x3_gn_info: host arithmetic only; the kernel symbol ("gemm_gn_kernel<1, 256, 320, 9>": mode, tile rows, tile columns, stages)
+ * and *slab_rows for these sizes and tile bits, NULL and 0 where the launch is refused.  Cin <= 8 asks about the conv_in form. */
+int gdf_op_conv3x3_gn(const void* x, int ld, int B, int H, int W, int Cin, const void* Wt, int Cout, const float* bias,
+                      const float* rowvec, int stride, int ups, const float* res32, void* aux16, void* out16,
+                      float* out32, int narrow, float out16_scale, float* gn_partial, void* stream);
+int gdf_op_conv_in_gn(const void* x_nchw, int B, int Cin, int H, int W, const void* w_oihw, const float* bias, int Cout,
+                      void* out16, void* scratch, float out16_scale, float* gn_partial, void* stream);
+const char* gdf_op_conv3x3_gn_info(int B, int H, int W, int Cin, int Cout, int stride, int ups, int flags, int* slab_rows);
+
 /* LayerNorm over the last dim. */
 int gdf_op_layernorm(const void* x16, const float* x32, int ld, int R, int C, float eps, const float* gamma,
                      const float* beta, void* y, void* stream);

@@ -35,6 +35,14 @@ OPS = {
     "gdf_op_attention": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, vp]),
     "gdf_op_groupnorm_scratch_bytes": (C.c_size_t, [ci, ci, ci]),
     "gdf_op_groupnorm": (ci, [vp, vp, ci, ci, ci, ci, ci, fp, vp, vp, ci, vp, vp, vp]),
+    "gdf_op_gn_path": (ci, [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
+    "gdf_op_gn_stats": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, fp, vp, vp, vp, vp, vp]),
+    "gdf_op_gn_apply": (ci, [vp, ci, vp, ci, ci, ci, ci, vp, ci, vp, ci, ci, vp]),
+    "gdf_op_gn_finalize": (ci, [vp, ci, ci, ci, ci, ci, fp, vp, vp, vp, vp, vp]),
+    "gdf_op_gn_fold_floats": (C.c_size_t, [ci, ci, ci]),
+    "gdf_op_conv3x3_gn": (ci, [vp, ci, ci, ci, ci, ci, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp, ci, fp, vp, vp]),
+    "gdf_op_conv_in_gn": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, vp, vp, fp, vp, vp]),
+    "gdf_op_conv3x3_gn_info": (C.c_char_p, [ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(ci)]),
     "gdf_op_layernorm": (ci, [vp, vp, ci, ci, ci, fp, vp, vp, vp, vp]),
     "gdf_op_copy2d": (ci, [vp, vp, ci, vp, ci, ci, ci, vp]),
     "gdf_op_relayout_conv3": (ci, [vp, vp, ci, ci, vp]),
