@@ -294,8 +294,9 @@ int gemm_gn_slab_rows(const GemmParams& p) {
   return (v == 128 || v == 160 || v == 256 || v == 826) ? 64 : 0;
 }
 
-hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
-  if (p.M <= 0 || p.N <= 0) return hipSuccess;
+// Every reason launch_gemm refuses a launch, as host arithmetic on the parameters (no pointer is followed): shared by launch_gemm and the
+// kernel-name query of the C ABI (gdf_op_gemm_kernel), so that the query answers NULL exactly where the launch returns an error.
+hipError_t gemm_check(const GemmParams& p) {
   if (p.mode != A_CONV_SMALLC && (p.K % BK) != 0) return hipErrorInvalidValue;
   if (p.mode == A_CONV3 && (p.Cin % BK) != 0) return hipErrorInvalidValue;
   if (p.k_w > 0 && (p.K != 2 * p.k_w || (p.k_w % BK) != 0 || p.mode == A_CONV_SMALLC || (p.dit && !p.bf16) || (p.mode == A_CONV3 && (p.k_w % (9 * BK)) != 0)))
@@ -305,8 +306,36 @@ hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
   const int v = pick_variant(p);
   if (v != 16 && ((p.geglu ? p.N / 2 : p.N) % 8) != 0) return hipErrorInvalidValue;   // ragged N only in the BN = 16 variant
   if (p.bf16 && !p.dit) return hipErrorInvalidValue;                                      // bf16 exists on the MMDiT path only
+  if (p.gn_partial) return (gemm_gn_slab_rows(p) == 0 || !p.out16) ? hipErrorInvalidValue : hipSuccess;
+  if (p.dit) {
+    if (p.mode != A_DENSE || p.geglu || p.batch > 1) return hipErrorInvalidValue;
+    if (p.qkn_nq && ((v != 8256 && v != 1256) || (p.qkn_nq % 128) != 0)) return hipErrorInvalidValue;   // one head per 128-column wave tile
+    if (p.qkn_nq && (p.res32 || p.res16 || p.rowvec || p.aux16 || p.out32)) return hipErrorInvalidValue;  // the QKN instantiation: bias -> norm + RoPE -> out16 only
+    if (p.mx && (!p.bf16 || p.qkn_nq || is_dit_split(p) || (p.N % 8))) return hipErrorInvalidValue;      // fp8 (e4m3) operands ('fp8-mx' plans)
+    if (!p.mx && is_dit_split(p) && v != 8256 && p.qkn_nq) return hipErrorInvalidValue;                   // split QKN: the 256x256 two-group tile only
+    return hipSuccess;
+  }
+  if (p.geglu && (p.mode != A_DENSE || (p.N % 32) != 0)) return hipErrorInvalidValue;    // weight rows / bias interleaved [16 h | 16 gate]
+  if (v == 16 && (p.mode == A_CONV_SMALLC || (is_split(p) && !p.geglu && p.mode != A_CONV3))) return hipErrorInvalidValue;   // narrow N: conv_out, plain dense
+  return hipSuccess;
+}
+
+// false where a forced `variant` names a tile the form has no instantiation of (825 / 826 on a plain dense GEMM, 825 on a conv, the
+// 16 / 160 / 932 / 826 tiles with GEGLU): launch_gemm then falls back to the form's 128x128 tile, which gemm_kernel_name() does not follow.
+// The complete entry point of the C ABI and its name query refuse these, so that the name the query gives is the kernel that runs.
+bool gemm_variant_ok(const GemmParams& p) {
+  if (!p.variant || p.dit || p.mode == A_CONV_SMALLC) return true;         // (MMDiT: four tiles, all instantiated; conv_in: the name follows the fallback)
+  const int v = pick_variant(p);
+  if (p.geglu) return v != 16 && v != 160 && v != 932 && v != 826;
+  if (p.mode == A_DENSE) return v != 825 && v != 826;
+  return v != 825;
+}
+
+hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
+  if (p.M <= 0 || p.N <= 0) return hipSuccess;
+  if (gemm_check(p) != hipSuccess) return hipErrorInvalidValue;
+  const int v = pick_variant(p);
   if (p.gn_partial) {                                                                     // GroupNorm partial sums from the epilogue (VAE convs)
-    if (gemm_gn_slab_rows(p) == 0 || !p.out16) return hipErrorInvalidValue;
     if (p.mode == A_CONV_SMALLC) return launch_t<A_CONV_SMALLC, 128, 128, 2, false, false, false, false, false, false, true>(p, s);
     if (v == 932) return launch_t<A_CONV3, 256, 320, 9, false, false, false, false, false, false, true>(p, s);
     if (v == 160) return launch_t<A_CONV3, 128, 160, 2, false, false, false, false, false, false, true>(p, s);
@@ -315,13 +344,7 @@ hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
     return launch_t<A_CONV3, 128, 128, 2, false, false, false, false, false, false, true>(p, s);
   }
   if (p.dit) {
-    if (p.mode != A_DENSE || p.geglu || p.batch > 1) return hipErrorInvalidValue;
-    if (p.qkn_nq && ((v != 8256 && v != 1256) || (p.qkn_nq % 128) != 0)) return hipErrorInvalidValue;   // one head per 128-column wave tile
-    if (p.qkn_nq && (p.res32 || p.res16 || p.rowvec || p.aux16 || p.out32)) return hipErrorInvalidValue;  // the QKN instantiation: bias -> norm + RoPE -> out16 only
-    if (p.mx) {                                                                           // fp8 (e4m3) operands ('fp8-mx' plans): 256x256 two-group tile only
-      if (!p.bf16 || p.qkn_nq || is_dit_split(p) || (p.N % 8)) return hipErrorInvalidValue;
-      return launch_t<A_DENSE, 256, 256, 8, false, true, true, false, false, true>(p, s);
-    }
+    if (p.mx) return launch_t<A_DENSE, 256, 256, 8, false, true, true, false, false, true>(p, s);   // fp8 (e4m3) operands ('fp8-mx' plans): 256x256 two-group tile only
     if (is_dit_split(p)) {                                                                // bf16 hi + lo operands ('bfloat16x2' plans)
       if (v == 8256) return p.qkn_nq ? launch_t<A_DENSE, 256, 256, 8, false, true, true, true, true>(p, s) : launch_t<A_DENSE, 256, 256, 8, false, true, true, false, true>(p, s);
       return p.qkn_nq ? hipErrorInvalidValue : launch_t<A_DENSE, 128, 128, 2, false, true, true, false, true>(p, s);
@@ -339,7 +362,6 @@ hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
   }
   if (is_split(p)) {                                                                      // "precise" plans: the reduced tile set of pick_variant
     if (p.geglu) {
-      if (p.mode != A_DENSE || (p.N % 32) != 0) return hipErrorInvalidValue;
       return v == 825 ? launch_t<A_DENSE, 256, 256, 8, true, false, false, false, true>(p, s)
                       : launch_t<A_DENSE, 128, 128, 2, true, false, false, false, true>(p, s);
     }
@@ -364,7 +386,6 @@ hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
   }
   if (p.geglu) {
     // weight rows / bias interleaved [16 h | 16 gate] (launch_relayout_rows geglu = 16)
-    if (p.mode != A_DENSE || (p.N % 32) != 0) return hipErrorInvalidValue;
     if (v == 825) return launch_t<A_DENSE, 256, 256, 8, true>(p, s);
     if (v == 320) return launch_t<A_DENSE, 256, 320, 2, true>(p, s);
     return v == 256 ? launch_t<A_DENSE, 256, 128, 3, true>(p, s) : launch_t<A_DENSE, 128, 128, 2, true>(p, s);
@@ -468,15 +489,24 @@ int gemm_splitk_factor(const GemmParams& p) {
   return s < 2 ? 1 : s;
 }
 
-hipError_t launch_gemm_splitk(const GemmParams& p, int splitk, float* ws, hipStream_t s) {
-  if (splitk <= 1) return launch_gemm(p, s);
-  if (p.dit || p.geglu || p.batch > 1 || (p.N % 8) || p.mode == A_CONV_SMALLC || (p.K % BK)) return hipErrorInvalidValue;
+// pass 1 of launch_gemm_splitk (raw partial sums, one slab per K range) as parameters of launch_gemm: false where the split launch is refused;
+// `splitk` comes back clamped to the K-tile count, <= 1 meaning the plain launch of `p`
+bool gemm_splitk_pass1(const GemmParams& p, int& splitk, float* ws, GemmParams& g) {
+  g = p;
+  if (splitk <= 1) return true;
+  if (p.dit || p.geglu || p.batch > 1 || (p.N % 8) || p.mode == A_CONV_SMALLC || (p.K % BK)) return false;
   if (splitk > p.K / BK) splitk = p.K / BK;
-  if (splitk <= 1) return launch_gemm(p, s);
-  GemmParams g = p;                                       // pass 1: raw partial sums, one slab per K range
+  if (splitk <= 1) return true;
   g.bias = nullptr; g.rowvec = nullptr; g.res32 = nullptr; g.res16 = nullptr; g.aux16 = nullptr; g.out16 = nullptr;
   g.acc_scale = 0.f; g.out16_scale = 0.f;
   g.out32 = ws; g.ldo32 = p.N; g.splitk = splitk; g.o32_sstride = (long)p.M * p.N; g.variant = 0;
+  return true;
+}
+
+hipError_t launch_gemm_splitk(const GemmParams& p, int splitk, float* ws, hipStream_t s) {
+  GemmParams g;
+  if (!gemm_splitk_pass1(p, splitk, ws, g)) return hipErrorInvalidValue;
+  if (splitk <= 1) return launch_gemm(p, s);
   hipError_t e = launch_gemm(g, s);
   if (e != hipSuccess) return e;
   long blocks = ((long)p.M * (p.N / 8) + 255) / 256;

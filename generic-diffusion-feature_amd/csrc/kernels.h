@@ -145,6 +145,11 @@ struct GemmParams {
   float* gn_partial;
 };
 hipError_t launch_gemm(const GemmParams& p, hipStream_t s);
+// hipSuccess where launch_gemm accepts `p` (host arithmetic only, no pointer is followed; launch_gemm itself starts with this check)
+hipError_t gemm_check(const GemmParams& p);
+// false where a forced `variant` names a tile the form has no instantiation of: launch_gemm would run the form's 128x128 tile under
+// another name than gemm_kernel_name() gives (gdf_op_gemm_ex and gdf_op_gemm_kernel refuse these)
+bool gemm_variant_ok(const GemmParams& p);
 // rows per statistics slab if launch_gemm can run `p` (shape, mode, epilogue form) with gn_partial set, else 0
 int gemm_gn_slab_rows(const GemmParams& p);
 // Deterministic split-K for problems with few output tiles and a long K (the 8x8-level 3x3 convs of SD1.5: 160 tiles of 128x128,
@@ -152,6 +157,9 @@ int gemm_gn_slab_rows(const GemmParams& p);
 // launch writes one raw partial-sum slab per K range and splitk_reduce_kernel sums them in a fixed order and applies the epilogue.
 int gemm_splitk_factor(const GemmParams& p);
 hipError_t launch_gemm_splitk(const GemmParams& p, int splitk, float* ws, hipStream_t s);
+// the first launch of launch_gemm_splitk as GemmParams `g` (host arithmetic): false where the split launch is refused; `splitk` is clamped to
+// the K-tile count, <= 1 afterwards = the plain launch of `p`
+bool gemm_splitk_pass1(const GemmParams& p, int& splitk, float* ws, GemmParams& g);
 const char* gemm_kernel_name(const GemmParams& p);
 bool gemm_qkn_ok(int M, int N, int K);   // kernel symbol launch_gemm would pick (only M,N,K,mode,geglu,bn,variant are read)
 

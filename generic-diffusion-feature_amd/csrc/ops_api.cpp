@@ -27,6 +27,64 @@ static AttnParams attn_params(const gdf_attn_args& g) {
   return a;
 }
 
+// GemmParams of gdf_op_gemm_ex / gdf_op_gemm_kernel: M, K, OH, OW and the byte extents are derived as gdf_op_gemm_split / gdf_op_conv3x3_split / conv_in_run /
+// gdf_op_gemm_mx derive them.  what == nullptr: the host-only query (no error text)
+static int gemm_params(const gdf_gemm_args& a, GemmParams& g, const char* what) {
+  auto bad = [&](const char* msg) { if (what) set_error(std::string(what) + ": " + msg); return GDF_ERR_ARG; };
+  if (a.mode != 0 && a.mode != 1) return bad("mode is 0 (dense) or 1 (conv3)");
+  if (a.N < 0 || a.a_lo < 0 || a.lda < 0) return bad("negative size");
+  size_t a_bytes, w_bytes;
+  if (a.mode == 1 && a.Cin <= 8) {                                               // the conv_in form: packed 8-channel pixels, 16 taps x 8 channels of weights, K = 128
+    if (a.B < 0 || a.H < 0 || a.Wd < 0) return bad("negative size");
+    if (a.stride != 1 || a.ups || a.pad0 || a.a_lo > 0) return bad("conv_in form (Cin <= 8): stride 1, no ups / pad0 / a_lo");
+    const size_t M = (size_t)a.B * a.H * a.Wd;
+    a_bytes = M * 16; w_bytes = (size_t)a.N * 256;
+    g.lda = 8; g.M = (int)M; g.K = 128; g.mode = A_CONV_SMALLC; g.H = a.H; g.W = a.Wd; g.OH = a.H; g.OW = a.Wd; g.stride = 1; g.Cin = 8;
+    g.rows_per_sample = a.rows_per_sample > 0 ? a.rows_per_sample : a.H * a.Wd;
+  } else if (a.mode == 1) {
+    if (a.B < 0 || a.H < 0 || a.Wd < 0 || (a.stride != 1 && a.stride != 2)) return bad("conv3: sizes >= 0, stride 1 or 2");
+    const int IH = a.ups ? 2 * a.H : a.H, IW = a.ups ? 2 * a.Wd : a.Wd;
+    const int OH = (IH - 1) / a.stride + 1, OW = (IW - 1) / a.stride + 1;
+    a_bytes = ((size_t)a.B * a.H * a.Wd - 1) * a.lda * 2 + (size_t)(a.a_lo + a.Cin) * 2;
+    w_bytes = (size_t)a.N * 9 * a.Cin * 2;
+    g.lda = a.lda; g.M = a.B * OH * OW; g.K = 9 * a.Cin * (a.a_lo > 0 ? 2 : 1); g.mode = A_CONV3; g.H = a.H; g.W = a.Wd; g.OH = OH; g.OW = OW;
+    if (a.a_lo > 0) { g.k_w = 9 * a.Cin; g.a_lo_bytes = (uint32_t)a.a_lo * 2u; }
+    g.stride = a.stride; g.ups = a.ups ? 1 : 0; g.pad0 = a.pad0 ? 1 : 0; g.Cin = a.Cin;
+    g.rows_per_sample = a.rows_per_sample > 0 ? a.rows_per_sample : OH * OW;
+  } else if (a.mx) {                                                             // fp8 rows in 2-byte units (kernels.h GemmParams::mx), query only
+    if ((a.K % 128) || (a.lda % 2)) return bad("fp8: K must be a multiple of 128, lda even");
+    a_bytes = ((size_t)a.M - 1) * a.lda + (size_t)a.K; w_bytes = (size_t)a.N * a.K;
+    g.lda = a.lda / 2; g.M = a.M; g.K = a.K / 2; g.mode = A_DENSE; g.mx = 1;
+    g.rows_per_sample = 1;
+  } else {
+    a_bytes = ((size_t)a.M - 1) * a.lda * 2 + (size_t)(a.a_lo + a.K) * 2;
+    w_bytes = (size_t)a.N * a.K * 2;
+    g.lda = a.lda; g.M = a.M; g.K = a.a_lo > 0 ? 2 * a.K : a.K; g.mode = A_DENSE;
+    if (a.a_lo > 0) { g.k_w = a.K; g.a_lo_bytes = (uint32_t)a.a_lo * 2u; }
+    g.rows_per_sample = a.rows_per_sample > 0 ? a.rows_per_sample : 1;
+  }
+  if (g.M <= 0 || a.N == 0) { g.N = a.N; return GDF_OK; }                        // empty problem: nothing is launched
+  if (!(a_bytes < (1ull << 31) && w_bytes < (1ull << 31))) {
+    if (what) span_ok(a_bytes, w_bytes, what);
+    return GDF_ERR_UNSUPPORTED;
+  }
+  g.A = (const half_t*)a.A; g.a_bytes = (uint32_t)a_bytes; g.N = a.N;
+  g.Wt = (const half_t*)a.W; g.w_bytes = (uint32_t)w_bytes;
+  const int Nout = a.geglu ? a.N / 2 : a.N;
+  g.bias = a.bias; g.rowvec = a.rowvec; g.ldrv = a.ldrv > 0 ? a.ldrv : a.N;
+  g.res32 = a.res32; g.res16 = (const half_t*)a.res16; g.ldres = a.ldres > 0 ? a.ldres : Nout;
+  g.out16 = (half_t*)a.out16; g.ldo16 = a.ldo16 > 0 ? a.ldo16 : Nout; g.out32 = a.out32; g.ldo32 = a.ldo32 > 0 ? a.ldo32 : Nout;
+  g.aux16 = (half_t*)a.aux16; g.ldaux = a.ldaux > 0 ? a.ldaux : Nout;
+  g.geglu = a.geglu ? 16 : 0; g.bn = a.bn == 16 ? 16 : 128; g.variant = a.variant; g.no_superblock = a.no_superblock ? 1 : 0;
+  g.batch = a.batch; g.w_bstride = a.w_bstride; g.o_bstride = a.o_bstride;
+  g.dit = a.dit || a.mx ? 1 : 0; g.act = a.act; g.rv_mul = a.rv_mul; g.rv_seg_rows = a.rv_seg_rows; g.rv_rps2 = a.rv_rps2 > 0 ? a.rv_rps2 : 1; g.rv_tok = a.rv_tok;
+  g.qkn_nq = a.qkn_nq; g.qkn_wq = a.qkn_wq; g.qkn_wk = a.qkn_wk; g.qkn_eps = a.qkn_eps; g.rope_cos = a.rope_cos; g.rope_sin = a.rope_sin;
+  g.qkn_pos0 = a.qkn_pos0; g.qkn_rps = a.qkn_rps > 0 ? a.qkn_rps : 1; g.qkn_seg_rows = a.qkn_seg_rows; g.qkn_pos1 = a.qkn_pos1; g.qkn_rps2 = a.qkn_rps2 > 0 ? a.qkn_rps2 : 1;
+  g.bf16 = a.bf16 || a.mx ? 1 : 0; g.out_f16 = a.out_f16;
+  g.acc_scale = a.acc_scale; g.out16_scale = a.out16_scale; g.o16_lo = a.o16_lo; g.cus = a.cus;
+  return GDF_OK;
+}
+
 extern "C" {
 
 int gdf_op_attention_ex(const gdf_attn_args* args, void* stream) {
@@ -36,6 +94,26 @@ int gdf_op_attention_ex(const gdf_attn_args* args, void* stream) {
 
 const char* gdf_op_attention_kernel(const gdf_attn_args* args) {
   return args ? attention_kernel_name(attn_params(*args)) : nullptr;
+}
+
+int gdf_op_gemm_ex(const gdf_gemm_args* args, void* stream) {
+  if (!args) { set_error("gdf_op_gemm_ex: args is NULL"); return GDF_ERR_ARG; }
+  if (args->mx) { set_error("gdf_op_gemm_ex: the fp8 form is launched by gdf_op_gemm_mx (it needs the operands' scales)"); return GDF_ERR_ARG; }
+  GemmParams g{};
+  const int rc = gemm_params(*args, g, "gemm_ex");
+  if (rc != GDF_OK) return rc;
+  if (!gemm_variant_ok(g)) { set_error("gemm_ex: this form has no instantiation of the forced tile variant"); return GDF_ERR_ARG; }
+  if (args->splitk > 1) return fin(launch_gemm_splitk(g, args->splitk, args->splitk_ws, (hipStream_t)stream), "gemm_ex");
+  return fin(launch_gemm(g, (hipStream_t)stream), "gemm_ex");
+}
+
+const char* gdf_op_gemm_kernel(const gdf_gemm_args* args) {
+  if (!args) return nullptr;
+  GemmParams p{}, g{};
+  if (gemm_params(*args, p, nullptr) != GDF_OK || p.M <= 0 || p.N <= 0) return nullptr;
+  int splitk = args->splitk;
+  if (!gemm_splitk_pass1(p, splitk, nullptr, g)) return nullptr;      // (splitk <= 1: g = p)
+  return gemm_check(g) == hipSuccess && gemm_variant_ok(g) ? gemm_kernel_name(g) : nullptr;
 }
 
 int gdf_op_gemm(const void* A, int lda, const void* W, const float* bias, const float* res32, const void* res16,

@@ -28,6 +28,62 @@ int gdf_op_conv3x3(const void* x, int ld, int B, int H, int W, int Cin, const vo
                    const float* rowvec, int stride, int ups, const float* res32, void* aux16, void* out16,
                    float* out32, int narrow /* bit0: BN=16; bits 8..: tile variant */, void* stream);
 
+/* The complete GEMM / 3x3-conv launch: every field a plan builder sets (csrc/kernels.h GemmParams), one launch_gemm (or launch_gemm_splitk).
+ *   A, lda       dense: fp16 (bf16 = 1: bf16) rows [M][lda]; conv3: NHWC x[B][H][W][lda >= Cin].  A column offset is part of the pointer.
+ *   mode         0 dense (M, N, K), 1 conv3 (B, H, W, Cin, stride, ups, pad0; N = Cout; M and K are derived: M = B * OH * OW with
+ *                OH = (IH - 1) / stride + 1, IH = ups ? 2 H : H, K = 9 * Cin).  pad0 = 1: zero padding right / bottom only.
+ *   K            dense: the WEIGHT matrix's contraction size; a_lo > 0: A rows are split (hi | lo) pairs, lo a_lo elements after hi, and the
+ *                launch contracts over 2 K (conv3 likewise per pixel).  The byte extents of A and W (out-of-range loads return 0) are
+ *                derived as gdf_op_gemm_split / gdf_op_conv3x3_split derive them; operands of 2 GiB and more are rejected.
+ *   W            [N][K] fp16 / bf16 (conv3: the gdf_op_relayout_conv3 layout; geglu: gdf_op_relayout_geglu(group 16) rows and bias).
+ *   bias, rowvec fp32 [N] / [samples][ldrv]; rows_per_sample 0 = 1 (dense) or OH * OW (conv3); ldrv 0 = N.
+ *   res32 | res16 (ldres), out16 (ldo16), out32 (ldo32), aux16 (ldaux): leading dimensions in elements, 0 = the output width (N, geglu: N / 2).
+ *   bn           0 | 128, or 16 = the narrow-N tile; variant: a tile forced as in gdf_op_gemm's flags bits 8..19; one the form has no
+ *                instantiation of (826 on a dense GEMM) is an error here and NULL from the query.
+ *   splitk > 1   launch_gemm_splitk with the workspace splitk_ws (splitk * M * N floats).
+ *   batch > 1    `batch` problems sharing A: problem b reads W + b * w_bstride and writes out16 + b * o_bstride (elements).
+ *   dit          the MMDiT epilogue of gdf_op_gemm_dit: act, rv_mul, rv_seg_rows / rv_rps2, rv_tok (row vector per token: row % rows_per_sample),
+ *                qkn_* (RMSNorm + rotary embedding on the q / k heads; position qkn_pos0 + row % qkn_rps, rows >= qkn_seg_rows > 0:
+ *                qkn_pos1 + (row - qkn_seg_rows) % qkn_rps2; rope tables fp32 [position][128]), bf16 operands, out_f16 (saturating fp16 store).
+ *   acc_scale, out16_scale   v = acc * acc_scale + bias ...; out16 = e16(v * out16_scale); 0 means 1.
+ *   o16_lo > 0   out16 is written as a split (hi, lo) pair, lo o16_lo elements after hi in the same row.
+ *   cus > 0      tile choice, persistent grid and super-block order as on a stream restricted to `cus` CUs.
+ *   conv3 with Cin <= 8   the conv_in form (what gdf_op_conv_in prepares in its scratch): A is the image as NHWC pixels of 8 packed fp16
+ *                channels (channels from Cin up zero; lda is not read), W is [N][16 taps][8 channels] (taps from 9 up and channels from Cin up
+ *                zero); stride 1, no ups / pad0 / a_lo.  Every epilogue field applies, o16_lo included (the conv_in of a "precise" plan).
+ *   mx           gdf_op_gemm_kernel only: the fp8 form of gdf_op_gemm_mx (K in bytes, a multiple of 128); gdf_op_gemm_ex refuses it. */
+typedef struct gdf_gemm_args {
+  const void* A; int lda;
+  const void* W;
+  int mode;
+  int M, N, K;
+  int B, H, Wd, Cin, stride, ups, pad0;
+  const float* bias;
+  const float* rowvec; int rows_per_sample, ldrv;
+  const float* res32; const void* res16; int ldres;
+  void* out16; int ldo16;
+  float* out32; int ldo32;
+  void* aux16; int ldaux;
+  int geglu, bn, variant, no_superblock;
+  int splitk; float* splitk_ws;
+  int batch; long w_bstride, o_bstride;
+  int dit, act, rv_mul, rv_seg_rows, rv_rps2, rv_tok;
+  int qkn_nq; const float* qkn_wq; const float* qkn_wk; float qkn_eps; const float* rope_cos; const float* rope_sin;
+  int qkn_pos0, qkn_rps, qkn_seg_rows, qkn_pos1, qkn_rps2;
+  int bf16, out_f16;
+  float acc_scale, out16_scale;
+  int a_lo, o16_lo;
+  int cus;
+  int mx;
+} gdf_gemm_args;
+int gdf_op_gemm_ex(const gdf_gemm_args* args, void* stream);
+/* Symbol of the GEMM kernel gdf_op_gemm_ex launches for these arguments, as a profiler prints it without namespace and signature
+ * ("gemm_kernel<1, 256, 320, 9, false>": mode, tile rows, tile columns, stages (8 / 9: the 8-phase main loops), GEGLU;
+ * "gemm_dit_kernel<256, 256, 8, true, false>": tile, stages, bf16, QKN).  With splitk > 1: the kernel of the partial-sum launch.
+ * Host arithmetic only: no device is touched and no pointer is followed (only whether res32 / res16 / rowvec / aux16 / out32 are set
+ * matters).  NULL for arguments the launch rejects and for an empty problem.  The string lives as long as the library. */
+const char* gdf_op_gemm_kernel(const gdf_gemm_args* args);
+
 /* SPLIT-OPERAND forms (the opt-in "precise" plans, gdf.h gdf_plan_opts.reserved[1]): an activation is a pair of fp16 numbers
  * hi = fp16(v), lo = fp16(v - hi) stored in ONE row, lo `a_lo` (input) / `o16_lo` / `y_lo` / `o_lo` (output) elements after hi, and a
  * contraction runs over [hi | lo] against the weight matrix read twice: out = (hi + lo) W^T to fp32 accuracy.  a_lo = 0 / *_lo = 0:

@@ -20,8 +20,25 @@ class AttnArgs(C.Structure):
                 ("q_lo", ci), ("kv_lo", ci), ("o_scale", fp)]
 
 
+class GemmArgs(C.Structure):
+    """gdf_gemm_args of include/gdf_ops.h (same field order)"""
+    _fields_ = [("A", vp), ("lda", ci), ("W", vp), ("mode", ci), ("M", ci), ("N", ci), ("K", ci),
+                ("B", ci), ("H", ci), ("Wd", ci), ("Cin", ci), ("stride", ci), ("ups", ci), ("pad0", ci),
+                ("bias", vp), ("rowvec", vp), ("rows_per_sample", ci), ("ldrv", ci),
+                ("res32", vp), ("res16", vp), ("ldres", ci), ("out16", vp), ("ldo16", ci), ("out32", vp), ("ldo32", ci),
+                ("aux16", vp), ("ldaux", ci), ("geglu", ci), ("bn", ci), ("variant", ci), ("no_superblock", ci),
+                ("splitk", ci), ("splitk_ws", vp), ("batch", ci), ("w_bstride", C.c_long), ("o_bstride", C.c_long),
+                ("dit", ci), ("act", ci), ("rv_mul", ci), ("rv_seg_rows", ci), ("rv_rps2", ci), ("rv_tok", ci),
+                ("qkn_nq", ci), ("qkn_wq", vp), ("qkn_wk", vp), ("qkn_eps", fp), ("rope_cos", vp), ("rope_sin", vp),
+                ("qkn_pos0", ci), ("qkn_rps", ci), ("qkn_seg_rows", ci), ("qkn_pos1", ci), ("qkn_rps2", ci),
+                ("bf16", ci), ("out_f16", ci), ("acc_scale", fp), ("out16_scale", fp), ("a_lo", ci), ("o16_lo", ci),
+                ("cus", ci), ("mx", ci)]
+
+
 OPS = {
     "gdf_op_gemm": (ci, [vp, ci, vp, vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp]),
+    "gdf_op_gemm_ex": (ci, [C.POINTER(GemmArgs), vp]),
+    "gdf_op_gemm_kernel": (C.c_char_p, [C.POINTER(GemmArgs)]),
     "gdf_op_conv3x3": (ci, [vp, ci, ci, ci, ci, ci, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp]),
     "gdf_op_conv_in": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp]),
     "gdf_op_gemm_split": (ci, [vp, ci, ci, vp, vp, vp, ci, vp, ci, ci, vp, ci, ci, ci, ci, ci, vp]),
