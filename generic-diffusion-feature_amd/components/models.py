@@ -164,6 +164,66 @@ def scheduler_step_scalars(scheduler, timestep):
     return a, b
 
 
+def ddim_timesteps(config, num_inference_steps, num_train_timesteps=1000):
+    """DDIMScheduler.set_timesteps(num_inference_steps).timesteps (descending ints) from the scheduler config alone — the published rule of
+    diffusers' DDIMScheduler per `timestep_spacing` (Table 2 of arXiv 2305.08891), restated so that no diffusers install is needed; the class
+    itself is used when it can be imported.  `config`: anything with attributes or keys (a missing entry takes DDIMScheduler's default)."""
+    def cfg(name, default):
+        if config is None:
+            return default
+        if isinstance(config, dict):
+            return config.get(name, default)
+        return getattr(config, name, default)
+    T = int(cfg("num_train_timesteps", num_train_timesteps))
+    offset = int(cfg("steps_offset", 0))
+    spacing = cfg("timestep_spacing", "leading")
+    n = int(num_inference_steps)
+    if n < 1 or n > T:
+        raise ValueError(f"num_inference_steps must be in [1, {T}]")
+    try:
+        from diffusers import DDIMScheduler
+        sch = DDIMScheduler.from_config(config)
+        sch.set_timesteps(n)
+        return [int(v) for v in sch.timesteps]
+    except Exception:                                                # not importable here, or a config the class does not take: the rule itself
+        pass
+    import numpy as np
+    if spacing == "linspace":
+        ts = np.linspace(0, T - 1, n).round()[::-1].astype(np.int64)
+    elif spacing == "leading":
+        ts = (np.arange(0, n) * (T // n)).round()[::-1].astype(np.int64) + offset
+    elif spacing == "trailing":
+        ts = np.round(np.arange(T, 0, -T / n)).astype(np.int64) - 1
+    else:
+        raise ValueError(f"unknown timestep_spacing {spacing!r}: 'leading', 'trailing' or 'linspace'")
+    return [int(v) for v in ts]
+
+
+def ddim_inversion_table(scheduler, num_inference_steps, stop_at_t):
+    """The reference's DDIM inversion loop (feature/components/ddim_inversion.py:19-43) as rows (timestep, c_in, c_sample, c_eps) for
+    NativeUNet.trajectory: the DDIM timesteps of `scheduler.config` reversed (ascending) and walked from index 1; at timestep t the UNet sees
+    the latents as they are (c_in = 1: DDIM's scale_model_input is the identity, and the loop does not call it, :28-31) and
+        current_t = max(0, t - 1000 // n), a_cur = alphas_cumprod[current_t], a_next = alphas_cumprod[t]
+        latents = (latents - sqrt(1 - a_cur) eps) sqrt(a_next / a_cur) + sqrt(1 - a_next) eps                                  (:39-41)
+                = c_sample latents + c_eps eps,   c_sample = sqrt(a_next / a_cur),  c_eps = sqrt(1 - a_next) - sqrt(1 - a_cur) c_sample;
+    the loop ends after the first step with t >= stop_at_t (:42-43).  alphas_cumprod is the PIPELINE scheduler's (:35-36); a scheduler without a
+    config (the synthetic pipes') takes DDIMScheduler's defaults over its own number of training steps.  Coefficients are computed in float64."""
+    ac = scheduler.alphas_cumprod
+    ac = ac.double().cpu().tolist() if torch.is_tensor(ac) else [float(v) for v in ac]
+    n = int(num_inference_steps)
+    stop = float(stop_at_t.flatten()[0]) if torch.is_tensor(stop_at_t) else float(stop_at_t)
+    ts = ddim_timesteps(getattr(scheduler, "config", None), n, num_train_timesteps=len(ac))[::-1]
+    rows = []
+    for i in range(1, n):
+        t = ts[i]
+        a_cur, a_next = ac[max(0, t - 1000 // n)], ac[t]
+        c_sample = (a_next / a_cur) ** 0.5
+        rows.append((t, 1.0, c_sample, (1.0 - a_next) ** 0.5 - (1.0 - a_cur) ** 0.5 * c_sample))
+        if t >= stop:
+            break
+    return rows
+
+
 def native_vae_decoder(pipe, device):
     """The pipe's native AutoencoderKL decoder, created on first use (only a config that asks for 'vae-out' needs it)."""
     dec = getattr(pipe, "_native_vae_decoder", None)

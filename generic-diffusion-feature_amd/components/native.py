@@ -66,6 +66,8 @@ SIGNATURES = {
     "gdf_plan_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_int]),
+    "gdf_trajectory": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "gdf_plan_set_graph": (C.c_int, [C.c_void_p, C.c_int]),
     "gdf_plan_graph_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "gdf_plan_graph_failures": (C.c_long, [C.c_void_p]),
@@ -811,13 +813,14 @@ class NativeUNet(_NativeModel):
         return ".norm" in name or name.startswith("conv_norm_out")
 
     # ---- plans ------------------------------------------------------------------------------------
-    def _plan(self, batch, h, w, n_ctx, hook_ids, shared_ctx=False, split=None):
+    def _plan(self, batch, h, w, n_ctx, hook_ids, shared_ctx=False, split=None, early_exit=None):
         split = self.split_for(hook_ids, lat=min(h, w)) if split is None else split
-        key = (batch, h, w, n_ctx, tuple(hook_ids), self.stream_fp32, self.early_exit, bool(shared_ctx), split, self.cus)
+        early_exit = self.early_exit if early_exit is None else bool(early_exit)
+        key = (batch, h, w, n_ctx, tuple(hook_ids), self.stream_fp32, early_exit, bool(shared_ctx), split, self.cus)
         p = self._plans.get(key)
         if p is None:
             ids = (C.c_char_p * max(1, len(hook_ids)))(*[s.encode() for s in hook_ids])
-            opts = PlanOpts(int(self.stream_fp32), int(self.early_exit))
+            opts = PlanOpts(int(self.stream_fp32), int(early_exit))
             opts.reserved[0] = int(bool(shared_ctx))
             opts.reserved[1] = 1 if split == SPLIT_ALL else (split << 8)
             opts.reserved[2] = int(self.cus)
@@ -872,6 +875,51 @@ class NativeUNet(_NativeModel):
                 return n_.permute(0, 3, 1, 2), o_
             noise_nchw, out = self._verify_level(run, ids, (noise_nchw, out))
         return noise_nchw, out
+
+    # ---- multi-step latent trajectory ---------------------------------------------------------------------
+    TRAJECTORY_MAX_STEPS = 1024          # GDF_TRAJECTORY_MAX_STEPS (include/gdf.h)
+
+    def trajectory(self, latents_f32, table, encoder_hidden_states, text_embeds=None, time_ids=None, shared_ctx=False, eager=False):
+        """len(table) x (one hook-less forward + one scheduler update) on the device (gdf_trajectory, include/gdf.h): row k of `table` is
+        (timestep, c_in, c_sample, c_eps); forward k sees fp16(c_in[k] * x_k) at timestep[k], then x_{k+1} = c_sample[k] x_k + c_eps[k] noise_pred_k
+        on the fp32 master.  Returns the final fp32 latents (B,4,H,W) as a new tensor; `latents_f32` is not modified.
+        The plan has no hooks (the reference pauses its feature store meanwhile, diffusion_feature.py:384-386).  Its operand-split level is the
+        one the CURRENT feature selection (requested_ids) gives the extraction forward that consumes the result: the latents are that forward's
+        input and are not computed at a coarser level than its hooks are promised at."""
+        dev = self.device
+        B, _, H, W = latents_f32.shape
+        ctx = encoder_hidden_states
+        rows = [tuple(float(v) for v in r) for r in table]
+        if not rows or len(rows) > self.TRAJECTORY_MAX_STEPS or any(len(r) != 4 for r in rows):
+            raise ValueError(f"table must hold 1..{self.TRAJECTORY_MAX_STEPS} rows of (timestep, c_in, c_sample, c_eps)")
+        txt = tid = None
+        if self.cfg["addition_embed_text_time"]:
+            if text_embeds is None or time_ids is None:
+                raise ValueError("text_embeds and time_ids are required for this UNet")
+            txt, tid = text_embeds, time_ids
+            pooled = self.cfg["add_in_dim"] - 6 * self.cfg["addition_time_embed_dim"]
+            if tuple(txt.shape) != (B, pooled) or tuple(tid.shape) != (B, 6):
+                raise ValueError(f"text_embeds {tuple(txt.shape)} / time_ids {tuple(tid.shape)} do not match the model "
+                                 f"(expected ({B},{pooled}) / ({B},6))")
+        if ctx.shape[0] != B or ctx.shape[2] != self.cfg["cross_attention_dim"]:
+            raise ValueError("encoder_hidden_states shape mismatch")
+        ids = self.requested_ids()
+        have = set(ids)
+        split = self.split_for(ids + [i for i in self.extra_hook_ids if i not in have], lat=min(H, W))
+        plan = self._plan(B, H, W, ctx.shape[1], (), shared_ctx, split, early_exit=False)
+        flat = (C.c_float * (4 * len(rows)))(*[v for r in rows for v in r])
+        lib = self.lib
+
+        def call(staged, hook_ptrs, out_ptr, ws_ptr, stream_ptr):
+            vp = lambda a: C.c_void_p(a.data_ptr() if a is not None else 0)
+            x32, c, tx, ti = staged
+            _check(lib.gdf_trajectory(plan.handle, vp(x32), len(rows), flat, vp(c), vp(tx), vp(ti), out_ptr, ws_ptr, stream_ptr), "trajectory")
+
+        f16, f32 = torch.float16, torch.float32
+        plan.run(dev, [("x32", latents_f32, f32), ("ctx", ctx, f16), ("txt", txt, f16), ("tid", tid, f32)],
+                 (B, H, W, self.cfg["out_channels"]), call, eager=eager)
+        # the master lives in the plan's staging buffer, which the next call overwrites: hand out a copy (ordered on the caller's stream)
+        return plan.staged["x32"].clone()
 
     def __call__(self, sample, timestep=None, encoder_hidden_states=None, added_cond_kwargs=None,
                  down_block_additional_residuals=None, mid_block_additional_residual=None, return_dict=False,

@@ -248,6 +248,13 @@ int gdf_forward(gdf_plan* p, const void* latents, const float* timesteps, const 
                       workspace, (hipStream_t)stream, nullptr, nullptr, nullptr, 0);
 }
 
+int gdf_trajectory(gdf_plan* p, float* latents_f32, int n_steps, const float* table, const void* ctx, const void* add_text_embeds,
+                   const float* add_time_ids, void* noise_pred_scratch, void* workspace, void* stream) {
+  if (!p) { set_error("null plan"); return GDF_ERR_ARG; }
+  return plan_trajectory(p->p, *p->p.model, latents_f32, n_steps, table, ctx, add_text_embeds, add_time_ids, noise_pred_scratch, workspace,
+                         (hipStream_t)stream);
+}
+
 int gdf_plan_profile(gdf_plan* p, const void* latents, const float* timesteps, const void* ctx,
                      const void* add_text_embeds, const float* add_time_ids, void* const* hook_out, void* noise_pred,
                      void* workspace, void* stream, float* ms, const char** names, double* flops, int cap) {

@@ -8,6 +8,8 @@
 //   2321-2324) + apply_rotary_emb (attention_processor.py:2331-2335)                           -> qk_norm_rope_kernel
 //   FluxPosEmbed (transformer_flux.py:498-499)                                                 -> rope_table_kernel
 // All are streaming kernels: 16 bytes per lane, one pass over the data.
+#include <algorithm>
+
 #include "kernels.h"
 
 namespace gdf {
@@ -481,6 +483,90 @@ __global__ void silu_vec_kernel(const float* x, float* out, long n) {
 hipError_t launch_silu_vec(const float* x, float* out, long n, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(silu_vec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, out, n);
+  return hipGetLastError();
+}
+
+// ---- multi-step latent trajectory (gdf_trajectory, include/gdf.h): the scheduler update between two denoiser forwards ----
+// Replaces the latent update of the reference's inversion loop (components/ddim_inversion.py:39-41) and, in general, any scheduler step of the
+// form x' = c_sample x + c_eps eps followed by scale_model_input.  It lives in this file because this file is compiled without SLP vectorisation
+// (no packed-fp32 forms: DESIGN.md 3.5) and the kernel runs between forwards while other queues may run GEMMs.
+//   x     fp32 master latents (B, 4, H, W) NCHW, updated in place
+//   eps   fp16 noise_pred (B, H, W, 4) channels-last, as the plan's conv_out writes it; read only
+//   y     fp16 (B, 4, H, W): the next forward's input  c_in[next] * x'
+//   tbuf  fp32 (B): the next forward's timestep
+//   steps int32 {step, ticket, n_rows, 0} followed by float rows[n_rows][4] = {timestep, c_in, c_sample, c_eps}
+// Launch k reads row `step` for the update and row min(step + 1, n_rows - 1) for c_in and the timestep, then step becomes step + 1: every step
+// of a trajectory is the SAME launch with the SAME arguments, so one hipGraph serves them all.  `step` is advanced by the workgroup that
+// finishes last (ticket counter), i.e. after every workgroup has read it.  prime = 1: no update (eps is not read, x is not written), row 0
+// supplies c_in and the timestep and step becomes 0 — the launch in front of the first forward.  step outside [0, n_rows): nothing is written.
+__global__ __launch_bounds__(256) void latent_step_kernel(float* x, const half_t* eps, half_t* y, float* tbuf, int* steps, int B, int HW,
+                                                          int hw8, int prime) {
+  const int k = steps[0], n = steps[2];
+  if (n < 1) return;
+  const bool live = prime || (k >= 0 && k < n);
+  if (live) {
+    const float* rows = (const float*)(steps + 4);
+    const int nx = prime ? 0 : (k + 1 < n ? k + 1 : n - 1);
+    const float cs = prime ? 1.f : rows[4 * k + 2], ce = prime ? 0.f : rows[4 * k + 3];
+    const float tn = rows[4 * nx], cin = rows[4 * nx + 1];
+    const long stride = (long)gridDim.x * blockDim.x, t0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    // 8 pixels of one sample per item: per channel two 16-byte loads / stores of x and one 16-byte store of y; eps: four 16-byte loads
+    for (long i = t0; i < (long)B * hw8; i += stride) {
+      const long b = i / hw8;
+      const int p0 = (int)(i - b * hw8) * 8;
+      f16x8 ev[4];
+      if (!prime) {
+        const f16x8* ep = (const f16x8*)(eps + ((size_t)b * HW + p0) * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ev[j] = ep[j];
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        float* xp = x + ((size_t)b * 4 + c) * HW + p0;
+        f32x4 xa = *(const f32x4*)xp, xb = *(const f32x4*)(xp + 4);
+        f16x8 yo;
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+          float v = p < 4 ? xa[p] : xb[p - 4];
+          if (!prime) v = __fmaf_rn(cs, v, ce * (float)ev[p >> 1][(p & 1) * 4 + c]);
+          if (p < 4) xa[p] = v; else xb[p - 4] = v;
+          yo[p] = (_Float16)(cin * v);
+        }
+        if (!prime) { *(f32x4*)xp = xa; *(f32x4*)(xp + 4) = xb; }
+        *(f16x8*)(y + ((size_t)b * 4 + c) * HW + p0) = yo;
+      }
+    }
+    // scalar tail: the pixels of every sample past its last whole group (all of them when a plane is no multiple of 16 bytes)
+    const int tail = HW - hw8 * 8;
+    for (long i = t0; i < (long)B * tail; i += stride) {
+      const long b = i / tail;
+      const int p = hw8 * 8 + (int)(i - b * tail);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const size_t o = ((size_t)b * 4 + c) * HW + p;
+        float v = x[o];
+        if (!prime) { v = __fmaf_rn(cs, v, ce * (float)eps[((size_t)b * HW + p) * 4 + c]); x[o] = v; }
+        y[o] = (_Float16)(cin * v);
+      }
+    }
+    if (blockIdx.x == 0) for (int b = threadIdx.x; b < B; b += blockDim.x) tbuf[b] = tn;
+  }
+  __syncthreads();                               // every wave of this workgroup has read `step`
+  if (threadIdx.x == 0) {
+    const unsigned t = atomicAdd((unsigned*)&steps[1], 1u);
+    if (t == gridDim.x - 1) { steps[1] = 0; if (live) steps[0] = prime ? 0 : k + 1; }
+  }
+}
+
+hipError_t launch_latent_step(float* x, const half_t* eps, half_t* y, float* tbuf, int* steps, int B, int H, int W, int prime, hipStream_t s) {
+  const long HW = (long)H * W;
+  if (B < 1 || H < 1 || W < 1 || (size_t)B * HW * 4 >= (1ull << 31)) return hipErrorInvalidValue;
+  if (!x || !y || !tbuf || !steps || (!prime && !eps)) return hipErrorInvalidValue;
+  const bool al = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)eps) & 15) == 0;
+  const int hw8 = (al && HW % 8 == 0) ? (int)(HW / 8) : 0;
+  const long items = (long)B * (hw8 ? hw8 : HW);
+  const unsigned grid = (unsigned)std::min<long>((items + 255) / 256, 256);
+  hipLaunchKernelGGL(latent_step_kernel, dim3(grid), dim3(256), 0, s, x, eps, y, tbuf, steps, B, (int)HW, hw8, prime);
   return hipGetLastError();
 }
 

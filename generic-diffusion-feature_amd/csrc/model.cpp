@@ -626,6 +626,18 @@ struct B : PlanBuilder {   // UNet op program
 
 }  // namespace
 
+// trajectory state at the end of a hook-less plan's workspace (model.h Plan::traj_off), every part 256-byte aligned
+struct TrajLayout { size_t lat16, tbuf, steps, end; };
+static TrajLayout traj_layout(const Plan& P) {
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  TrajLayout L;
+  L.lat16 = P.traj_off;
+  L.tbuf = L.lat16 + up((size_t)P.batch * P.model->arch.in_channels * P.H * P.W * 2);
+  L.steps = L.tbuf + up((size_t)P.batch * 4);
+  L.end = L.steps + up(16 + (size_t)GDF_TRAJECTORY_MAX_STEPS * 16);
+  return L;
+}
+
 int plan_build(const Model& m, Plan& P, int batch, int H, int W, int n_ctx, const char* const* ids, int n_ids,
                const PlanOpts& opts, bool dry) {
   const int L = m.arch.n_levels;
@@ -669,6 +681,10 @@ int plan_build(const Model& m, Plan& P, int batch, int H, int W, int n_ctx, cons
   b.build(H, W);
   if (b.bad) return GDF_ERR_UNSUPPORTED;
   P.ws_bytes = b.ar.peak + 256;
+  if (!dry && P.requested.empty() && !opts.early_exit && P.writes_noise) {
+    P.traj_off = (P.ws_bytes + 255) & ~(size_t)255;
+    P.ws_bytes = traj_layout(P).end;
+  }
   return GDF_OK;
 }
 
@@ -768,6 +784,16 @@ static hipError_t record_in_capture(hipEvent_t ev, hipStream_t) {
   return r ? record_event_node(*r, ev) : hipErrorInvalidValue;
 }
 
+// Trajectory calls (plan_trajectory binds the fp32 master): the scheduler update follows the op program — in the same graph when one is recorded.
+// Plans built with hooks never get here with a master bound, and their op program is untouched.
+static int traj_step(const Plan& P, const Bind& b, hipStream_t s) {
+  if (P.traj_off == NPOS || !b.base[BUF_X32]) return GDF_OK;
+  const hipError_t e = launch_latent_step((float*)b.base[BUF_X32], (const half_t*)b.base[BUF_NOISE], (half_t*)b.base[BUF_LAT],
+                                          (float*)b.base[BUF_T], (int*)b.ws(traj_layout(P).steps), P.batch, P.H, P.W, 0, s);
+  if (e != hipSuccess) { set_error(std::string("op 'latent_step' failed: ") + hipGetErrorString(e)); return GDF_ERR_HIP; }
+  return GDF_OK;
+}
+
 // evset >= 0: record the timing events of set `evset` around every op of the timed label; `external` = while this thread records the plan's
 // graph (event-record nodes that fire at every replay)
 static int run_ops_eager(Plan& P, const Bind& b, hipStream_t s, int evset = -1, bool external = false) {
@@ -791,7 +817,7 @@ static int run_ops_eager(Plan& P, const Bind& b, hipStream_t s, int evset = -1, 
     }
     if (e != hipSuccess) { set_error(std::string("op '") + op.name + "' failed: " + hipGetErrorString(e)); return GDF_ERR_HIP; }
   }
-  return GDF_OK;
+  return traj_step(P, b, s);
 }
 
 // hipGraph path: the op program is recorded once per distinct binding table into a hipGraph (explicit kernel nodes, launch.h) and replayed on
@@ -909,6 +935,37 @@ int plan_run(Plan& P, const Bind& b, hipStream_t s, float* ms, const char** name
     ++i;
   }
   if (ms) { hipEventDestroy(e0); hipEventDestroy(e1); }
+  return traj_step(P, b, s);
+}
+
+int plan_trajectory(Plan& P, const Model& m, float* x32, int n_steps, const float* table, const void* ctx, const void* txt, const float* tid,
+                    void* noise, void* ws, hipStream_t s) {
+  if (m.kind != 0) { set_error("gdf_trajectory needs a UNet plan"); return GDF_ERR_STATE; }
+  if (m.n_set != (int)m.params.size()) { set_error("model weights incomplete"); return GDF_ERR_STATE; }
+  if (P.traj_off == NPOS) { set_error("gdf_trajectory needs a plan created with zero hooks and early_exit off"); return GDF_ERR_STATE; }
+  if (!x32 || !table || !ctx || !noise || !ws) { set_error("null input pointer"); return GDF_ERR_ARG; }
+  if (n_steps < 1 || n_steps > GDF_TRAJECTORY_MAX_STEPS) { set_error("n_steps must be in [1, GDF_TRAJECTORY_MAX_STEPS]"); return GDF_ERR_ARG; }
+  const TrajLayout L = traj_layout(P);
+  // the latent_step block, uploaded once: {step 0, ticket 0, n_rows, 0} and the coefficient rows
+  P.traj_host.resize(4 + 4 * (size_t)n_steps);
+  const int32_t hdr[4] = {0, 0, n_steps, 0};
+  memcpy(P.traj_host.data(), hdr, sizeof hdr);
+  memcpy(P.traj_host.data() + 4, table, 16 * (size_t)n_steps);
+  if (hipMemcpyAsync((char*)ws + L.steps, P.traj_host.data(), P.traj_host.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) {
+    set_error("gdf_trajectory: table upload failed"); return GDF_ERR_HIP;
+  }
+  Bind b;
+  b.base[BUF_WS] = (char*)ws; b.base[BUF_WT] = (char*)m.weights; b.base[BUF_LAT] = (char*)ws + L.lat16; b.base[BUF_T] = (char*)ws + L.tbuf;
+  b.base[BUF_CTX] = (char*)ctx; b.base[BUF_TXT] = (char*)txt; b.base[BUF_TID] = (char*)tid; b.base[BUF_NOISE] = (char*)noise;
+  b.base[BUF_X32] = (char*)x32;
+  // the first forward's input and timestep (row 0); from here on every step is the same launch sequence with the same arguments
+  const hipError_t e = launch_latent_step(x32, nullptr, (half_t*)b.base[BUF_LAT], (float*)b.base[BUF_T], (int*)b.ws(L.steps), P.batch, P.H,
+                                          P.W, 1, s);
+  if (e != hipSuccess) { set_error(std::string("op 'latent_step' failed: ") + hipGetErrorString(e)); return GDF_ERR_HIP; }
+  for (int k = 0; k < n_steps; ++k) {
+    const int rc = plan_run(P, b, s, nullptr, nullptr, nullptr, 0);
+    if (rc != GDF_OK) return rc;
+  }
   return GDF_OK;
 }
 

@@ -121,6 +121,7 @@ struct Model {
 // Flux reuses the slots: LAT = hidden_states, T = timestep, CTX = encoder_hidden_states, TXT = pooled_projections,
 // TID = guidance, NOISE = output; IDS_IMG / IDS_TXT = img_ids / txt_ids
 enum { BUF_WS = 0, BUF_WT, BUF_LAT, BUF_T, BUF_CTX, BUF_TXT, BUF_TID, BUF_NOISE, BUF_IDS_IMG, BUF_IDS_TXT, BUF_COUNT };
+enum { BUF_X32 = BUF_IDS_IMG };                 // UNet trajectory (gdf_trajectory): the caller's fp32 master latents; null on a plain forward
 enum { BUF_HOOK0 = 1 << 16 };                   // Ref.buf = BUF_HOOK0 + slot: the caller's hook buffer `slot` (an op's output IS the hook)
 struct Ref { int buf = BUF_WS; size_t off = 0; };
 struct Bind {
@@ -154,6 +155,11 @@ struct Plan {
   bool want_maps = false;
   bool writes_noise = false;
   size_t ws_bytes = 0;
+  // UNet plans without hooks and without early exit (they exist for noise_pred): byte offset of the trajectory state at the end of the workspace
+  // — the forwards' fp16 latent input (B, 4, H, W), their timestep buffer (B) and the latent_step block {step, ticket, n_rows, 0} + coefficient
+  // rows (plan_trajectory).  NPOS: the plan cannot run a trajectory.
+  size_t traj_off = NPOS;
+  std::vector<float> traj_host;               // host image of the latent_step block of the last gdf_trajectory call (source of its upload)
   std::vector<std::string> dry_ids;
   // live per-kernel timing (bench roofline): HIP events around every op of one kernel label
   std::vector<std::string> labels;
@@ -188,6 +194,9 @@ int plan_build(const Model& m, Plan& P, int batch, int H, int W, int n_ctx, cons
 int plan_forward(Plan& P, const Model& m, const void* lat, const float* t, const void* ctx, const void* txt,
                  const float* tid, void* const* hook_out, void* noise, void* ws, hipStream_t s, float* ms,
                  const char** names, double* flops, int cap);
+// n_steps x (forward + latent_step) on one stream, nothing from the host in between (include/gdf.h gdf_trajectory)
+int plan_trajectory(Plan& P, const Model& m, float* x32, int n_steps, const float* table, const void* ctx, const void* txt, const float* tid,
+                    void* noise, void* ws, hipStream_t s);
 // executes the op program against an already filled binding table (shared by the UNet and Flux front ends)
 int plan_run(Plan& P, const Bind& b, hipStream_t s, float* ms, const char** names, double* flops, int cap);
 

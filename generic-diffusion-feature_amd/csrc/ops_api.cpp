@@ -460,4 +460,10 @@ int gdf_op_attention_joint(const void* q, int ldq, const void* k, int ldk, const
   return fin(launch_attention(a, (hipStream_t)stream), "attention_joint");
 }
 
+int gdf_op_latent_step(float* latents_f32, const void* noise_pred, void* latents_f16, float* timesteps, void* steps, int B, int H, int W,
+                       int prime, void* stream) {
+  return fin(launch_latent_step(latents_f32, (const half_t*)noise_pred, (half_t*)latents_f16, timesteps, (int*)steps, B, H, W, prime,
+                                (hipStream_t)stream), "latent_step");
+}
+
 }  // extern "C"

@@ -6,7 +6,8 @@ Kept verbatim: constructor keywords (:27-40), `encode_prompt` (:149-206) 4-tuple
 `extract` signature and return contract (:222-235, :517) — dict[layer_id -> (B,C,H,W) fp16 tensor] in hook
 execution order —, `preprocess_image`, `offload_prompt_encoder`, background-extraction accessors,
 the layer-selection config surface (JSON path | dict | None) and the version / dtype strings.
-In scope is the single-timestep path (no `denoising_from`, ControlNet, DDIM inversion: SURVEY.md §2).
+In scope are the single-timestep path and, for the UNet versions, `use_ddim_inversion` (the inversion steps run as one device-resident
+trajectory, NativeUNet.trajectory); `denoising_from` and ControlNet are not.
 """
 import copy
 import os
@@ -178,9 +179,21 @@ class FeatureExtractor(nn.Module):
                 use_control=False, use_ddim_inversion=False):
         """One single-timestep denoiser forward; returns {layer_id: (B,C,H,W) fp16}.
         image_type: 'image' (list of PIL), 'tensors' ((B,3,h,w) in [-1,1]) or — native extension —
-        'latents' (pre-noised latents (B,4,H/8,W/8), skipping the VAE stage)."""
-        if denoising_from or use_control or use_ddim_inversion:
-            raise NotImplementedError("only the single-timestep path is native (SURVEY.md §2 #1)")
+        'latents' (pre-noised latents (B,4,H/8,W/8), skipping the VAE stage).
+        use_ddim_inversion (UNet versions): the latents are the image's DDIM inversion up to timestep t instead of its noised encoding
+        (reference :381-386), see _ddim_inverted_latents."""
+        if use_control:
+            raise NotImplementedError("use_control: ControlNet conditioning needs cv2, controlnet_aux and a ControlNet model class, none of which "
+                                      "the native path carries (SURVEY.md §2 #5)")
+        if denoising_from:
+            raise NotImplementedError("denoising_from is deprecated upstream and runs there only together with ControlNet (its denoising call "
+                                      "reads the ControlNet branch's raw image, reference diffusion_feature.py:394); not native")
+        if use_ddim_inversion:
+            if self.version == 'flux' or self.version.startswith('pixart'):
+                raise NotImplementedError("use_ddim_inversion exists for the UNet versions ('1-5', '2-1', 'xl', 'pgv2') only: the reference's "
+                                          "inversion loop calls pipe.unet (components/ddim_inversion.py:31)")
+            if image_type == 'latents':
+                raise ValueError("use_ddim_inversion inverts an image: image_type must be 'image' or 'tensors'")
         self.feature_store.reset()
         device = self.device
         if self.version == 'flux':                                                       # reference :246-254
@@ -250,7 +263,10 @@ class FeatureExtractor(nn.Module):
                 # (bilinear resampling at scale 1 samples exactly the pixel centres: the identity, so tensors that already have the target
                 #  size — e.g. the CLI's loader threads, which ran preprocess_image themselves — skip the launch)
                 image = F.interpolate(image, (self.img_size, self.img_size), mode='bilinear')
-            latents = self.pipe.prepare_latents(image, latent_timestep, 1, batch_size, prompt_embeds.dtype, device)
+            if use_ddim_inversion:                                                       # :381-386 (the feature store has nothing to pause:
+                latents = self._ddim_inverted_latents(image, prompts, prompt_embeds, added_cond_kwargs, t)    # the trajectory's plan has no hooks)
+            else:
+                latents = self.pipe.prepare_latents(image, latent_timestep, 1, batch_size, prompt_embeds.dtype, device)
 
         latent_model_input = self.pipe.scheduler.scale_model_input(latents, t)          # :405-406
 
@@ -298,6 +314,31 @@ class FeatureExtractor(nn.Module):
             self.feature_store.stored_feats['attn'] = aggregate_attention(maps, self.img_size // 8)
             self.pipe.unet.last_extra = {}
         return self.feature_store.stored_feats                                           # :517
+
+    def _ddim_inverted_latents(self, image, prompts, prompt_embeds, added_cond_kwargs, t):
+        """The reference's `ddim_inversion(self.pipe, image, device, prompts, 100, t)` (:385, components/ddim_inversion.py:7-45) on the native path:
+        VAE encode without noise -> fp32 latents -> the inversion steps as ONE device-resident trajectory (no fp16 rounding of the latents and no
+        host round trip between steps) -> fp32 latents, which the caller hands to scale_model_input as it does the noised ones.
+        Kept as the reference has it, odd or not: the inversion forwards see the UN-scaled latents (:28-31: no scale_model_input, whatever the
+        pipeline's scheduler is) while the extraction forward that follows applies the pipeline scheduler's scale_model_input to the result;
+        '1-5' / '2-1' scale the VAE sample by the constant 0.18215 (:15) and condition on prompts[0] (:31).
+        Native extension: the reference cannot run this for 'xl' / 'pgv2' (its UNet call passes no added_cond_kwargs, :31); here they use
+        vae.config.scaling_factor and the text_embeds / time_ids of the extraction forward."""
+        from components.models import ddim_inversion_table
+        unet, enc = self.pipe.unet, getattr(self.pipe, 'native_vae', None)
+        if enc is None or not hasattr(unet, 'trajectory'):
+            raise NotImplementedError("use_ddim_inversion needs the native VAE encoder and UNet (libgdf.so); this pipeline has neither")
+        device = self.device
+        xl = self.version in ('xl', 'pgv2')
+        image = image.to(device)
+        f = 1 << (len(enc.cfg["block_out_channels"]) - 1)
+        B, _, H, W = image.shape
+        eps = torch.randn((B, enc.cfg["latent_channels"], H // f, W // f), device=device, dtype=torch.float32)    # latent_dist.sample() (:15)
+        sf = float(self.pipe.vae.config.scaling_factor) if xl else 0.18215
+        lat = enc.encode(image, eps=eps, noise=None, noise_a=1.0, noise_b=0.0, scaling_factor=sf)
+        table = ddim_inversion_table(self.pipe.scheduler, 100, t)
+        return unet.trajectory(lat.float(), table, prompt_embeds.to(device), added_cond_kwargs.get("text_embeds"),
+                               added_cond_kwargs.get("time_ids"), shared_ctx=prompts[0].shape[0] == 1)
 
     def set_background_extraction(self, idxs):
         self.feature_store.store_idx = idxs

@@ -132,6 +132,22 @@ int gdf_forward(gdf_plan* p, const void* latents, const float* timesteps, const 
                 const void* add_text_embeds, const float* add_time_ids,
                 void* const* hook_out, void* noise_pred, void* workspace, void* stream);
 
+/* A device-resident multi-step latent trajectory: n_steps x (one forward + one scheduler update), e.g. DDIM inversion
+ * (/root/reference/feature/components/ddim_inversion.py:19-43).
+ *   p             a plan created with ZERO hooks and early_exit = 0 (the reference pauses its feature store meanwhile,
+ *                 diffusion_feature.py:384-386); its gdf_plan_workspace_bytes already includes the trajectory state
+ *   latents_f32   (B,4,H,W) fp32 NCHW, in-out: the master copy of the latents, never rounded to fp16 between steps
+ *   table         HOST pointer, n_steps rows of {timestep, c_in, c_sample, c_eps}: forward k runs at timestep[k] on fp16(c_in[k] * x_k)
+ *                 (the scheduler's scale_model_input), then  x_{k+1} = c_sample[k] * x_k + c_eps[k] * noise_pred_k  in fp32
+ *   noise_pred_scratch   (B,H,W,4) fp16, overwritten by every forward
+ * The table is uploaded once per call; every forward and every update is enqueued on `stream` with no host synchronisation and no
+ * host-to-device copy between steps.  The update kernel (csrc/dit.hip latent_step_kernel) picks its row with a device-side step counter, so
+ * all steps are the same launches with the same arguments: with graph replay enabled (below) the steps of a call replay ONE graph of
+ * forward ops + update, built with the graph API like any other. */
+#define GDF_TRAJECTORY_MAX_STEPS 1024
+int gdf_trajectory(gdf_plan* p, float* latents_f32, int n_steps, const float* table, const void* ctx,
+                   const void* add_text_embeds, const float* add_time_ids, void* noise_pred_scratch, void* workspace, void* stream);
+
 /* hipGraph replay: with enable != 0 every forward on a NON-default stream is served by one hipGraphLaunch of the plan's op
  * program, recorded once per distinct set of buffer addresses (workspace, inputs, hooks, outputs; LRU of 12) after one eager
  * warm-up forward.  The graph is BUILT with the graph API (kernel nodes in launch order, csrc/launch.h) — no stream is ever put into

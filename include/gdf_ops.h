@@ -279,6 +279,21 @@ int gdf_op_rope_table(const float* ids, int S, int a0, int a1, int a2, float* co
 int gdf_op_attention_joint(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int B,
                            int heads, int T, int S, int D, void* stream);
 
+/* One launch of latent_step_kernel: the scheduler update between two forwards of a latent trajectory (gdf_trajectory, gdf.h).
+ *   latents_f32  (B, 4, H, W) fp32 NCHW master, updated in place:  x' = c_sample * x + c_eps * eps
+ *   noise_pred   (B, H, W, 4) fp16 channels-last (what gdf_forward writes); read only
+ *   latents_f16  (B, 4, H, W) fp16 NCHW out:  c_in[next] * x'   (the scheduler's scale_model_input for the next forward)
+ *   timesteps    (B) fp32 out: the next row's timestep in every slot
+ *   steps        device block  int32 {step, ticket, n_rows, 0}  followed by  float rows[n_rows][4] = {timestep, c_in, c_sample, c_eps};
+ *                ticket must be 0 before the first launch.  The launch uses row `step` for the update and row min(step + 1, n_rows - 1)
+ *                ("next") for c_in and the timestep, then stores step + 1: consecutive steps are the same launch with the same arguments.
+ *                A step outside [0, n_rows) writes nothing.
+ *   prime = 1    no update: eps is not read and the master is not written; row 0 is "next" and step becomes 0 (the launch in front of the
+ *                first forward).
+ * Replaces the latent update of /root/reference/feature/components/ddim_inversion.py:39-41. */
+int gdf_op_latent_step(float* latents_f32, const void* noise_pred, void* latents_f16, float* timesteps, void* steps, int B, int H, int W,
+                       int prime, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
