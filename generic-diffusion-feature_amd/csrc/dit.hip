@@ -153,20 +153,30 @@ __global__ __launch_bounds__(256) void layernorm_mod_kernel(const half_t* x16, c
   }
 }
 
+// registers chunks (8 columns per lane each) of the instantiation that holds a row of C columns; 0: no instantiation (C % 8, C > 4096)
+int layernorm_mod_maxc(int C) {
+  if (C <= 0 || C % 8 || C > 64 * 8 * 8) return 0;
+  const int CH = C / 8;
+  return CH <= 64 ? 1 : CH <= 128 ? 2 : CH <= 256 ? 4 : CH <= 384 ? 6 : 8;
+}
+
 hipError_t launch_layernorm_mod(const half_t* x16, const float* x32, int ld, int R, int C, float eps, const float* scale,
                                 const float* shift, int ldm, int rps, int seg_rows, int rps2, half_t* y, hipStream_t s,
                                 int bf16, int ldy, int y_lo, unsigned char* q8, int ldq8, float* q8_scale) {
-  if (C % 8 || C > 64 * 8 * 8 || (ldm & 3) || rps <= 0 || (y_lo & 7) || (ldy & 7) || (q8 && ((ldq8 & 7) || !q8_scale))) return hipErrorInvalidValue;
+  const int maxc = layernorm_mod_maxc(C);
+  if (!maxc || (ldm & 3) || rps <= 0 || (y_lo & 7) || (ldy & 7) || (q8 && ((ldq8 & 7) || !q8_scale))) return hipErrorInvalidValue;
+  if (!x16 == !x32 || (x32 ? (ld & 3) : (ld & 7))) return hipErrorInvalidValue;   // one source; its rows stay aligned for the 16-byte loads
   if (ldy <= 0) ldy = C;
   if (R <= 0) return hipSuccess;
-  const int CH = C / 8;
   dim3 grid((R + 3) / 4), blk(256);
 #define GDF_LNM(N) hipLaunchKernelGGL(layernorm_mod_kernel<N>, grid, blk, 0, s, x16, x32, ld, R, C, eps, scale, shift, ldm, rps, seg_rows, rps2, y, bf16, ldy, y_lo, q8, ldq8, q8_scale)
-  if (CH <= 64) GDF_LNM(1);
-  else if (CH <= 128) GDF_LNM(2);
-  else if (CH <= 256) GDF_LNM(4);
-  else if (CH <= 384) GDF_LNM(6);
-  else GDF_LNM(8);
+  switch (maxc) {
+    case 1: GDF_LNM(1); break;
+    case 2: GDF_LNM(2); break;
+    case 4: GDF_LNM(4); break;
+    case 6: GDF_LNM(6); break;
+    default: GDF_LNM(8); break;
+  }
 #undef GDF_LNM
   return hipGetLastError();
 }

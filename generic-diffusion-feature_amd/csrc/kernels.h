@@ -228,9 +228,13 @@ hipError_t launch_layernorm(const half_t* x16, const float* x32, int ld, int R, 
 // the MMDiT blocks): y = LN(x, eps) * (1 + scale[s][c]) + shift[s][c]; s = row / rps for row < seg_rows (or
 // seg_rows == 0), else (row - seg_rows) / rps2.  x fp32 (or fp16) [R][ld], y fp16 [R][C], scale/shift fp32 rows of ldm.
 // y_lo > 0: y is written as a split pair (rows of ldy elements, hi at column 0, lo = e16(v - hi) at column y_lo)
+// Exactly one of x16 / x32 is set.  x16 is ALWAYS fp16 (the kernel reads it with a plain cast whatever `bf16` says; `bf16` is the type of y
+// only); no plan passes x16.  ld % 4 == 0 for x32, ld % 8 == 0 for x16 (16-byte loads).
 hipError_t launch_layernorm_mod(const half_t* x16, const float* x32, int ld, int R, int C, float eps, const float* scale,
                                 const float* shift, int ldm, int rps, int seg_rows, int rps2, half_t* y, hipStream_t s,
                                 int bf16 = 0, int ldy = 0, int y_lo = 0, unsigned char* q8 = nullptr, int ldq8 = 0, float* q8_scale = nullptr);
+// MAXC of the layernorm_mod_kernel<MAXC> that launch_layernorm_mod instantiates for C columns (1, 2, 4, 6, 8), or 0 where it rejects C
+int layernorm_mod_maxc(int C);
 // 'fp8-mx' plans: 16-bit rows [R][ld] (K columns) -> fp8 e4m3 [R][ldq] with one power-of-two scale per row (q = fp8(v / scale[r])).
 // launch_layernorm_mod's q8 / q8_scale write the same form of its own output in the same pass.
 hipError_t launch_quant_rows_fp8(const half_t* x, int ld, int R, int K, int bf16, unsigned char* q, int ldq, float* scale, hipStream_t s);

@@ -440,6 +440,15 @@ int gdf_op_layernorm_mod(const float* x32, int ld, int R, int C, float eps, cons
                                   g_e16_bf), "layernorm_mod");
 }
 
+int gdf_op_layernorm_mod_ex(const void* x16, const float* x32, int ld, int R, int C, float eps, const float* scale, const float* shift,
+                            int ldm, int rps, int seg_rows, int rps2, void* y, int bf16, int ldy, int y_lo, void* q8, int ldq8,
+                            float* q8_scale, void* stream) {
+  return fin(launch_layernorm_mod((const half_t*)x16, x32, ld, R, C, eps, scale, shift, ldm, rps, seg_rows, rps2, (half_t*)y,
+                                  (hipStream_t)stream, bf16, ldy, y_lo, (unsigned char*)q8, ldq8, q8_scale), "layernorm_mod_ex");
+}
+
+int gdf_op_layernorm_mod_path(int C) { return layernorm_mod_maxc(C); }
+
 int gdf_op_qk_norm_rope(void* x, int ld, int R, int heads, int q_col, int k_col, const float* wq, const float* wk, float eps,
                         const float* cos_t, const float* sin_t, int pos0, int rps, void* stream) {
   return fin(launch_qk_norm_rope((half_t*)x, ld, R, heads, 128, q_col, k_col, wq, wk, eps, cos_t, sin_t, pos0, rps, (hipStream_t)stream,

@@ -268,6 +268,17 @@ int gdf_op_gemm_dit(const void* A, int lda, const void* W, const float* bias, in
 int gdf_op_layernorm_mod(const float* x32, int ld, int R, int C, float eps, const float* scale, const float* shift, int ldm,
                          int rps, int seg_rows, int rps2, void* y, void* stream);
 
+/* The same kernel with every argument of its launcher (test surface): exactly one of x16 (fp16, whatever `bf16` says) / x32 is the source,
+ * rows of ld elements (ld % 8 == 0 / ld % 4 == 0); y fp16 (bf16 = 0) or bf16 rows of ldy elements (0: C); y_lo > 0: y is a split pair, hi at
+ * column 0 and lo = e16(v - hi) at column y_lo ('bfloat16x2' plans); q8 != NULL: the same row also as OCP e4m3 bytes, rows of ldq8, with one
+ * power-of-two scale per row in q8_scale, both made from the fp32 values ('fp8-mx' plans, see gdf_op_quant_rows_fp8). */
+int gdf_op_layernorm_mod_ex(const void* x16, const float* x32, int ld, int R, int C, float eps, const float* scale, const float* shift,
+                            int ldm, int rps, int seg_rows, int rps2, void* y, int bf16, int ldy, int y_lo, void* q8, int ldq8,
+                            float* q8_scale, void* stream);
+/* Host arithmetic only: the MAXC of the layernorm_mod_kernel<MAXC> (8 * 64 * MAXC columns in registers) the launcher instantiates for C
+ * columns: 1, 2, 4, 6 or 8; 0 where it rejects C (C % 8 != 0, C > 4096). */
+int gdf_op_layernorm_mod_path(int C);
+
 /* In place RMSNorm(q), RMSNorm(k) per head (D = 128) + rotary embedding on fp16 rows [R][ld]; position = pos0 + r % rps. */
 int gdf_op_qk_norm_rope(void* x, int ld, int R, int heads, int q_col, int k_col, const float* wq, const float* wk, float eps,
                         const float* cos_t, const float* sin_t, int pos0, int rps, void* stream);
