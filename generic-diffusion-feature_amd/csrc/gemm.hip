@@ -28,7 +28,8 @@
 //
 // Source layout (round 6): gemm_common.h (types, LDS-DMA, MFMA wrappers, GELU, tile order), gemm_tile.h (GemmTile: tile geometry, tile origin,
 // operand address generators), gemm_mainloop_ring.h (2- / 3-stage LDS rings), gemm_mainloop_8phase.h (the two-group 256x256 / 256x320 loops),
-// gemm_epilogue.h (the staged epilogue), this file (gemm_body = locate -> main loop -> epilogue, kernel instantiations, pick_variant, launch_gemm).
+// gemm_epilogue.h (the staged epilogue), this file (gemm_body = locate -> main loop -> epilogue, the kernel wrappers, dispatch: gemm_select -> GemmSel
+// descriptor -> instantiation table -> launch_gemm / gemm_kernel_name, split-K).
 #include "gemm_mainloop_ring.h"
 #include "gemm_mainloop_8phase.h"
 #include "gemm_epilogue.h"
@@ -127,23 +128,24 @@ static int persist_wgs() {
   return n;
 }
 
-template <int MODE, int BM, int BN, int STAGES, bool GEGLU, bool DIT = false, bool BF = false, bool QKN = false, bool SPLIT = false, bool MX = false,
-          bool GNS = false>
+// the __global__ wrapper that runs gemm_body with these template arguments: the one map from an instantiation to its kernel symbol
+template <int MODE, int BM, int BN, int STAGES, bool GEGLU, bool DIT, bool BF, bool QKN, bool SPLIT, bool MX, bool GNS>
+static constexpr auto gemm_wrapper() -> void (*)(const GemmParams) {
+  if constexpr (MX) return gemm_mx_kernel<BM, BN, STAGES>;
+  else if constexpr (GNS) return gemm_gn_kernel<MODE, BM, BN, STAGES>;
+  else if constexpr (DIT && SPLIT) return gemm_dit_split_kernel<BM, BN, STAGES, BF, QKN>;
+  else if constexpr (DIT) return gemm_dit_kernel<BM, BN, STAGES, BF, QKN>;
+  else if constexpr (SPLIT) return gemm_split_kernel<MODE, BM, BN, STAGES, GEGLU>;
+  else return gemm_kernel<MODE, BM, BN, STAGES, GEGLU>;
+}
+
+template <int MODE, int BM, int BN, int STAGES, bool GEGLU, bool DIT, bool BF, bool QKN, bool SPLIT, bool MX, bool GNS>
 static hipError_t launch_t(const GemmParams& p, hipStream_t s) {
   const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
   const int smem = (STAGES >= 8 ? 2 : STAGES) * (BM * 128 + BN * 128);
+  constexpr auto fn = gemm_wrapper<MODE, BM, BN, STAGES, GEGLU, DIT, BF, QKN, SPLIT, MX, GNS>();
   static std::atomic<uint64_t> attr_mask{0};             // per template instantiation, one bit per device
-  {
-    const void* fn;
-    if constexpr (MX) fn = (const void*)gemm_mx_kernel<BM, BN, STAGES>;
-    else if constexpr (GNS) fn = (const void*)gemm_gn_kernel<MODE, BM, BN, STAGES>;
-    else if constexpr (DIT && SPLIT) fn = (const void*)gemm_dit_split_kernel<BM, BN, STAGES, BF, QKN>;
-    else if constexpr (DIT) fn = (const void*)gemm_dit_kernel<BM, BN, STAGES, BF, QKN>;
-    else if constexpr (SPLIT) fn = (const void*)gemm_split_kernel<MODE, BM, BN, STAGES, GEGLU>;
-    else fn = (const void*)gemm_kernel<MODE, BM, BN, STAGES, GEGLU>;
-    const hipError_t e = ensure_dyn_smem(attr_mask, fn, smem);
-    if (e != hipSuccess) return e;
-  }
+  if (const hipError_t e = ensure_dyn_smem(attr_mask, (const void*)fn, smem); e != hipSuccess) return e;
   GemmParams q = p;
   q.sb_gm = q.sb_gn = 0;
   if (!p.no_superblock) {
@@ -160,15 +162,101 @@ static hipError_t launch_t(const GemmParams& p, hipStream_t s) {
   const int pw = (p.cus > 0 && p.cus < persist_wgs()) ? p.cus : persist_wgs();
   if (STAGES == 8 && gx > pw && !(p.batch > 1)) gx = pw;   // persistent: one workgroup per CU walks the tiles
   const dim3 grid(gx, (STAGES == 2 && p.splitk > 1) ? p.splitk : p.batch > 1 ? p.batch : 1);
-  if constexpr (MX) hipLaunchKernelGGL((gemm_mx_kernel<BM, BN, STAGES>), grid, dim3(BM * 2), smem, s, q);
-  else if constexpr (GNS) hipLaunchKernelGGL((gemm_gn_kernel<MODE, BM, BN, STAGES>), grid, dim3(BM * 2), smem, s, q);
-  else if constexpr (DIT && SPLIT) hipLaunchKernelGGL((gemm_dit_split_kernel<BM, BN, STAGES, BF, QKN>), grid, dim3(BM * 2), smem, s, q);
-  else if constexpr (DIT) hipLaunchKernelGGL((gemm_dit_kernel<BM, BN, STAGES, BF, QKN>), grid, dim3(BM * 2), smem, s, q);
-  else if constexpr (SPLIT) hipLaunchKernelGGL((gemm_split_kernel<MODE, BM, BN, STAGES, GEGLU>), grid, dim3(BM * 2), smem, s, q);
-  else hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, STAGES, GEGLU>), grid, dim3(BM * 2), smem, s, q);
+  hipLaunchKernelGGL(fn, grid, dim3(BM * 2), smem, s, q);
   return hipGetLastError();
 }
 
+// ---- dispatch: select (host arithmetic only, no device call) -> descriptor -> instantiation table -> launch / name ----
+// The descriptor (GemmSel, kernels.h) spells one instantiation: the template arguments of gemm_body.  launch_gemm() launches the table
+// entry the descriptor names and gemm_kernel_name() prints the same descriptor, so what a test or a profile reads is what runs.
+// a table entry: key, launcher, rows of a wave tile (the GroupNorm statistics slab of the GNS forms), all from the same template arguments
+struct GemmInst { GemmSel k; hipError_t (*launch)(const GemmParams&, hipStream_t); int wtm; };
+template <int MODE, int BM, int BN, int STAGES, bool GEGLU = false, bool DIT = false, bool BF = false, bool QKN = false, bool SPLIT = false,
+          bool MX = false, bool GNS = false>
+static constexpr GemmInst inst() {
+  return {{true, MODE, BM, BN, STAGES, GEGLU, DIT, BF, QKN, SPLIT, MX, GNS, false}, launch_t<MODE, BM, BN, STAGES, GEGLU, DIT, BF, QKN, SPLIT, MX, GNS>,
+          GemmTile<MODE, BM, BN, STAGES, GEGLU, DIT, BF, QKN, SPLIT, MX, GNS>::WTM};
+}
+// every instantiation of the library; a descriptor none of them matches is an error, never another kernel
+static const GemmInst kGemmInst[] = {
+    inst<A_DENSE, 128, 16, 2>(),                             // gemm_kernel: dense
+    inst<A_DENSE, 128, 128, 2>(),
+    inst<A_DENSE, 128, 160, 2>(),
+    inst<A_DENSE, 256, 128, 3>(),
+    inst<A_DENSE, 256, 320, 2>(),
+    inst<A_DENSE, 256, 320, 9>(),
+    inst<A_DENSE, 128, 128, 2, true>(),                      // GEGLU: weight rows / bias interleaved [16 h | 16 gate] (launch_relayout_rows geglu = 16)
+    inst<A_DENSE, 256, 128, 3, true>(),
+    inst<A_DENSE, 256, 320, 2, true>(),
+    inst<A_DENSE, 256, 256, 8, true>(),
+    inst<A_CONV3, 128, 16, 2>(),                             // 3x3 conv (128x16: conv_out)
+    inst<A_CONV3, 128, 128, 2>(),
+    inst<A_CONV3, 128, 160, 2>(),
+    inst<A_CONV3, 256, 128, 3>(),
+    inst<A_CONV3, 256, 320, 2>(),
+    inst<A_CONV3, 256, 256, 8>(),
+    inst<A_CONV3, 256, 320, 9>(),
+    inst<A_CONV_SMALLC, 128, 128, 2>(),                      // conv_in
+    inst<A_CONV_SMALLC, 128, 160, 2>(),
+    inst<A_DENSE, 128, 128, 2, false, false, false, false, true>(),  // gemm_split_kernel ("precise" plans), a reduced set of tiles: dense / conv 256x320 two-group, 128x160, 128x128
+    inst<A_DENSE, 128, 160, 2, false, false, false, false, true>(),
+    inst<A_DENSE, 256, 320, 9, false, false, false, false, true>(),
+    inst<A_DENSE, 128, 128, 2, true, false, false, false, true>(),   // (GEGLU: 256x256 two-group and 128x128)
+    inst<A_DENSE, 256, 256, 8, true, false, false, false, true>(),
+    inst<A_CONV3, 128, 16, 2, false, false, false, false, true>(),   // (the narrow-N tile: conv_out)
+    inst<A_CONV3, 128, 128, 2, false, false, false, false, true>(),
+    inst<A_CONV3, 128, 160, 2, false, false, false, false, true>(),
+    inst<A_CONV3, 256, 320, 9, false, false, false, false, true>(),
+    inst<A_CONV_SMALLC, 128, 128, 2, false, false, false, false, true>(),
+    inst<A_CONV_SMALLC, 128, 160, 2, false, false, false, false, true>(),
+    inst<A_DENSE, 128, 128, 2, false, true>(),               // gemm_dit_kernel: fp16, then bf16; QKN on the 256x256 tile only
+    inst<A_DENSE, 256, 128, 3, false, true>(),
+    inst<A_DENSE, 256, 256, 2, false, true>(),
+    inst<A_DENSE, 256, 256, 2, false, true, false, true>(),
+    inst<A_DENSE, 256, 256, 8, false, true>(),
+    inst<A_DENSE, 256, 256, 8, false, true, false, true>(),
+    inst<A_DENSE, 128, 128, 2, false, true, true>(),
+    inst<A_DENSE, 256, 128, 3, false, true, true>(),
+    inst<A_DENSE, 256, 256, 2, false, true, true>(),
+    inst<A_DENSE, 256, 256, 2, false, true, true, true>(),
+    inst<A_DENSE, 256, 256, 8, false, true, true>(),
+    inst<A_DENSE, 256, 256, 8, false, true, true, true>(),
+    inst<A_DENSE, 128, 128, 2, false, true, true, false, true>(),    // gemm_dit_split_kernel: bf16 hi + lo operands ('bfloat16x2' plans)
+    inst<A_DENSE, 256, 256, 8, false, true, true, false, true>(),
+    inst<A_DENSE, 256, 256, 8, false, true, true, true, true>(),
+    inst<A_DENSE, 256, 256, 8, false, true, true, false, false, true>(),   // gemm_mx_kernel: fp8 (e4m3) operands ('fp8-mx' plans), the 256x256 two-group tile only
+    inst<A_CONV3, 128, 128, 2, false, false, false, false, false, false, true>(),   // gemm_gn_kernel: GroupNorm partial sums from the epilogue of a plain 3x3 conv / conv_in
+    inst<A_CONV3, 128, 160, 2, false, false, false, false, false, false, true>(),
+    inst<A_CONV3, 256, 128, 3, false, false, false, false, false, false, true>(),
+    inst<A_CONV3, 256, 256, 8, false, false, false, false, false, false, true>(),
+    inst<A_CONV3, 256, 320, 9, false, false, false, false, false, false, true>(),
+    inst<A_CONV_SMALLC, 128, 128, 2, false, false, false, false, false, false, true>(),
+};
+
+static const GemmInst* find_inst(const GemmSel& k) {
+  for (const GemmInst& e : kGemmInst)
+    if (e.k.MODE == k.MODE && e.k.BM == k.BM && e.k.BN == k.BN && e.k.STAGES == k.STAGES && e.k.GEGLU == k.GEGLU && e.k.DIT == k.DIT &&
+        e.k.BF == k.BF && e.k.QKN == k.QKN && e.k.SPLIT == k.SPLIT && e.k.MX == k.MX && e.k.GNS == k.GNS) return &e;
+  return nullptr;
+}
+struct Tile { int bm, bn, st; };                       // BM, BN, STAGES
+static constexpr Tile T128x16{128, 16, 2}, T128x128{128, 128, 2}, T128x160{128, 160, 2}, T256x128{256, 128, 3}, T256x320R{256, 320, 2},
+    T256x256R{256, 256, 2}, T256x256{256, 256, 8}, T256x320{256, 320, 9}, NO_TILE{0, 0, 0};
+static bool operator==(const Tile& a, const Tile& b) { return a.bm == b.bm && a.bn == b.bn && a.st == b.st; }
+
+// The public `variant` codes (include/gdf_ops.h), decoded here and nowhere else.  UNet / VAE forms: false = not a code, which means the
+// 128x128 tile.  825 / 826 are the 256x256 two-group tile of the GEGLU / of the conv form; on the other form they name no tile it has.
+static bool unet_tile(int code, bool geglu, Tile& t) {
+  t = code == 16 ? T128x16 : code == 160 ? T128x160 : code == 256 ? T256x128 : code == 320 ? T256x320R : code == 932 ? T256x320
+      : code == 825 ? (geglu ? T256x256 : NO_TILE) : code == 826 ? (geglu ? NO_TILE : T256x256) : T128x128;
+  return code == 128 || !(t == T128x128);
+}
+// MMDiT forms: false = not one of their four codes, which means the automatic choice
+static bool dit_tile(int code, Tile& t) {
+  if (code != 128 && code != 1256 && code != 2128 && code != 8256) return false;
+  t = code == 128 ? T128x128 : code == 1256 ? T256x256R : code == 2128 ? T256x128 : T256x256;
+  return true;
+}
 // Tile selection.  Every channel count of the SD / SDXL UNets is a multiple of 160 (320 k), so the 128x160 tile
 // (2 workgroups per CU, 72 KiB LDS each) covers N without a ragged last column tile and makes M/128 * N/160 a
 // multiple of the 512 workgroup slots for the SDXL batch-16 shapes (no tail round).  128x128 serves other N;
@@ -179,64 +267,48 @@ static double round_fill(long tiles, int slots) {
   const long rounds = (tiles + slots - 1) / slots;
   return (double)tiles / (double)(rounds * slots);
 }
-
-static int pick_variant_any(const GemmParams& p);
-// split-operand launches ("precise" plans) are instantiated for a reduced set of tiles: dense / conv 256x320 two-group, 128x160,
-// 128x128; GEGLU 256x256 two-group and 128x128; the narrow-N tile
-static bool is_split(const GemmParams& p) { return !p.dit && (p.k_w > 0 || p.o16_lo > 0); }
-static bool is_dit_split(const GemmParams& p) { return p.dit && (p.k_w > 0 || p.o16_lo > 0); }
-static int pick_variant(const GemmParams& p) {
-  const int v = pick_variant_any(p);
-  if (is_dit_split(p)) return (v == 8256 || v == 1256) ? 8256 : 128;      // 'bfloat16x2' MMDiT plans: 256x256 two-group or 128x128
-  if (!is_split(p) || v == 16) return v;
-  if (p.geglu) return v == 825 ? 825 : 128;
-  if (p.mode == A_CONV_SMALLC) return v == 160 ? 160 : 128;
-  return (v == 932 || v == 160) ? v : 128;
+static Tile splitk_tile(int N) {                       // split-K lives in the 2-stage ring tiles
+  static const int force = [] { const char* e = getenv("GDF_SPLITK_TILE"); return e ? atoi(e) : 0; }();   // diagnostics: 128 | 160
+  if (force == 160 && N % 160 == 0) return T128x160;
+  if (force == 128 && N % 128 == 0) return T128x128;
+  // round 5: the 128x160 tile whenever it divides N (SD1.5's 8x8 level, N = 1280: 750 / 891 vs 715 / 824 TFLOP/s at K = 11520 / 23040,
+  // tools/bench_conv_small_m.py)
+  return (N % 160 == 0) ? T128x160 : T128x128;
 }
-static int pick_variant_any(const GemmParams& p) {
+static Tile dit_auto_tile(const GemmParams& p) {   // MMDiT widths are multiples of 256 (3072 = 24 x 128): 256x256 tiles (128 KiB ring, 1 workgroup / CU)
+  const long t256 = (long)((p.M + 255) / 256) * ((p.N + 255) / 256);
+  // 8-phase schedule: 1177-1362 vs 1002-1188 TFLOP/s (2-stage ring) at the Flux shapes.  A ragged last column tile is fine up to
+  // 1/8 of padding (PixArt C = 1152 = 4.5 x 256: 1017-1187 vs 873-1020 on the 256x128 ring)
+  if (t256 >= 128 && (long)((p.N + 255) / 256) * 256 <= (long)p.N + p.N / 8) return T256x256;
+  return (p.N % 128 == 0 && (long)((p.M + 255) / 256) * (p.N / 128) >= 256) ? T256x128 : T128x128;   // PixArt: C = 1152 = 9 x 128
+}
+
+static Tile unet_auto_tile(const GemmParams& p) {
   const int S1 = p.cus > 0 ? p.cus : 256, S2 = 2 * S1;   // workgroup slots at 1 / 2 workgroups per CU (whole chip or a CU partition)
-  if (p.dit) {   // MMDiT widths are multiples of 256 (3072 = 24 x 128): 256x256 tiles (128 KiB ring, 1 workgroup / CU)
-    const long t256 = (long)((p.M + 255) / 256) * ((p.N + 255) / 256);
-    if (p.variant == 128 || p.variant == 1256 || p.variant == 2128 || p.variant == 8256) return p.variant;
-    // 8-phase schedule: 1177-1362 vs 1002-1188 TFLOP/s (2-stage ring) at the Flux shapes.  A ragged last column tile is fine up to
-    // 1/8 of padding (PixArt C = 1152 = 4.5 x 256: 1017-1187 vs 873-1020 on the 256x128 ring)
-    if (t256 >= 128 && (long)((p.N + 255) / 256) * 256 <= (long)p.N + p.N / 8) return 8256;
-    return (p.N % 128 == 0 && (long)((p.M + 255) / 256) * (p.N / 128) >= 256) ? 2128 : 128;   // PixArt: C = 1152 = 9 x 128
-  }
-  if (p.bn == 16) return 16;
-  if (p.splitk > 1) {                                                            // split-K lives in the 2-stage ring tiles
-    static const int force = [] { const char* e = getenv("GDF_SPLITK_TILE"); return e ? atoi(e) : 0; }();   // diagnostics: 128 | 160
-    if (force == 160 && p.N % 160 == 0) return 160;
-    if (force == 128 && p.N % 128 == 0) return 128;
-    // round 5: the 128x160 tile whenever it divides N (SD1.5's 8x8 level, N = 1280: 750 / 891 vs 715 / 824 TFLOP/s at K = 11520 / 23040,
-    // tools/bench_conv_small_m.py); gemm_splitk_factor counts its tiles the same way
-    return (p.N % 160 == 0) ? 160 : 128;
-  }
-  if (p.variant) return p.variant;
-  const long tiles256 = (long)((p.M + 255) / 256) * ((p.N + 127) / 128);
   const long tiles320 = (long)((p.M + 255) / 256) * ((p.N + 319) / 320);
+  auto rank320 = [&](double r160, double r128) {         // N % 320 == 0: 256x320 two-group against the two small tiles, rate x fill of the rounds
+    const double s320 = 1.00 * round_fill(tiles320, S1), s160 = r160 * round_fill((long)((p.M + 127) / 128) * (p.N / 160), S2);
+    const double s128 = r128 * round_fill((long)((p.M + 127) / 128) * ((p.N + 127) / 128), S2);
+    return (s320 >= s160 && s320 >= s128) ? T256x320 : (s160 >= s128 ? T128x160 : T128x128);
+  };
   if (p.geglu) {
     // 8-phase 256x256: 1130 vs 1073 TFLOP/s (256x320 ring) at 16384 x 10240 x 1280, 899 vs 869 at 65536 x 5120 x 640
     // The batch-16 shapes fill whole rounds of every tile; other batch sizes may leave a mostly idle last round, so the
     // candidates are ranked by (measured rate at full rounds) x (fill of the rounds they need)
     const long tm256 = (p.M + 255) / 256, tm128 = (p.M + 127) / 128;
-    double best = 0.0; int bv = 128;
-    auto cand = [&](int v, double rate, long tiles, int slots) { const double sc = rate * round_fill(tiles, slots); if (sc > best) { best = sc; bv = v; } };
-    if (p.N % 256 == 0) cand(825, 1.00, tm256 * (p.N / 256), S1);
-    if (p.N % 320 == 0) cand(320, 0.95, tm256 * (p.N / 320), S1);
-    cand(256, 0.80, tm256 * ((p.N + 127) / 128), S1);
-    cand(128, 0.70, tm128 * ((p.N + 127) / 128), S2);
-    return bv;
+    double best = 0.0; Tile bt = T128x128;
+    auto cand = [&](Tile t, double rate, long tiles, int slots) { const double sc = rate * round_fill(tiles, slots); if (sc > best) { best = sc; bt = t; } };
+    if (p.N % 256 == 0) cand(T256x256, 1.00, tm256 * (p.N / 256), S1);
+    if (p.N % 320 == 0) cand(T256x320R, 0.95, tm256 * (p.N / 320), S1);
+    cand(T256x128, 0.80, tm256 * ((p.N + 127) / 128), S1);
+    cand(T128x128, 0.70, tm128 * ((p.N + 127) / 128), S2);
+    return bt;
   }
   if (p.mode != A_DENSE) {                                                 // convs (K = 9 Cin is long)
-    if (p.N % 320 == 0) {                                                  // 8-phase 256x320: 1150-1350 TFLOP/s (ring 1090-1310, 128x160 950-1140)
-      const double s932 = 1.00 * round_fill(tiles320, S1), s160 = 0.85 * round_fill((long)((p.M + 127) / 128) * (p.N / 160), S2);
-      const double s128 = 0.70 * round_fill((long)((p.M + 127) / 128) * ((p.N + 127) / 128), S2);
-      return (s932 >= s160 && s932 >= s128) ? 932 : (s160 >= s128 ? 160 : 128);
-    }
-    if (p.N % 160 == 0) return 160;
-    if (p.N % 256 == 0 && (long)((p.M + 255) / 256) * (p.N / 256) >= 256) return 826;   // VAE widths 256 / 512: 989-1146 vs 830-965 (256x128 ring)
-    return (p.N <= 128 && p.M >= (1 << 20)) ? 256 : 128;                   // VAE level-0 convs (N = 128, 4 M pixels): 797 vs 697
+    if (p.N % 320 == 0) return rank320(0.85, 0.70);                        // 8-phase 256x320: 1150-1350 TFLOP/s (ring 1090-1310, 128x160 950-1140)
+    if (p.N % 160 == 0) return T128x160;
+    if (p.N % 256 == 0 && (long)((p.M + 255) / 256) * (p.N / 256) >= 256) return T256x256;   // VAE widths 256 / 512: 989-1146 vs 830-965 (256x128 ring)
+    return (p.N <= 128 && p.M >= (1 << 20)) ? T256x128 : T128x128;         // VAE level-0 convs (N = 128, 4 M pixels): 797 vs 697
   }
   // short-K GEMMs with the fp32 residual epilogue (attention out-projections: 10 B/element of epilogue traffic against
   // 20 K-tiles of MFMA work) fill the chip in ONE round of 256x320 tiles, so main loop and epilogue traffic never overlap;
@@ -245,36 +317,81 @@ static int pick_variant_any(const GemmParams& p) {
   // 64.7 vs 77.7 us, 32768 x 640 x 640 47.0 vs 49.8, 65536 x 640 x 640 equal; it still loses at half-filled rounds, 8192 x 1280 x 1280
   // 47.3 vs 37.3, and at N = 320, tools/bench_res32.py)
   if (p.res32 && p.K <= 1536 && p.N % 160 == 0 && tiles320 <= S2 &&
-      !(p.N % 320 == 0 && p.N >= 640 && p.K >= 640 && tiles320 % S1 == 0)) return 160;
-  if (p.N % 320 == 0) {                                                    // 8-phase: qkv 1113, ff_out 1088, attn2_q 1045, shortcut 1086 (ring: 1051 / 983 / 980 / 1002)
-    const double s932 = 1.00 * round_fill(tiles320, S1), s160 = 0.87 * round_fill((long)((p.M + 127) / 128) * (p.N / 160), S2);
-    const double s128 = 0.72 * round_fill((long)((p.M + 127) / 128) * ((p.N + 127) / 128), S2);
-    return (s932 >= s160 && s932 >= s128) ? 932 : (s160 >= s128 ? 160 : 128);
+      !(p.N % 320 == 0 && p.N >= 640 && p.K >= 640 && tiles320 % S1 == 0)) return T128x160;
+  if (p.N % 320 == 0) return rank320(0.87, 0.72);                          // 8-phase: qkv 1113, ff_out 1088, attn2_q 1045, shortcut 1086 (ring: 1051 / 983 / 980 / 1002)
+  if (p.N % 160 == 0 && p.K >= 1024) return T128x160;
+  if ((long)p.M * p.N >= (1L << 26) && (long)((p.M + 255) / 256) * ((p.N + 127) / 128) >= S2) return T256x128;    // short-K, large MxN (qkv @ C=640): 712 vs 642
+  return T128x128;
+}
+
+// every reason launch_gemm refuses a launch and every tile it chooses: the queries answer "none" exactly where the launch returns an error
+GemmSel gemm_select(const GemmParams& p) {
+  GemmSel k{};                                                                              // ok = false
+  if ((p.mode != A_CONV_SMALLC && (p.K % BK) != 0) || (p.mode == A_CONV3 && (p.Cin % BK) != 0)) return k;
+  if (p.k_w > 0 && (p.K != 2 * p.k_w || (p.k_w % BK) != 0 || p.mode == A_CONV_SMALLC || (p.dit && !p.bf16) || (p.mode == A_CONV3 && (p.k_w % (9 * BK)) != 0)))
+    return k;                                                                               // split operands: K = [hi | lo] over one weight matrix
+  if (p.o16_lo > 0 && ((p.dit && !p.bf16) || p.bn == 16 || (p.o16_lo % 8) != 0)) return k;   // (MMDiT: the bf16 pair form only)
+  if ((p.out_f16 && !(p.dit && p.bf16)) || (p.bf16 && !p.dit)) return k;                    // bf16 exists on the MMDiT path only
+  // split hi + lo operands or outputs ("precise" UNet plans, 'bfloat16x2' MMDiT plans): their own instantiations
+  const bool split = p.k_w > 0 || p.o16_lo > 0;
+  Tile t; bool forced = false, known = true;                                                // (the tile is GemmParams::variant's; that was a code)
+  if (p.dit) {
+    if (p.mx) t = T256x256;                                                                 // fp8 operands: the one tile
+    else if (!dit_tile(p.variant, t)) t = dit_auto_tile(p);
+    if (split) t = (t.bm == 256 && t.bn == 256) ? T256x256 : T128x128;                      // 'bfloat16x2' plans: 256x256 two-group or 128x128
+  } else if (p.bn == 16) t = T128x16;
+  else if (p.splitk > 1) t = splitk_tile(p.N);
+  else if (p.variant) { known = unet_tile(p.variant, p.geglu != 0, t); forced = true; }
+  else t = unet_auto_tile(p);
+  if (t.bn != 16 && ((p.geglu ? p.N / 2 : p.N) % 8) != 0) return k;                         // ragged N only in the BN = 16 variant
+  k.MODE = p.mode; k.GEGLU = p.geglu != 0; k.DIT = p.dit != 0; k.BF = p.dit && p.bf16; k.QKN = p.dit && p.qkn_nq; k.SPLIT = split; k.MX = p.dit && p.mx; k.GNS = p.gn_partial != nullptr;
+  auto found = [&](const Tile& x) { k.BM = x.bm; k.BN = x.bn; k.STAGES = x.st; return find_inst(k); };
+  if (p.gn_partial) {
+    // GroupNorm partial sums from the epilogue: plain 3x3 convs, one slab per wave tile; a forced tile without this epilogue (or a number that is no code) is refused
+    if ((p.mode != A_CONV3 && p.mode != A_CONV_SMALLC) || p.dit || p.geglu || p.splitk > 1 || p.batch > 1 || split || p.bn == 16) return k;
+    if ((p.M % 64) != 0 || (p.N % 8) != 0) return k;
+    if (p.mode == A_CONV_SMALLC ? t == T128x160 : !known) return k;
+    if (p.mode == A_CONV_SMALLC) t = T128x128;                                              // conv_in: the 128x128 tile
+    if (const GemmInst* e = found(t)) k.ok = (p.M % e->wtm) == 0;
+    return k;
   }
-  if (p.N % 160 == 0 && p.K >= 1024) return 160;
-  if ((long)p.M * p.N >= (1L << 26) && tiles256 >= S2) return 256;        // short-K, large MxN (qkv @ C=640): 712 vs 642
-  return 128;
+  if (p.dit) {
+    if (p.mode != A_DENSE || p.geglu || p.batch > 1) return k;
+    if (p.qkn_nq && (t.bm != 256 || t.bn != 256 || (p.qkn_nq % 128) != 0)) return k;       // one head per 128-column wave tile
+    if (p.qkn_nq && (p.res32 || p.res16 || p.rowvec || p.aux16 || p.out32)) return k;       // the QKN instantiation: bias -> norm + RoPE -> out16 only
+    if (p.mx && (!p.bf16 || p.qkn_nq || split || (p.N % 8))) return k;                      // fp8 (e4m3) operands ('fp8-mx' plans)
+  } else {
+    if (p.geglu && (p.mode != A_DENSE || (p.N % 32) != 0)) return k;                        // weight rows / bias interleaved [16 h | 16 gate]
+    if (t.bn == 16 && (p.mode == A_CONV_SMALLC || (split && !p.geglu && p.mode != A_CONV3))) return k;   // narrow N: conv_out, plain dense
+    if (p.mode == A_CONV_SMALLC && !(t == T128x160)) t = T128x128;                          // conv_in has two tiles: any other choice means 128x128
+  }
+  if (!found(t)) {
+    // the fall-backs, all to the form's 128x128 tile: the reduced tile set of the split forms (silent: it is their selection rule), and a
+    // forced tile this form has no instantiation of (flagged: the C ABI refuses it).  Anything else without an entry is an error
+    const bool reduced = split && t.bn != 16;
+    if ((!reduced && !forced) || !found(T128x128)) return k;
+    k.forced_missing = !reduced;
+  }
+  k.ok = true;
+  return k;
 }
 
 // true when an MMDiT GEMM of this shape runs on the 256x256 tile, i.e. may carry the fused RMSNorm + RoPE epilogue (qkn_*)
 bool gemm_qkn_ok(int M, int N, int K) {
   GemmParams g{}; g.M = M; g.N = N; g.K = K; g.dit = 1; g.mode = A_DENSE;
-  const int v = pick_variant(g);
-  return v == 8256 || v == 1256;
+  const GemmSel k = gemm_select(g);
+  return k.ok && k.BM == 256 && k.BN == 256;
 }
 
-// kernel symbol (as rocprofv3 prints it) that launch_gemm would pick for these parameters
-const char* gemm_kernel_name(const GemmParams& p) {
-  const int v = pick_variant(p);
-  int bm = 128, bn = 128, st = 2;
-  if (v == 16) bn = 16; else if (v == 160) bn = 160; else if (v == 256) { bm = 256; st = 3; } else if (v == 320) { bm = 256; bn = 320; }
-  else if (v == 825) { bm = 256; bn = 256; st = 8; } else if (v == 932) { bm = 256; bn = 320; st = 9; } else if (v == 826) { bm = 256; bn = 256; st = 8; }
-  if (p.mode == A_CONV_SMALLC && v != 160) { bm = 128; bn = 128; st = 2; }
+// kernel symbol (as rocprofv3 prints it) of the instantiation the descriptor spells; nullptr where launch_gemm refuses
+const char* gemm_kernel_name(const GemmSel& k) {
+  if (!k.ok) return nullptr;
+  auto tf = [](bool v) { return v ? "true" : "false"; };
   char tmp[64];
-  if (p.gn_partial && !p.dit) snprintf(tmp, sizeof tmp, "gemm_gn_kernel<%d, %d, %d, %d>", p.mode, bm, bn, st);
-  else if (p.dit && p.mx) snprintf(tmp, sizeof tmp, "gemm_mx_kernel<256, 256, 8>");
-  else if (p.dit) snprintf(tmp, sizeof tmp, "%s<%d, %d, %d, %s, %s>", is_dit_split(p) ? "gemm_dit_split_kernel" : "gemm_dit_kernel", v == 128 ? 128 : 256, (v == 1256 || v == 8256) ? 256 : 128, v == 8256 ? 8 : v == 2128 ? 3 : 2, p.bf16 ? "true" : "false", p.qkn_nq ? "true" : "false");
-  else snprintf(tmp, sizeof tmp, "%s<%d, %d, %d, %d, %s>", is_split(p) ? "gemm_split_kernel" : "gemm_kernel", p.mode, bm, bn, st, p.geglu ? "true" : "false");
+  if (k.MX) snprintf(tmp, sizeof tmp, "gemm_mx_kernel<%d, %d, %d>", k.BM, k.BN, k.STAGES);
+  else if (k.GNS) snprintf(tmp, sizeof tmp, "gemm_gn_kernel<%d, %d, %d, %d>", k.MODE, k.BM, k.BN, k.STAGES);
+  else if (k.DIT) snprintf(tmp, sizeof tmp, "%s<%d, %d, %d, %s, %s>", k.SPLIT ? "gemm_dit_split_kernel" : "gemm_dit_kernel", k.BM, k.BN, k.STAGES, tf(k.BF), tf(k.QKN));
+  else snprintf(tmp, sizeof tmp, "%s<%d, %d, %d, %d, %s>", k.SPLIT ? "gemm_split_kernel" : "gemm_kernel", k.MODE, k.BM, k.BN, k.STAGES, tf(k.GEGLU));
   // interned: the returned pointer stays valid for the life of the library (plan build time only, mutex-protected)
   static std::mutex mu;
   static std::deque<std::string> names;
@@ -283,136 +400,18 @@ const char* gemm_kernel_name(const GemmParams& p) {
   names.emplace_back(tmp);
   return names.back().c_str();
 }
-
-// GroupNorm partial sums from the epilogue: plain 3x3 convs on the tiles whose wave tile is 64 rows (128x128, 256x128 ring, 256x256 two-group)
+// rows per GroupNorm statistics slab when `p` runs with gn_partial set: the wave-tile height of the selected instantiation, 0 = it cannot
 int gemm_gn_slab_rows(const GemmParams& p) {
-  if ((p.mode != A_CONV3 && p.mode != A_CONV_SMALLC) || p.dit || p.geglu || p.splitk > 1 || p.batch > 1 || is_split(p) || p.bn == 16) return 0;
-  if ((p.M % 64) != 0 || (p.N % 8) != 0) return 0;
-  const int v = pick_variant(p);
-  if (p.mode == A_CONV_SMALLC) return v != 160 ? 64 : 0;                 // conv_in: the 128x128 tile
-  if (v == 932) return (p.M % 128) == 0 ? 128 : 0;                       // round 5: 256x320 two-group (the UNet's N = 320 k convs): 128-row wave tiles
-  return (v == 128 || v == 160 || v == 256 || v == 826) ? 64 : 0;
-}
-
-// Every reason launch_gemm refuses a launch, as host arithmetic on the parameters (no pointer is followed): shared by launch_gemm and the
-// kernel-name query of the C ABI (gdf_op_gemm_kernel), so that the query answers NULL exactly where the launch returns an error.
-hipError_t gemm_check(const GemmParams& p) {
-  if (p.mode != A_CONV_SMALLC && (p.K % BK) != 0) return hipErrorInvalidValue;
-  if (p.mode == A_CONV3 && (p.Cin % BK) != 0) return hipErrorInvalidValue;
-  if (p.k_w > 0 && (p.K != 2 * p.k_w || (p.k_w % BK) != 0 || p.mode == A_CONV_SMALLC || (p.dit && !p.bf16) || (p.mode == A_CONV3 && (p.k_w % (9 * BK)) != 0)))
-    return hipErrorInvalidValue;                                                         // split operands: K = [hi | lo] over one weight matrix
-  if (p.o16_lo > 0 && ((p.dit && !p.bf16) || p.bn == 16 || (p.o16_lo % 8) != 0)) return hipErrorInvalidValue;   // (MMDiT: the bf16 pair form only)
-  if (p.out_f16 && !(p.dit && p.bf16)) return hipErrorInvalidValue;
-  const int v = pick_variant(p);
-  if (v != 16 && ((p.geglu ? p.N / 2 : p.N) % 8) != 0) return hipErrorInvalidValue;   // ragged N only in the BN = 16 variant
-  if (p.bf16 && !p.dit) return hipErrorInvalidValue;                                      // bf16 exists on the MMDiT path only
-  if (p.gn_partial) return (gemm_gn_slab_rows(p) == 0 || !p.out16) ? hipErrorInvalidValue : hipSuccess;
-  if (p.dit) {
-    if (p.mode != A_DENSE || p.geglu || p.batch > 1) return hipErrorInvalidValue;
-    if (p.qkn_nq && ((v != 8256 && v != 1256) || (p.qkn_nq % 128) != 0)) return hipErrorInvalidValue;   // one head per 128-column wave tile
-    if (p.qkn_nq && (p.res32 || p.res16 || p.rowvec || p.aux16 || p.out32)) return hipErrorInvalidValue;  // the QKN instantiation: bias -> norm + RoPE -> out16 only
-    if (p.mx && (!p.bf16 || p.qkn_nq || is_dit_split(p) || (p.N % 8))) return hipErrorInvalidValue;      // fp8 (e4m3) operands ('fp8-mx' plans)
-    if (!p.mx && is_dit_split(p) && v != 8256 && p.qkn_nq) return hipErrorInvalidValue;                   // split QKN: the 256x256 two-group tile only
-    return hipSuccess;
-  }
-  if (p.geglu && (p.mode != A_DENSE || (p.N % 32) != 0)) return hipErrorInvalidValue;    // weight rows / bias interleaved [16 h | 16 gate]
-  if (v == 16 && (p.mode == A_CONV_SMALLC || (is_split(p) && !p.geglu && p.mode != A_CONV3))) return hipErrorInvalidValue;   // narrow N: conv_out, plain dense
-  return hipSuccess;
-}
-
-// false where a forced `variant` names a tile the form has no instantiation of (825 / 826 on a plain dense GEMM, 825 on a conv, the
-// 16 / 160 / 932 / 826 tiles with GEGLU): launch_gemm then falls back to the form's 128x128 tile, which gemm_kernel_name() does not follow.
-// The complete entry point of the C ABI and its name query refuse these, so that the name the query gives is the kernel that runs.
-bool gemm_variant_ok(const GemmParams& p) {
-  if (!p.variant || p.dit || p.mode == A_CONV_SMALLC) return true;         // (MMDiT: four tiles, all instantiated; conv_in: the name follows the fallback)
-  const int v = pick_variant(p);
-  if (p.geglu) return v != 16 && v != 160 && v != 932 && v != 826;
-  if (p.mode == A_DENSE) return v != 825 && v != 826;
-  return v != 825;
+  GemmParams q = p; q.gn_partial = (float*)1;                                               // selects the form only: never followed
+  const GemmSel k = gemm_select(q);
+  return k.ok ? find_inst(k)->wtm : 0;
 }
 
 hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
   if (p.M <= 0 || p.N <= 0) return hipSuccess;
-  if (gemm_check(p) != hipSuccess) return hipErrorInvalidValue;
-  const int v = pick_variant(p);
-  if (p.gn_partial) {                                                                     // GroupNorm partial sums from the epilogue (VAE convs)
-    if (p.mode == A_CONV_SMALLC) return launch_t<A_CONV_SMALLC, 128, 128, 2, false, false, false, false, false, false, true>(p, s);
-    if (v == 932) return launch_t<A_CONV3, 256, 320, 9, false, false, false, false, false, false, true>(p, s);
-    if (v == 160) return launch_t<A_CONV3, 128, 160, 2, false, false, false, false, false, false, true>(p, s);
-    if (v == 826) return launch_t<A_CONV3, 256, 256, 8, false, false, false, false, false, false, true>(p, s);
-    if (v == 256) return launch_t<A_CONV3, 256, 128, 3, false, false, false, false, false, false, true>(p, s);
-    return launch_t<A_CONV3, 128, 128, 2, false, false, false, false, false, false, true>(p, s);
-  }
-  if (p.dit) {
-    if (p.mx) return launch_t<A_DENSE, 256, 256, 8, false, true, true, false, false, true>(p, s);   // fp8 (e4m3) operands ('fp8-mx' plans): 256x256 two-group tile only
-    if (is_dit_split(p)) {                                                                // bf16 hi + lo operands ('bfloat16x2' plans)
-      if (v == 8256) return p.qkn_nq ? launch_t<A_DENSE, 256, 256, 8, false, true, true, true, true>(p, s) : launch_t<A_DENSE, 256, 256, 8, false, true, true, false, true>(p, s);
-      return p.qkn_nq ? hipErrorInvalidValue : launch_t<A_DENSE, 128, 128, 2, false, true, true, false, true>(p, s);
-    }
-    if (p.bf16) {
-      if (v == 8256) return p.qkn_nq ? launch_t<A_DENSE, 256, 256, 8, false, true, true, true>(p, s) : launch_t<A_DENSE, 256, 256, 8, false, true, true>(p, s);
-      if (v == 1256) return p.qkn_nq ? launch_t<A_DENSE, 256, 256, 2, false, true, true, true>(p, s) : launch_t<A_DENSE, 256, 256, 2, false, true, true>(p, s);
-      if (v == 2128) return launch_t<A_DENSE, 256, 128, 3, false, true, true>(p, s);
-      return launch_t<A_DENSE, 128, 128, 2, false, true, true>(p, s);
-    }
-    if (v == 8256) return p.qkn_nq ? launch_t<A_DENSE, 256, 256, 8, false, true, false, true>(p, s) : launch_t<A_DENSE, 256, 256, 8, false, true>(p, s);
-    if (v == 1256) return p.qkn_nq ? launch_t<A_DENSE, 256, 256, 2, false, true, false, true>(p, s) : launch_t<A_DENSE, 256, 256, 2, false, true>(p, s);
-    if (v == 2128) return launch_t<A_DENSE, 256, 128, 3, false, true>(p, s);
-    return launch_t<A_DENSE, 128, 128, 2, false, true>(p, s);
-  }
-  if (is_split(p)) {                                                                      // "precise" plans: the reduced tile set of pick_variant
-    if (p.geglu) {
-      return v == 825 ? launch_t<A_DENSE, 256, 256, 8, true, false, false, false, true>(p, s)
-                      : launch_t<A_DENSE, 128, 128, 2, true, false, false, false, true>(p, s);
-    }
-    if (v == 16) {
-      if (p.mode == A_CONV3) return launch_t<A_CONV3, 128, 16, 2, false, false, false, false, true>(p, s);   // conv_out
-      return hipErrorInvalidValue;
-    }
-    switch (p.mode) {
-      case A_DENSE:
-        if (v == 160) return launch_t<A_DENSE, 128, 160, 2, false, false, false, false, true>(p, s);
-        if (v == 932) return launch_t<A_DENSE, 256, 320, 9, false, false, false, false, true>(p, s);
-        return launch_t<A_DENSE, 128, 128, 2, false, false, false, false, true>(p, s);
-      case A_CONV3:
-        if (v == 160) return launch_t<A_CONV3, 128, 160, 2, false, false, false, false, true>(p, s);
-        if (v == 932) return launch_t<A_CONV3, 256, 320, 9, false, false, false, false, true>(p, s);
-        return launch_t<A_CONV3, 128, 128, 2, false, false, false, false, true>(p, s);
-      case A_CONV_SMALLC:
-        return v == 160 ? launch_t<A_CONV_SMALLC, 128, 160, 2, false, false, false, false, true>(p, s)
-                        : launch_t<A_CONV_SMALLC, 128, 128, 2, false, false, false, false, true>(p, s);
-    }
-    return hipErrorInvalidValue;
-  }
-  if (p.geglu) {
-    // weight rows / bias interleaved [16 h | 16 gate] (launch_relayout_rows geglu = 16)
-    if (v == 825) return launch_t<A_DENSE, 256, 256, 8, true>(p, s);
-    if (v == 320) return launch_t<A_DENSE, 256, 320, 2, true>(p, s);
-    return v == 256 ? launch_t<A_DENSE, 256, 128, 3, true>(p, s) : launch_t<A_DENSE, 128, 128, 2, true>(p, s);
-  }
-  if (v == 16) {
-    if (p.mode == A_CONV3) return launch_t<A_CONV3, 128, 16, 2, false>(p, s);
-    if (p.mode == A_DENSE) return launch_t<A_DENSE, 128, 16, 2, false>(p, s);
-    return hipErrorInvalidValue;
-  }
-  switch (p.mode) {
-    case A_DENSE:
-      if (v == 160) return launch_t<A_DENSE, 128, 160, 2, false>(p, s);
-      if (v == 932) return launch_t<A_DENSE, 256, 320, 9, false>(p, s);
-      if (v == 320) return launch_t<A_DENSE, 256, 320, 2, false>(p, s);
-      if (v == 256) return launch_t<A_DENSE, 256, 128, 3, false>(p, s);
-      return launch_t<A_DENSE, 128, 128, 2, false>(p, s);
-    case A_CONV3:
-      if (v == 160) return launch_t<A_CONV3, 128, 160, 2, false>(p, s);
-      if (v == 932) return launch_t<A_CONV3, 256, 320, 9, false>(p, s);
-      if (v == 826) return launch_t<A_CONV3, 256, 256, 8, false>(p, s);
-      if (v == 320) return launch_t<A_CONV3, 256, 320, 2, false>(p, s);
-      if (v == 256) return launch_t<A_CONV3, 256, 128, 3, false>(p, s);
-      return launch_t<A_CONV3, 128, 128, 2, false>(p, s);
-    case A_CONV_SMALLC:
-      return v == 160 ? launch_t<A_CONV_SMALLC, 128, 160, 2, false>(p, s) : launch_t<A_CONV_SMALLC, 128, 128, 2, false>(p, s);
-  }
-  return hipErrorInvalidValue;
+  const GemmSel k = gemm_select(p);
+  const GemmInst* e = k.ok ? find_inst(k) : nullptr;
+  return e && (p.out16 || !k.GNS) ? e->launch(p, s) : hipErrorInvalidValue;                 // (the statistics are those of the stored fp16 image)
 }
 
 // ---- split-K: sum the partial slabs in a fixed order (deterministic) and apply the GEMM epilogue of kernels.h ----
@@ -479,7 +478,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p, 
 int gemm_splitk_factor(const GemmParams& p) {
   static const int off = [] { const char* e = getenv("GDF_SPLITK"); return e && atoi(e) == 0; }();     // diagnostics: GDF_SPLITK=0
   if (off || p.dit || p.geglu || p.bn == 16 || p.batch > 1 || p.mode == A_CONV_SMALLC || p.variant || (p.N % 128) || (p.K % BK)) return 1;
-  const long tiles = (long)((p.M + 127) / 128) * ((p.N % 160 == 0) ? p.N / 160 : p.N / 128);       // (the split tile: pick_variant_any)
+  const long tiles = (long)((p.M + 127) / 128) * (p.N / splitk_tile(p.N).bn);
   const int nk = p.K / BK;
   const int S1 = p.cus > 0 ? p.cus : 256;
   if (tiles >= S1 || nk < 64) return 1;

@@ -92,7 +92,7 @@ struct GemmParams {
   int sb_gm, sb_gn;      // (set by launch_gemm) tiles per XCD super-block, 0 = linear XCD-chunked order
   int no_superblock;     // diagnostics: force the linear order
   int no_early_mma;      // diagnostics: disable the opposite-order heads of the two waves sharing a SIMD (256x128 variant)
-  int variant;           // 0 = auto; 128 / 160 / 256 force the 128x128, 128x160 or 256x128 tile (diagnostics)
+  int variant;           // 0 = auto, else a tile forced by its public code (include/gdf_ops.h gdf_op_gemm; decoded in gemm.hip: unet_tile / dit_tile)
   // ---- MMDiT epilogue (dit != 0 selects gemm_dit_kernel; dense only) ----
   //      v = acc + bias;  act == 1: v = gelu_tanh(v);  rowvec: v = rv_mul ? v * rowvec[sample][col] : v + rowvec[sample][col];
   //      then residual / stores as above.  sample = row / rows_per_sample for row < rv_seg_rows (or rv_seg_rows == 0),
@@ -144,14 +144,23 @@ struct GemmParams {
   // Requires M % slab_rows == 0 and (rows per sample) % slab_rows == 0.  nullptr = off (every UNet / MMDiT plan).
   float* gn_partial;
 };
+// Dispatch: gemm_select() maps the parameters to a descriptor, which spells ONE instantiation (the template arguments of gemm_body); launch_gemm()
+// launches the instantiation the descriptor names and gemm_kernel_name() prints the same descriptor.  Host arithmetic only, no pointer is followed.
+struct GemmSel {
+  bool ok;                 // false: launch_gemm refuses these parameters
+  int MODE, BM, BN, STAGES; bool GEGLU, DIT, BF, QKN, SPLIT, MX, GNS;
+  bool forced_missing;     // `variant` named a tile this form has no instantiation of: the descriptor is the form's 128x128 tile, which launch_gemm
+                           // runs; gdf_op_gemm_ex and gdf_op_gemm_kernel refuse these
+};
+GemmSel gemm_select(const GemmParams& p);
 hipError_t launch_gemm(const GemmParams& p, hipStream_t s);
-// hipSuccess where launch_gemm accepts `p` (host arithmetic only, no pointer is followed; launch_gemm itself starts with this check)
-hipError_t gemm_check(const GemmParams& p);
-// false where a forced `variant` names a tile the form has no instantiation of: launch_gemm would run the form's 128x128 tile under
-// another name than gemm_kernel_name() gives (gdf_op_gemm_ex and gdf_op_gemm_kernel refuse these)
-bool gemm_variant_ok(const GemmParams& p);
+// kernel symbol (as the profiler prints it) of the descriptor's instantiation, nullptr where !ok
+const char* gemm_kernel_name(const GemmSel& k);
+inline const char* gemm_kernel_name(const GemmParams& p) { return gemm_kernel_name(gemm_select(p)); }
 // rows per statistics slab if launch_gemm can run `p` (shape, mode, epilogue form) with gn_partial set, else 0
 int gemm_gn_slab_rows(const GemmParams& p);
+// true when an MMDiT GEMM of this shape runs on the 256x256 tile, i.e. may carry the fused RMSNorm + RoPE epilogue (qkn_*)
+bool gemm_qkn_ok(int M, int N, int K);
 // Deterministic split-K for problems with few output tiles and a long K (the 8x8-level 3x3 convs of SD1.5: 160 tiles of 128x128,
 // K = 11520..23040): gemm_splitk_factor() > 1 says it pays; the caller provides `splitk * M * N` floats of workspace, the GEMM
 // launch writes one raw partial-sum slab per K range and splitk_reduce_kernel sums them in a fixed order and applies the epilogue.
@@ -160,8 +169,6 @@ hipError_t launch_gemm_splitk(const GemmParams& p, int splitk, float* ws, hipStr
 // the first launch of launch_gemm_splitk as GemmParams `g` (host arithmetic): false where the split launch is refused; `splitk` is clamped to
 // the K-tile count, <= 1 afterwards = the plain launch of `p`
 bool gemm_splitk_pass1(const GemmParams& p, int& splitk, float* ws, GemmParams& g);
-const char* gemm_kernel_name(const GemmParams& p);
-bool gemm_qkn_ok(int M, int N, int K);   // kernel symbol launch_gemm would pick (only M,N,K,mode,geglu,bn,variant are read)
 
 // ------------------------------------------------------------------------------------------------
 // flash attention (self / cross), fp16 in, fp32 softmax, fp16 out

@@ -102,7 +102,7 @@ int gdf_op_gemm_ex(const gdf_gemm_args* args, void* stream) {
   GemmParams g{};
   const int rc = gemm_params(*args, g, "gemm_ex");
   if (rc != GDF_OK) return rc;
-  if (!gemm_variant_ok(g)) { set_error("gemm_ex: this form has no instantiation of the forced tile variant"); return GDF_ERR_ARG; }
+  if (gemm_select(g).forced_missing) { set_error("gemm_ex: this form has no instantiation of the forced tile variant"); return GDF_ERR_ARG; }
   if (args->splitk > 1) return fin(launch_gemm_splitk(g, args->splitk, args->splitk_ws, (hipStream_t)stream), "gemm_ex");
   return fin(launch_gemm(g, (hipStream_t)stream), "gemm_ex");
 }
@@ -113,7 +113,8 @@ const char* gdf_op_gemm_kernel(const gdf_gemm_args* args) {
   if (gemm_params(*args, p, nullptr) != GDF_OK || p.M <= 0 || p.N <= 0) return nullptr;
   int splitk = args->splitk;
   if (!gemm_splitk_pass1(p, splitk, nullptr, g)) return nullptr;      // (splitk <= 1: g = p)
-  return gemm_check(g) == hipSuccess && gemm_variant_ok(g) ? gemm_kernel_name(g) : nullptr;
+  const GemmSel k = gemm_select(g);
+  return k.forced_missing ? nullptr : gemm_kernel_name(k);
 }
 
 int gdf_op_gemm(const void* A, int lda, const void* W, const float* bias, const float* res32, const void* res16,

@@ -104,6 +104,36 @@ def test_reachable_kernels_are_all_kernel_tested():
     print("GEMM_REACHABLE\n" + "\n".join(sorted(reachable)))
 
 
+VARIANT_CODES = (16, 128, 160, 256, 320, 825, 826, 932, 1256, 2128, 8256, 832)   # the eleven public codes and 832, a number that is no code
+
+
+def test_forced_variants_name_only_kernel_tested_instantiations():
+    """every form x every forced `variant` code: the query answers None or a kernel with a kernel-level row — nothing nameable lies outside the
+    tested instantiation list (a name printed for an instantiation that does not exist would be outside it)"""
+    L = lib()
+    tested = {c["kernel"] for c in CASES} | {c["kernel"] for c in CONV_CASES}
+    outside = []
+    for v in VARIANT_CODES:
+        got = {}
+        for M, N, K in itertools.product((200, 4096, 16384), (128, 320, 1280, 3072), (64, 1280)):
+            for split in (False, True):
+                got["dense", split, M, N, K] = name(L, M, N, K, split=split, variant=v)
+                got["conv3", split, M, N, K] = name(L, M, N, K, conv=True, split=split, variant=v)
+                got["conv_in", split, M, N] = name(L, M, N, 4, conv=True, variant=v, **(dict(o16_lo=N) if split else {}))
+                got["geglu", split, M, N, K] = name(L, M, N, K, geglu=1, split=split, variant=v)
+                got["narrow", split, M, N, K] = name(L, M, N, K, conv=True, bn=16, split=split, variant=v)
+            got["narrow dense", M, N, K] = name(L, M, N, K, bn=16, variant=v)
+            for bf16, split, qkn in ((0, False, 0), (0, False, 128), (1, False, 0), (1, False, 128), (1, True, 0), (1, True, 128)):
+                got["dit", bf16, split, qkn, M, N, K] = name(L, M, N, K, dit=1, bf16=bf16, split=split, qkn=qkn, variant=v)
+            got["mx", M, N, K] = name(L, M, N, K, mx=1, variant=v)
+            for cin in (4, K):
+                n = L.gdf_op_conv3x3_gn_info(1, IMG[M][0], IMG[M][1], cin, N, 1, 0, v << 8, None)
+                got["gn", M, N, cin] = n.decode() if n is not None else None
+        assert any(n is not None for n in got.values()), v
+        outside += [(v, k, n) for k, n in got.items() if n is not None and n not in tested]
+    assert not outside, outside[:20]
+
+
 def test_case_inputs_leave_the_bounds_their_headroom():
     """the CPU half of the small cases: the emulated contract (fp32 accumulation, one rounding) stays under a third of every per-block bound"""
     L = lib()
