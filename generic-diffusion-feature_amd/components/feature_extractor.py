@@ -72,6 +72,15 @@ class FeatureStore:
         return self.feats
 
 
+def background_capture_rows(store_idx, n_rows):
+    """UNet calls (0-based rows of a sampling table) whose features a run of n_rows calls keeps, given FeatureStore.store_idx: the store
+    counts encounters from 1 (:63-67), so encounter i is row i - 1 and indices past the last call never fire; store_idx None keeps what
+    the last call overwrote everything with (:60-61) — the last row."""
+    if store_idx is None:
+        return [n_rows - 1]
+    return sorted({int(i) - 1 for i in store_idx if 1 <= int(i) <= n_rows})
+
+
 class FeatureGatherer:
     """Kept for API compatibility (reference :83-89): forwards `module_id-feat_id` to the store."""
 

@@ -164,6 +164,70 @@ def scheduler_step_scalars(scheduler, timestep):
     return a, b
 
 
+def sampling_table(scheduler, num_inference_steps):
+    """A scheduler's whole `set_timesteps(n)` ... `step` run as rows (timestep, c_in, c_sample, w0, w1, w2, w3, w4) for NativeUNet.sample, plus
+    its init_noise_sigma (1.0 when it has none): forward k sees c_in[k] x_k at timestep[k], then
+        x_{k+1} = c_sample[k] x_k + sum_{j<5} w_j[k] e_{k-j}                                   (e_i: the model output of call i).
+    Works for every scheduler whose run is LINEAR in (x_0, e_0, ..., e_{K-1}) reaching back at most five UNet calls — DDIM, EulerDiscrete,
+    PNDM / PLMS (four outputs, but its warm-up call at the repeated timestep is not among them, so call 4 reaches call 0), LMS,
+    DPMSolverMultistep without thresholding — and needs none of their formulas: like scheduler_step_scalars it PROBES.
+    On deep copies, after set_timesteps(n), the whole step chain runs in float64 on one-element tensors for the basis inputs x_0 = 1 with
+    every e = 0 and e_i = 1 alone for each i, which gives x_k = A_k x_0 + sum_i B_{k,i} e_i; then
+        c_sample[k] = A_{k+1} / A_k,      w_j[k] = B_{k+1,k-j} - c_sample[k] B_{k,k-j}.
+    Every coefficient older than j = 4 must vanish (1e-9 of the row's largest) and one more chain on random inputs must follow the table;
+    a scheduler that fails either check (ancestral and other stochastic ones, thresholding, more history) raises NotImplementedError.
+    c_in[k] is `scale_model_input(1, t_k)`.  The timesteps are `scheduler.timesteps` as they stand: PNDM with skip_prk_steps lists its
+    second timestep twice, which is two rows and two UNet calls.  K + 2 chains of K steps: milliseconds for the usual 20-50 steps."""
+    import copy
+    name = type(scheduler).__name__
+    base = copy.deepcopy(scheduler)
+    base.set_timesteps(int(num_inference_steps))
+    ts = [t for t in base.timesteps]
+    K = len(ts)
+    if K < 1:
+        raise ValueError("the scheduler has no timesteps")
+    one = lambda v: torch.full((1, 1, 1, 1), float(v), dtype=torch.float64)
+
+    def chain(x0, es):
+        sch = copy.deepcopy(base)
+        x, xs, cin = one(x0), [float(x0)], []
+        for k, t in enumerate(ts):
+            cin.append(float(sch.scale_model_input(one(1.0), t).flatten()[0]))
+            x = sch.step(one(es[k]), t, x, return_dict=False)[0].double()
+            xs.append(float(x.flatten()[0]))
+        return xs, cin
+
+    zeros = [0.0] * K
+    A, c_in = chain(1.0, zeros)
+    Bm = [chain(0.0, [1.0 if i == j else 0.0 for j in range(K)])[0] for i in range(K)]          # Bm[i][k] = B_{k,i}
+    rows = []
+    for k in range(K):
+        if A[k] == 0.0:
+            raise NotImplementedError(f"{name}: the sample's own coefficient vanishes at step {k}; no per-step table exists")
+        cs = A[k + 1] / A[k]
+        w = [Bm[k - j][k + 1] - cs * Bm[k - j][k] for j in range(k + 1)]
+        top = max([abs(cs)] + [abs(v) for v in w])
+        future = max([abs(Bm[i][k + 1]) for i in range(k + 1, K)] + [0.0])
+        if any(abs(v) > 1e-9 * top for v in w[5:]) or future > 1e-9 * top:
+            raise NotImplementedError(f"{name}: step {k} reaches back more than five UNet calls; NativeUNet.sample keeps five model outputs")
+        w = (w + [0.0] * 5)[:5]
+        rows.append((float(ts[k]), c_in[k], cs) + tuple(w))
+    # the linearity check: one chain on random inputs against the table's recurrence, at every step
+    g = torch.Generator().manual_seed(1234)
+    x0 = float(torch.randn(1, generator=g, dtype=torch.float64))
+    es = torch.randn(K, generator=g, dtype=torch.float64).tolist()
+    xs, _ = chain(x0, es)
+    x = x0
+    for k in range(K):
+        x = rows[k][2] * x + sum(rows[k][3 + j] * es[k - j] for j in range(min(5, k + 1)))
+        if not abs(x - xs[k + 1]) <= 1e-6 * (1.0 + abs(xs[k + 1])):
+            raise NotImplementedError(f"{name}: scheduler.step is not a fixed linear function of the sample and the model outputs (step {k}: "
+                                      f"{xs[k + 1]!r} against {x!r} from the probed coefficients) — stochastic or thresholding schedulers cannot "
+                                      "run as a device-resident table")
+        x = xs[k + 1]
+    return rows, float(getattr(base, "init_noise_sigma", 1.0))
+
+
 def ddim_timesteps(config, num_inference_steps, num_train_timesteps=1000):
     """DDIMScheduler.set_timesteps(num_inference_steps).timesteps (descending ints) from the scheduler config alone — the published rule of
     diffusers' DDIMScheduler per `timestep_spacing` (Table 2 of arXiv 2305.08891), restated so that no diffusers install is needed; the class

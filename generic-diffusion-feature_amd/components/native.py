@@ -4,6 +4,7 @@
 There is NO CPU / PyTorch fallback here on purpose: if the HIP library is missing or no GPU is
 visible, construction raises.  PyTorch is only used for device memory, streams and tensor views.
 """
+import collections
 import ctypes as C
 import os
 import time
@@ -68,6 +69,11 @@ SIGNATURES = {
                                    C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_int]),
     "gdf_trajectory": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdf_sample_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "gdf_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdf_op_guided_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p]),
     "gdf_plan_set_graph": (C.c_int, [C.c_void_p, C.c_int]),
     "gdf_plan_graph_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "gdf_plan_graph_failures": (C.c_long, [C.c_void_p]),
@@ -920,6 +926,107 @@ class NativeUNet(_NativeModel):
                  (B, H, W, self.cfg["out_channels"]), call, eager=eager)
         # the master lives in the plan's staging buffer, which the next call overwrites: hand out a copy (ordered on the caller's stream)
         return plan.staged["x32"].clone()
+
+    # ---- guided sampling with hook capture at selected UNet calls -------------------------------------------------
+    def sample(self, latents_f32, rows, guidance, ctx_pos, ctx_neg=None, text_embeds=None, time_ids=None, hook_ids=(), capture_rows=(),
+               eager=False):
+        """len(rows) x (one forward + one guided scheduler update) on the device (gdf_sample, include/gdf.h).  Row k of `rows` is
+        (timestep, c_in, c_sample, w0, w1, w2, w3, w4) (components/models.py sampling_table): forward k sees fp16(c_in[k] * x_k) at timestep[k],
+        then e_k = e_uncond + guidance (e_cond - e_uncond) and x_{k+1} = c_sample[k] x_k + sum_j w_j[k] e_{k-j} on the fp32 master.
+        guidance > 1: the forwards have batch 2B, [ctx_neg, ctx_pos] (torch.cat([negative, positive])), and `text_embeds` / `time_ids`
+        already hold both halves in that order (2B rows).  guidance <= 1: batch B, ctx_pos alone, as diffusers does.
+        The rows listed in `capture_rows` run a plan with `hook_ids` instead of the hook-less one.
+        Returns (final fp32 latents (B,4,H,W), a new tensor; {row: OrderedDict id -> (2B|B, C, H, W) fp16}).
+        Both plans run at ONE operand-split level, chosen the way `trajectory` chooses it: the level the requested hooks (hook_ids plus the
+        current feature selection) are promised at.  The call BYPASSES the verify ladder (`verify=True` checks single forwards only)."""
+        dev = self.device
+        B, _, H, W = latents_f32.shape
+        guided = float(guidance) > 1.0
+        table = [tuple(float(v) for v in r) for r in rows]
+        if not table or len(table) > self.TRAJECTORY_MAX_STEPS or any(len(r) != 8 for r in table):
+            raise ValueError(f"rows must hold 1..{self.TRAJECTORY_MAX_STEPS} rows of (timestep, c_in, c_sample, w0, w1, w2, w3, w4)")
+        caps = [int(k) for k in capture_rows]
+        if any(k < 0 or k >= len(table) for k in caps) or any(b <= a for a, b in zip(caps, caps[1:])):
+            raise ValueError("capture_rows must be ascending row indices of `rows`")
+        hook_ids = list(hook_ids)
+        if caps and not hook_ids:
+            raise ValueError("capture_rows without hook_ids")
+        if guided:
+            if ctx_neg is None or ctx_neg.shape != ctx_pos.shape:
+                raise ValueError("a guided run needs ctx_neg of ctx_pos's shape")
+            ctx = torch.cat([ctx_neg.to(dev), ctx_pos.to(dev)], 0)
+        else:
+            ctx = ctx_pos.to(dev)
+        PB = 2 * B if guided else B
+        txt = tid = None
+        if self.cfg["addition_embed_text_time"]:
+            if text_embeds is None or time_ids is None:
+                raise ValueError("text_embeds and time_ids are required for this UNet")
+            txt, tid = text_embeds, time_ids
+            pooled = self.cfg["add_in_dim"] - 6 * self.cfg["addition_time_embed_dim"]
+            if tuple(txt.shape) != (PB, pooled) or tuple(tid.shape) != (PB, 6):
+                raise ValueError(f"text_embeds {tuple(txt.shape)} / time_ids {tuple(tid.shape)} do not match the model "
+                                 f"(expected ({PB},{pooled}) / ({PB},6))")
+        if ctx.shape[0] != PB or ctx.shape[2] != self.cfg["cross_attention_dim"]:
+            raise ValueError("encoder_hidden_states shape mismatch")
+        have = set(hook_ids)
+        promised = hook_ids + [i for i in self.requested_ids() + list(self.extra_hook_ids) if i not in have]
+        split = self.split_for(promised, lat=min(H, W))
+        plain = self._plan(PB, H, W, ctx.shape[1], (), False, split, early_exit=False)
+        hooked = self._plan(PB, H, W, ctx.shape[1], hook_ids, False, split, early_exit=False) if caps else None
+        lib = self.lib
+        flat = (C.c_float * (8 * len(table)))(*[v for r in table for v in r])
+        cap_arr = (C.c_int * max(1, len(caps)))(*caps)
+        f16, f32 = torch.float16, torch.float32
+        # Buffers of this call (allocated on the caller's stream, written on the plain plan's: _Plan.run orders the two).  The state block
+        # and the hooked plan's workspace keep their addresses from call to call, so the graphs keep theirs; the capture buffers are new
+        # tensors that belong to the caller.
+        with torch.cuda.device(dev):
+            nst = int(lib.gdf_sample_state_bytes(PB, H, W, len(table)))
+            st = getattr(plain, "sample_state", None)
+            if st is None or st.numel() < nst:
+                if st is not None and plain.stream is not None:
+                    plain.stream.synchronize()
+                st = plain.sample_state = torch.empty(nst, dtype=torch.uint8, device=dev)
+            captured, ptrs = {}, []
+            ws_h = None
+            if hooked is not None:
+                if hooked.workspace is None or hooked.workspace.numel() < hooked.ws_bytes:
+                    hooked.workspace = torch.empty(hooked.ws_bytes, dtype=torch.uint8, device=dev)
+                ws_h = hooked.workspace
+                offs, tot = [], 0
+                for (_, _, _, nbytes) in hooked.hooks:
+                    offs.append(tot)
+                    tot += (nbytes // 2 + 127) // 128 * 128
+                for k in caps:
+                    buf = torch.empty(max(tot, 128), dtype=f16, device=dev)
+                    od = collections.OrderedDict()
+                    for off, (hid, shape, stride, _) in zip(offs, hooked.hooks):
+                        od[hid] = torch.as_strided(buf, shape, stride, storage_offset=off)
+                        ptrs.append(buf.data_ptr() + 2 * off)
+                    captured[k] = od
+            hook_arr = (C.c_void_p * max(1, len(ptrs)))(*ptrs)
+
+        def call(staged, hook_ptrs, out_ptr, ws_ptr, stream_ptr):
+            vp = lambda a: C.c_void_p(a.data_ptr() if a is not None else 0)
+            x32, c, tx, ti = staged
+            # Capture rows run eagerly: every call brings new hook buffers, and a graph is keyed on them (one build per capture and call
+            # otherwise).  Their launches are queued while the GPU is still busy with the replayed rows before them.
+            off = hooked is not None and hooked.graph                        # (the plain plan's switch is _Plan.run's)
+            if off:
+                lib.gdf_plan_set_graph(hooked.handle, 0)
+            try:
+                _check(lib.gdf_sample(plain.handle, hooked.handle if hooked is not None else None, vp(x32), len(table), flat,
+                                      C.c_float(float(guidance)), vp(c), vp(tx), vp(ti), cap_arr, len(caps), hook_arr, out_ptr, vp(st), ws_ptr,
+                                      vp(ws_h), stream_ptr), "sample")
+            finally:
+                if off:
+                    lib.gdf_plan_set_graph(hooked.handle, 1)
+
+        plain.run(dev, [("x32", latents_f32, f32), ("ctx", ctx, f16), ("txt", txt, f16), ("tid", tid, f32)],
+                  (PB, H, W, self.cfg["out_channels"]), call, eager=eager)
+        # the master lives in the plan's staging buffer, which the next call overwrites: hand out a copy (ordered on the caller's stream)
+        return plain.staged["x32"].clone(), captured
 
     def __call__(self, sample, timestep=None, encoder_hidden_states=None, added_cond_kwargs=None,
                  down_block_additional_residuals=None, mid_block_additional_residual=None, return_dict=False,

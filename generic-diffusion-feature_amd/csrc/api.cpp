@@ -255,6 +255,16 @@ int gdf_trajectory(gdf_plan* p, float* latents_f32, int n_steps, const float* ta
                          (hipStream_t)stream);
 }
 
+size_t gdf_sample_state_bytes(int batch, int lat_h, int lat_w, int n_rows) { return sample_state_bytes(batch, lat_h, lat_w, n_rows); }
+
+int gdf_sample(gdf_plan* plain, gdf_plan* hooked, float* latents_f32, int n_rows, const float* table, float guidance, const void* ctx,
+               const void* add_text_embeds, const float* add_time_ids, const int* capture_rows, int n_capture, void* const* hook_out,
+               void* noise_pred_scratch, void* state, void* ws_plain, void* ws_hooked, void* stream) {
+  if (!plain) { set_error("null plan"); return GDF_ERR_ARG; }
+  return plan_sample(plain->p, hooked ? &hooked->p : nullptr, latents_f32, n_rows, table, guidance, ctx, add_text_embeds, add_time_ids,
+                     capture_rows, n_capture, hook_out, noise_pred_scratch, state, ws_plain, ws_hooked, (hipStream_t)stream);
+}
+
 int gdf_plan_profile(gdf_plan* p, const void* latents, const float* timesteps, const void* ctx,
                      const void* add_text_embeds, const float* add_time_ids, void* const* hook_out, void* noise_pred,
                      void* workspace, void* stream, float* ms, const char** names, double* flops, int cap) {

@@ -580,4 +580,148 @@ hipError_t launch_latent_step(float* x, const half_t* eps, half_t* y, float* tbu
   return hipGetLastError();
 }
 
+// ---- guided sampling (gdf_sample, include/gdf.h): classifier-free guidance + a scheduler step with history between two forwards ----
+// Replaces, per UNet call of a text-to-image loop, `noise_pred_uncond + g (noise_pred_text - noise_pred_uncond)`, `scheduler.step` of any
+// scheduler whose update is linear in the sample and the last five model outputs (DDIM, Euler, PLMS, LMS, DPM-Solver multistep:
+// components/models.py sampling_table) and `scheduler.scale_model_input` + `torch.cat([latents] * 2)` for the next call.  Same file as
+// latent_step_kernel for the same reason (no packed fp32), same ticket scheme: every step is the same launch with the same arguments.
+//   x     fp32 master latents (B, 4, H, W) NCHW, updated in place
+//   eps   fp16 noise_pred, channels-last as conv_out writes it, read only: guided (2B, H, W, 4), rows [0, B) unconditional and [B, 2B)
+//         conditional (torch.cat([negative, positive])); unguided (B, H, W, 4)
+//   hist  fp32 ring of the last five combined eps, (5, B, 4, H, W); slot k mod 5 is written by step k.  Five, not four: PNDM's warm-up
+//         call at the repeated timestep is not kept in its history, so its first four-term step reaches back five calls
+//   y     fp16 next forward input c_in[next] * x': guided (2B, 4, H, W), the same values in both halves; unguided (B, 4, H, W)
+//   tbuf  fp32 next timestep, 2B or B entries
+//   steps int32 {step, ticket, n_rows, guided}, float g, three unused words, then float rows[n_rows][8] =
+//         {timestep, c_in, c_sample, w0, w1, w2, w3, w4}
+// Step k:  e = e_u + g (e_c - e_u)  (unguided: e = eps);  hist[k mod 5] = e;  x' = c_sample x + sum_j w_j hist[(k - j) mod 5], all fp32; a term
+// with w_j == 0 is skipped, so a ring slot that no step has written is never read.  prime = 1: no update (eps and hist untouched, x not
+// written), row 0 supplies c_in and the timestep, step becomes 0.  step outside [0, n_rows): nothing is written.
+__global__ __launch_bounds__(256) void guided_step_kernel(float* x, const half_t* eps, float* hist, half_t* y, float* tbuf, int* steps,
+                                                          int B, int HW, int hw8, int prime) {
+  const int k = steps[0], n = steps[2];
+  if (n < 1) return;
+  const bool guided = steps[3] != 0;
+  const bool live = prime || (k >= 0 && k < n);
+  if (live) {
+    const float g = ((const float*)steps)[4];
+    const float* rows = (const float*)(steps + 8);
+    const int kr = prime ? 0 : k;
+    const int nx = prime ? 0 : (k + 1 < n ? k + 1 : n - 1);
+    const float cs = rows[8 * kr + 2];
+    const float w0 = rows[8 * kr + 3], w1 = rows[8 * kr + 4], w2 = rows[8 * kr + 5], w3 = rows[8 * kr + 6], w4 = rows[8 * kr + 7];
+    const float tn = rows[8 * nx], cin = rows[8 * nx + 1];
+    const size_t slot = (size_t)B * 4 * HW;                       // elements of one ring slot = of the master
+    const int s0 = kr % 5;                                        // (kr >= 0 here: live and not prime, or 0)
+    float* hk = hist + (size_t)s0 * slot;
+    const float* h1 = hist + (size_t)((s0 + 4) % 5) * slot;
+    const float* h2 = hist + (size_t)((s0 + 3) % 5) * slot;
+    const float* h3 = hist + (size_t)((s0 + 2) % 5) * slot;
+    const float* h4 = hist + (size_t)((s0 + 1) % 5) * slot;
+    const half_t* epc = eps + (guided ? (size_t)B * HW * 4 : 0);  // the conditional half
+    half_t* y2 = y + slot;                                        // the second half of the guided input
+    const long stride = (long)gridDim.x * blockDim.x, t0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    // 8 pixels of one sample per item.  eps: four 16-byte loads per half; per channel two 16-byte loads / stores of x, two stores of the
+    // ring slot, two loads per history term in use and one 16-byte store of y per half
+    for (long i = t0; i < (long)B * hw8; i += stride) {
+      const long b = i / hw8;
+      const int p0 = (int)(i - b * hw8) * 8;
+      f16x8 eu[4], ec[4];
+      if (!prime) {
+        const f16x8* up = (const f16x8*)(eps + ((size_t)b * HW + p0) * 4);
+        const f16x8* cp = (const f16x8*)(epc + ((size_t)b * HW + p0) * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { eu[j] = up[j]; if (guided) ec[j] = cp[j]; }
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const size_t o = ((size_t)b * 4 + c) * HW + p0;
+        f32x4 xa = *(const f32x4*)(x + o), xb = *(const f32x4*)(x + o + 4);
+        if (!prime) {
+          f32x4 ea, eb;
+#pragma unroll
+          for (int p = 0; p < 8; ++p) {
+            const float u = (float)eu[p >> 1][(p & 1) * 4 + c];
+            const float e = guided ? __fmaf_rn(g, (float)ec[p >> 1][(p & 1) * 4 + c] - u, u) : u;
+            if (p < 4) ea[p] = e; else eb[p - 4] = e;
+          }
+          *(f32x4*)(hk + o) = ea; *(f32x4*)(hk + o + 4) = eb;
+#pragma unroll
+          for (int p = 0; p < 4; ++p) { xa[p] = cs * xa[p]; xb[p] = cs * xb[p]; }
+          if (w0 != 0.f) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) { xa[p] = __fmaf_rn(w0, ea[p], xa[p]); xb[p] = __fmaf_rn(w0, eb[p], xb[p]); }
+          }
+          const float wj[4] = {w1, w2, w3, w4};
+          const float* hj[4] = {h1, h2, h3, h4};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (wj[j] != 0.f) {
+              const f32x4 ha = *(const f32x4*)(hj[j] + o), hb = *(const f32x4*)(hj[j] + o + 4);
+#pragma unroll
+              for (int p = 0; p < 4; ++p) { xa[p] = __fmaf_rn(wj[j], ha[p], xa[p]); xb[p] = __fmaf_rn(wj[j], hb[p], xb[p]); }
+            }
+          }
+          *(f32x4*)(x + o) = xa; *(f32x4*)(x + o + 4) = xb;
+        }
+        f16x8 yo;
+#pragma unroll
+        for (int p = 0; p < 8; ++p) yo[p] = (_Float16)(cin * (p < 4 ? xa[p] : xb[p - 4]));
+        *(f16x8*)(y + o) = yo;
+        if (guided) *(f16x8*)(y2 + o) = yo;
+      }
+    }
+    // scalar tail: the pixels of every sample past its last whole group (all of them when a plane is no multiple of 16 bytes)
+    const int tail = HW - hw8 * 8;
+    for (long i = t0; i < (long)B * tail; i += stride) {
+      const long b = i / tail;
+      const int p = hw8 * 8 + (int)(i - b * tail);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const size_t o = ((size_t)b * 4 + c) * HW + p;
+        float v = x[o];
+        if (!prime) {
+          const size_t oe = ((size_t)b * HW + p) * 4 + c;
+          const float u = (float)eps[oe];
+          const float e = guided ? __fmaf_rn(g, (float)epc[oe] - u, u) : u;
+          hk[o] = e;
+          v = cs * v;
+          if (w0 != 0.f) v = __fmaf_rn(w0, e, v);
+          if (w1 != 0.f) v = __fmaf_rn(w1, h1[o], v);
+          if (w2 != 0.f) v = __fmaf_rn(w2, h2[o], v);
+          if (w3 != 0.f) v = __fmaf_rn(w3, h3[o], v);
+          if (w4 != 0.f) v = __fmaf_rn(w4, h4[o], v);
+          x[o] = v;
+        }
+        const half_t yv = (_Float16)(cin * v);
+        y[o] = yv;
+        if (guided) y2[o] = yv;
+      }
+    }
+    const int nt = guided ? 2 * B : B;
+    if (blockIdx.x == 0) for (int b = threadIdx.x; b < nt; b += blockDim.x) tbuf[b] = tn;
+  }
+  __syncthreads();                               // every wave of this workgroup has read `step`
+  if (threadIdx.x == 0) {
+    const unsigned t = atomicAdd((unsigned*)&steps[1], 1u);
+    if (t == gridDim.x - 1) { steps[1] = 0; if (live) steps[0] = prime ? 0 : k + 1; }
+  }
+}
+
+// B: samples of the master (the plans of a guided run have batch 2B).  The guided flag lives in the steps block on the device, so the size
+// check covers the larger (guided) case.
+hipError_t launch_guided_step(float* x, const half_t* eps, float* hist, half_t* y, float* tbuf, int* steps, int B, int H, int W, int prime,
+                              hipStream_t s) {
+  const long HW = (long)H * W;
+  if (B < 1 || H < 1 || W < 1 || (size_t)B * HW * 4 * 5 >= (1ull << 31)) return hipErrorInvalidValue;
+  if (!x || !hist || !y || !tbuf || !steps || (!prime && !eps)) return hipErrorInvalidValue;
+  // (the halves of a guided eps / y are B * HW * 4 elements apart: with HW % 8 == 0 they share the base's 16-byte alignment)
+  const bool al = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)eps | (uintptr_t)hist) & 15) == 0;
+  const int hw8 = (al && HW % 8 == 0) ? (int)(HW / 8) : 0;
+  const long items = (long)B * (hw8 ? hw8 : HW);
+  const unsigned grid = (unsigned)std::min<long>((items + 255) / 256, 256);
+  hipLaunchKernelGGL(guided_step_kernel, dim3(grid), dim3(256), 0, s, x, eps, hist, y, tbuf, steps, B, (int)HW, hw8, prime);
+  return hipGetLastError();
+}
+
 }  // namespace gdf

@@ -281,6 +281,11 @@ hipError_t launch_silu_vec(const float* x, float* out, long n, hipStream_t s);
 // scheduler update between two forwards of a latent trajectory (dit.hip): x' = c_sample x + c_eps eps on the fp32 master, the next forward's fp16
 // input c_in x' and timestep; the coefficient row is picked by the device-side step counter at the head of `steps`
 hipError_t launch_latent_step(float* x, const half_t* eps, half_t* y, float* tbuf, int* steps, int B, int H, int W, int prime, hipStream_t s);
+// the update between two forwards of a guided sampling run (dit.hip): e = e_u + g (e_c - e_u) into a ring of the last five, x' = c_sample x +
+// sum_j w_j e_{k-j} on the fp32 master (B samples), the next forward's fp16 input (both halves when guided) and timestep; row, guidance scale
+// and the guided flag come from the `steps` block on the device
+hipError_t launch_guided_step(float* x, const half_t* eps, float* hist, half_t* y, float* tbuf, int* steps, int B, int H, int W, int prime,
+                              hipStream_t s);
 // strided 2-D copy with cast to fp16: dst[r][c] = src[r][c]   (hook stores)
 // src_bf16: s16 holds bf16; sat: clamp to the fp16 range instead of producing +-inf (hook stores of the bf16 / MMDiT path)
 // s_lo > 0: the 16-bit source is a split pair (lo s_lo elements after hi in the row): dst = fp16(hi + lo)

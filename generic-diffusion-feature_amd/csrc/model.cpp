@@ -784,9 +784,38 @@ static hipError_t record_in_capture(hipEvent_t ev, hipStream_t) {
   return r ? record_event_node(*r, ev) : hipErrorInvalidValue;
 }
 
+// gdf_sample's state block (include/gdf.h), every part 256-byte aligned: the forwards' fp16 input (batch, 4, H, W), their timestep buffer
+// (batch), the history ring (5, batch, 4, H, W) fp32 — sized for the unguided case, where the master has `batch` samples — and, last because
+// its size follows n_rows, the guided_step block (8 header words + 8 floats per row).  `batch` is the plans' batch.
+struct SampleLayout { size_t lat16, tbuf, hist, steps, end; };
+static SampleLayout sample_layout(int batch, int H, int W, int n_rows) {
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t n = (size_t)batch * 4 * H * W;
+  SampleLayout L;
+  L.lat16 = 0;
+  L.tbuf = L.lat16 + up(n * 2);
+  L.hist = L.tbuf + up((size_t)batch * 4);
+  L.steps = L.hist + up(5 * n * 4);
+  L.end = L.steps + up(32 + (size_t)n_rows * 32);
+  return L;
+}
+size_t sample_state_bytes(int batch, int H, int W, int n_rows) {
+  if (batch < 1 || H < 1 || W < 1 || n_rows < 1 || n_rows > GDF_TRAJECTORY_MAX_STEPS) return 0;
+  return sample_layout(batch, H, W, n_rows).end;
+}
+
 // Trajectory calls (plan_trajectory binds the fp32 master): the scheduler update follows the op program — in the same graph when one is recorded.
 // Plans built with hooks never get here with a master bound, and their op program is untouched.
 static int traj_step(const Plan& P, const Bind& b, hipStream_t s) {
+  if (b.base[BUF_SAMPLE] && b.base[BUF_X32] && P.model->kind == 0) { // gdf_sample: either UNet plan, the state is the caller's block; f[0] = guided (part of the graph key)
+    const bool guided = b.f[0] != 0.f;
+    const SampleLayout L = sample_layout(P.batch, P.H, P.W, 0);
+    char* st = b.base[BUF_SAMPLE];
+    const hipError_t e = launch_guided_step((float*)b.base[BUF_X32], (const half_t*)b.base[BUF_NOISE], (float*)(st + L.hist), (half_t*)b.base[BUF_LAT],
+                                            (float*)b.base[BUF_T], (int*)(st + L.steps), guided ? P.batch / 2 : P.batch, P.H, P.W, 0, s);
+    if (e != hipSuccess) { set_error(std::string("op 'guided_step' failed: ") + hipGetErrorString(e)); return GDF_ERR_HIP; }
+    return GDF_OK;
+  }
   if (P.traj_off == NPOS || !b.base[BUF_X32]) return GDF_OK;
   const hipError_t e = launch_latent_step((float*)b.base[BUF_X32], (const half_t*)b.base[BUF_NOISE], (half_t*)b.base[BUF_LAT],
                                           (float*)b.base[BUF_T], (int*)b.ws(traj_layout(P).steps), P.batch, P.H, P.W, 0, s);
@@ -964,6 +993,82 @@ int plan_trajectory(Plan& P, const Model& m, float* x32, int n_steps, const floa
   if (e != hipSuccess) { set_error(std::string("op 'latent_step' failed: ") + hipGetErrorString(e)); return GDF_ERR_HIP; }
   for (int k = 0; k < n_steps; ++k) {
     const int rc = plan_run(P, b, s, nullptr, nullptr, nullptr, 0);
+    if (rc != GDF_OK) return rc;
+  }
+  return GDF_OK;
+}
+
+int plan_sample(Plan& A, Plan* Hk, float* x32, int n_rows, const float* table, float guidance, const void* ctx, const void* txt,
+                const float* tid, const int* capture_rows, int n_capture, void* const* hook_out, void* noise, void* state, void* ws_plain,
+                void* ws_hooked, hipStream_t s) {
+  const Model& m = *A.model;
+  if (m.kind != 0 || (Hk && Hk->model->kind != 0)) { set_error("gdf_sample needs UNet plans"); return GDF_ERR_STATE; }
+  if (m.n_set != (int)m.params.size()) { set_error("model weights incomplete"); return GDF_ERR_STATE; }
+  if (!A.requested.empty() || A.opts.early_exit || !A.writes_noise) {
+    set_error("gdf_sample: the plain plan must be created with zero hooks and early_exit off"); return GDF_ERR_STATE;
+  }
+  if (n_capture < 0 || (n_capture > 0 && (!Hk || !capture_rows))) { set_error("gdf_sample: capture rows without a hooked plan"); return GDF_ERR_ARG; }
+  if (Hk && n_capture > 0) {
+    if (Hk->model != A.model) { set_error("gdf_sample: the two plans belong to different models"); return GDF_ERR_ARG; }
+    if (Hk->batch != A.batch || Hk->H != A.H || Hk->W != A.W || Hk->n_ctx != A.n_ctx) {
+      set_error("gdf_sample: batch / latent size / text length of the two plans differ"); return GDF_ERR_ARG;
+    }
+    if (Hk->opts.early_exit || !Hk->writes_noise) { set_error("gdf_sample: the hooked plan must run the whole forward (early_exit off)"); return GDF_ERR_STATE; }
+    if (Hk->hooks.size() && !hook_out) { set_error("hook_out is null"); return GDF_ERR_ARG; }
+    if (!ws_hooked) { set_error("null input pointer"); return GDF_ERR_ARG; }
+  }
+  if (!x32 || !table || !ctx || !noise || !state || !ws_plain) { set_error("null input pointer"); return GDF_ERR_ARG; }
+  if (n_rows < 1 || n_rows > GDF_TRAJECTORY_MAX_STEPS) { set_error("n_rows must be in [1, GDF_TRAJECTORY_MAX_STEPS]"); return GDF_ERR_ARG; }
+  for (int c = 0; c < n_capture; ++c)
+    if (capture_rows[c] < 0 || capture_rows[c] >= n_rows || (c && capture_rows[c] <= capture_rows[c - 1])) {
+      set_error("gdf_sample: capture_rows must be ascending row indices in [0, n_rows)"); return GDF_ERR_ARG;
+    }
+  const bool guided = guidance > 1.f;
+  if (guided && (A.batch & 1)) { set_error("gdf_sample: a guided run needs plans of batch 2B"); return GDF_ERR_ARG; }
+  const int B = guided ? A.batch / 2 : A.batch;
+  const SampleLayout L = sample_layout(A.batch, A.H, A.W, n_rows);
+  char* st = (char*)state;
+  // the guided_step block, uploaded once: {step 0, ticket 0, n_rows, guided}, g, three unused words, and the coefficient rows of 8 floats
+  A.traj_host.resize(8 + 8 * (size_t)n_rows);
+  const int32_t hdr[4] = {0, 0, n_rows, guided ? 1 : 0};
+  const float g4[4] = {guidance, 0.f, 0.f, 0.f};
+  memcpy(A.traj_host.data(), hdr, sizeof hdr);
+  memcpy(A.traj_host.data() + 4, g4, sizeof g4);
+  memcpy(A.traj_host.data() + 8, table, 32 * (size_t)n_rows);
+  if (hipMemcpyAsync(st + L.steps, A.traj_host.data(), A.traj_host.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) {
+    set_error("gdf_sample: table upload failed"); return GDF_ERR_HIP;
+  }
+  Bind b;
+  b.base[BUF_WS] = (char*)ws_plain; b.base[BUF_WT] = (char*)m.weights; b.base[BUF_LAT] = st + L.lat16; b.base[BUF_T] = st + L.tbuf;
+  b.base[BUF_CTX] = (char*)ctx; b.base[BUF_TXT] = (char*)txt; b.base[BUF_TID] = (char*)tid; b.base[BUF_NOISE] = (char*)noise;
+  b.base[BUF_X32] = (char*)x32; b.base[BUF_SAMPLE] = st;
+  b.f[0] = guided ? 1.f : 0.f;
+  // the first forward's input and timestep (row 0); from here on every row is forward + update with the same arguments per plan
+  const hipError_t e = launch_guided_step(x32, nullptr, (float*)(st + L.hist), (half_t*)b.base[BUF_LAT], (float*)b.base[BUF_T],
+                                          (int*)(st + L.steps), B, A.H, A.W, 1, s);
+  if (e != hipSuccess) { set_error(std::string("op 'guided_step' failed: ") + hipGetErrorString(e)); return GDF_ERR_HIP; }
+  int c = 0;
+  for (int k = 0; k < n_rows; ++k) {
+    int rc;
+    if (c < n_capture && capture_rows[c] == k) {
+      Bind bh = b;
+      bh.base[BUF_WS] = (char*)ws_hooked;
+      bh.hooks = hook_out + (size_t)c * Hk->hooks.size();
+      ++c;
+      // A requested '*-map' id runs its attention layer on the map-materialising kernel, whose output differs in the last bits from the
+      // flash kernel's: such a plan only OBSERVES the row (no update bound), and the plain plan computes the noise_pred the run continues
+      // with — so the latents do not depend on which rows are captured.  Without map ids the hooked forward is the plain forward plus
+      // stores, and runs instead of it.
+      if (Hk->want_maps) {
+        bh.base[BUF_SAMPLE] = nullptr; bh.base[BUF_X32] = nullptr;
+        rc = plan_run(*Hk, bh, s, nullptr, nullptr, nullptr, 0);
+        if (rc == GDF_OK) rc = plan_run(A, b, s, nullptr, nullptr, nullptr, 0);
+      } else {
+        rc = plan_run(*Hk, bh, s, nullptr, nullptr, nullptr, 0);
+      }
+    } else {
+      rc = plan_run(A, b, s, nullptr, nullptr, nullptr, 0);
+    }
     if (rc != GDF_OK) return rc;
   }
   return GDF_OK;

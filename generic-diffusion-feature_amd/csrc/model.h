@@ -120,7 +120,9 @@ struct Model {
 // ---- plan ----------------------------------------------------------------------------------------
 // Flux reuses the slots: LAT = hidden_states, T = timestep, CTX = encoder_hidden_states, TXT = pooled_projections,
 // TID = guidance, NOISE = output; IDS_IMG / IDS_TXT = img_ids / txt_ids
-enum { BUF_WS = 0, BUF_WT, BUF_LAT, BUF_T, BUF_CTX, BUF_TXT, BUF_TID, BUF_NOISE, BUF_IDS_IMG, BUF_IDS_TXT, BUF_COUNT };
+// SAMPLE: the caller's state block of a guided sampling run (gdf_sample, sample_layout); a slot of its OWN, which only plan_sample fills —
+// the executor appends the guided update wherever it is set, so it must never alias an input of another front end
+enum { BUF_WS = 0, BUF_WT, BUF_LAT, BUF_T, BUF_CTX, BUF_TXT, BUF_TID, BUF_NOISE, BUF_IDS_IMG, BUF_IDS_TXT, BUF_SAMPLE, BUF_COUNT };
 enum { BUF_X32 = BUF_IDS_IMG };                 // UNet trajectory (gdf_trajectory): the caller's fp32 master latents; null on a plain forward
 enum { BUF_HOOK0 = 1 << 16 };                   // Ref.buf = BUF_HOOK0 + slot: the caller's hook buffer `slot` (an op's output IS the hook)
 struct Ref { int buf = BUF_WS; size_t off = 0; };
@@ -160,6 +162,7 @@ struct Plan {
   // rows (plan_trajectory).  NPOS: the plan cannot run a trajectory.
   size_t traj_off = NPOS;
   std::vector<float> traj_host;               // host image of the latent_step block of the last gdf_trajectory call (source of its upload)
+                                              // (gdf_sample: of the guided_step block, kept by the plain plan)
   std::vector<std::string> dry_ids;
   // live per-kernel timing (bench roofline): HIP events around every op of one kernel label
   std::vector<std::string> labels;
@@ -197,6 +200,11 @@ int plan_forward(Plan& P, const Model& m, const void* lat, const float* t, const
 // n_steps x (forward + latent_step) on one stream, nothing from the host in between (include/gdf.h gdf_trajectory)
 int plan_trajectory(Plan& P, const Model& m, float* x32, int n_steps, const float* table, const void* ctx, const void* txt, const float* tid,
                     void* noise, void* ws, hipStream_t s);
+// n_rows x (forward + guided_step) on one stream; `hooked` runs instead of `plain` on the capture rows (include/gdf.h gdf_sample)
+size_t sample_state_bytes(int batch, int H, int W, int n_rows);
+int plan_sample(Plan& plain, Plan* hooked, float* x32, int n_rows, const float* table, float guidance, const void* ctx, const void* txt,
+                const float* tid, const int* capture_rows, int n_capture, void* const* hook_out, void* noise, void* state, void* ws_plain,
+                void* ws_hooked, hipStream_t s);
 // executes the op program against an already filled binding table (shared by the UNet and Flux front ends)
 int plan_run(Plan& P, const Bind& b, hipStream_t s, float* ms, const char** names, double* flops, int cap);
 

@@ -476,4 +476,10 @@ int gdf_op_latent_step(float* latents_f32, const void* noise_pred, void* latents
                                 (hipStream_t)stream), "latent_step");
 }
 
+int gdf_op_guided_step(float* latents_f32, const void* noise_pred, float* history, void* latents_f16, float* timesteps, void* steps, int B,
+                       int H, int W, int prime, void* stream) {
+  return fin(launch_guided_step(latents_f32, (const half_t*)noise_pred, history, (half_t*)latents_f16, timesteps, (int*)steps, B, H, W, prime,
+                                (hipStream_t)stream), "guided_step");
+}
+
 }  // extern "C"

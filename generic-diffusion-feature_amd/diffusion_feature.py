@@ -7,7 +7,9 @@ Kept verbatim: constructor keywords (:27-40), `encode_prompt` (:149-206) 4-tuple
 execution order —, `preprocess_image`, `offload_prompt_encoder`, background-extraction accessors,
 the layer-selection config surface (JSON path | dict | None) and the version / dtype strings.
 In scope are the single-timestep path and, for the UNet versions, `use_ddim_inversion` (the inversion steps run as one device-resident
-trajectory, NativeUNet.trajectory); `denoising_from` and ControlNet are not.
+trajectory, NativeUNet.trajectory) and `generate`: a classifier-free-guided text-to-image run with background extraction — the hooked
+layers keep the features of the UNet calls named by `set_background_extraction` (reference generate_with_extraction.py) — as one
+device-resident run (NativeUNet.sample).  `denoising_from` and ControlNet are not.
 """
 import copy
 import os
@@ -339,6 +341,83 @@ class FeatureExtractor(nn.Module):
         table = ddim_inversion_table(self.pipe.scheduler, 100, t)
         return unet.trajectory(lat.float(), table, prompt_embeds.to(device), added_cond_kwargs.get("text_embeds"),
                                added_cond_kwargs.get("time_ids"), shared_ctx=prompts[0].shape[0] == 1)
+
+    def generate(self, prompts, batch_size, num_inference_steps=50, guidance_scale=7.5, latents=None, generator=None, output_type='latent'):
+        """A text-to-image run with background feature extraction (UNet versions): what the reference's generate_with_extraction.py gets from
+        a stock pipeline call after `set_background_extraction([1, 10, 20, ...])` — every requested layer keeps the features of the N-th,
+        M-th, ... UNet call — as ONE device-resident run: fp32 master latents, guidance and the scheduler step in one kernel between
+        forwards, a hook-less plan replayed from one graph for the calls nobody keeps (NativeUNet.sample).
+        prompts: encode_prompt()'s 4-tuple, repeated over the batch as extract() does.  guidance_scale > 1: the forwards have batch
+        2 * batch_size, [negative, positive]; <= 1: the unguided batch, as diffusers does.  latents: (B,4,h,w) standard-normal noise (drawn
+        with `generator` when None); it is scaled by the scheduler's init_noise_sigma.
+        Afterwards `get_background_extraction()` gives {id: {encounter: (2B|B, C, H, W)}} (encounters count UNet calls from 1; indices past
+        the last call never fire) and feature_store.feats[id]['count'] is the number of calls; with store_idx None the store holds
+        {id: tensor} of the last call, as the reference's overwrite per call leaves it.
+        Returns the final fp32 latents, or with output_type='pt' (latents, image (B,3,H,W) fp16 from the native VAE decoder)."""
+        if self.version == 'flux' or self.version.startswith('pixart'):
+            raise NotImplementedError("generate exists for the UNet versions ('1-5', '2-1', 'xl', 'pgv2') only: the device-resident sampler "
+                                      "drives pipe.unet")
+        if self.attention:
+            raise NotImplementedError("generate does not produce the aggregated attention=[...] feature: the reference aggregates its "
+                                      "AttentionStore once per extract() call, there is no per-encounter form to match")
+        if output_type not in ('latent', 'pt'):
+            raise ValueError("output_type must be 'latent' or 'pt'")
+        from components.feature_extractor import background_capture_rows
+        from components.models import sampling_table
+        unet = self.pipe.unet
+        if not hasattr(unet, 'sample'):
+            raise NotImplementedError("generate needs the native UNet (libgdf.so); this pipeline has none")
+        fs = self.feature_store
+        fs.reset()
+        device = self.device
+        guided = float(guidance_scale) > 1.0
+        xl = self.version in ('xl', 'pgv2')
+        prompt_embeds, negative, pooled, negative_pooled = prompts
+        ctx_pos = prompt_embeds.repeat(batch_size, 1, 1).to(device)                     # as extract() (:272)
+        ctx_neg = negative.repeat(batch_size, 1, 1).to(device) if guided else None
+        text_embeds = time_ids = None
+        if xl:
+            pos_p = pooled.repeat(batch_size, 1, 1).squeeze(1)
+            text_embeds = (torch.cat([negative_pooled.repeat(batch_size, 1, 1).squeeze(1), pos_p], 0) if guided else pos_p).to(device)
+            add_time_ids = _get_add_time_ids(self.pipe, (self.img_size, self.img_size), (0, 0), (self.img_size, self.img_size),
+                                             dtype=torch.float32)
+            time_ids = add_time_ids.to(device).repeat(text_embeds.shape[0], 1)
+
+        self.pipe.scheduler = copy.deepcopy(self.scheduler_backup)
+        rows, init_sigma = sampling_table(self.pipe.scheduler, num_inference_steps)
+        f = int(getattr(self.pipe, 'vae_scale_factor', 8))
+        shape = (batch_size, unet.cfg["in_channels"], self.img_size // f, self.img_size // f)
+        if latents is None:
+            gdev = generator.device if generator is not None else device
+            latents = torch.randn(shape, generator=generator, device=gdev, dtype=torch.float32)
+        elif tuple(latents.shape) != shape:
+            raise ValueError(f"latents must have shape {shape}")
+        x0 = latents.to(device, torch.float32) * init_sigma
+
+        known = set(unet.hook_names())
+        ids = [i for i in unet.requested_ids() if i in known]
+        active = fs.status != 'pause' and bool(ids)
+        caps = background_capture_rows(fs.store_idx, len(rows)) if active else []
+        x, captured = unet.sample(x0, rows, guidance_scale, ctx_pos, ctx_neg, text_embeds, time_ids, hook_ids=ids if caps else (),
+                                  capture_rows=caps)
+        # delivery through the store, so that feature_resize, the cross-k / cross-v drop and accept_all -> cpu apply as in extract()
+        dropped = lambda hid: 'cross-k' in hid or 'cross-v' in hid
+        for k in caps:
+            for hid, t in captured[k].items():
+                if fs.store_idx is not None and not dropped(hid):
+                    # the calls between two captures ran without hooks: the store's own counter catches up before it counts this one
+                    fs.feats.setdefault(hid, {'feat': {}, 'count': 0})['count'] = k
+                fs.store(t, hid)
+        if active and fs.store_idx is not None:
+            for hid in ids:
+                if not dropped(hid):
+                    fs.feats.setdefault(hid, {'feat': {}, 'count': 0})['count'] = len(rows)
+        if output_type == 'pt':
+            from components.models import native_vae_decoder
+            image = native_vae_decoder(self.pipe, device).decode(x, None, c_sample=1.0, c_eps=0.0,
+                                                                 scaling_factor=float(self.pipe.vae.config.scaling_factor))
+            return x, image
+        return x
 
     def set_background_extraction(self, idxs):
         self.feature_store.store_idx = idxs

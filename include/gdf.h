@@ -148,6 +148,38 @@ int gdf_forward(gdf_plan* p, const void* latents, const float* timesteps, const 
 int gdf_trajectory(gdf_plan* p, float* latents_f32, int n_steps, const float* table, const void* ctx,
                    const void* add_text_embeds, const float* add_time_ids, void* noise_pred_scratch, void* workspace, void* stream);
 
+/* A device-resident guided sampling run with hook capture at selected UNet calls: n_rows x (one forward + one update), the loop of a
+ * classifier-free-guided text-to-image pipeline whose hooked layers keep the features of the N-th, M-th, ... UNet call (the reference's
+ * generate_with_extraction.py with FeatureStore.store_idx, feature_extractor.py:68-76).
+ *   plain, hooked   two plans of the SAME model, batch and latent size: batch 2B when guided, B when not.  `plain` has zero hooks; `hooked`
+ *                   (may be NULL when n_capture == 0) carries the hooks; neither has early_exit.  `hooked` runs INSTEAD of `plain` on exactly
+ *                   the rows listed in capture_rows and writes that capture's own hook buffers.  (A hooked plan with a '*-map' id runs its
+ *                   attention layers on another kernel; on its rows it runs IN FRONT OF `plain`, for the hooks alone, so that the latents
+ *                   never depend on which rows are captured.)
+ *   latents_f32     (B,4,H,W) fp32 NCHW, in-out: the master copy of the latents, updated in place, never rounded to fp16 between steps
+ *   table           HOST pointer, n_rows rows of 8 floats {timestep, c_in, c_sample, w0, w1, w2, w3, w4}: forward k runs at timestep[k] on
+ *                   fp16(c_in[k] * x_k) (both halves when guided), then  e_k = e_u + guidance (e_c - e_u)  and
+ *                   x_{k+1} = c_sample[k] x_k + sum_{j<5} w_j[k] e_{k-j}  in fp32 (components/models.py sampling_table derives the rows of a
+ *                   scheduler); 1 <= n_rows <= GDF_TRAJECTORY_MAX_STEPS
+ *   guidance        > 1: guided, the inputs below are concatenated [negative, positive] (2B rows);  <= 1: unguided, B rows, e_k = noise_pred
+ *   capture_rows    n_capture ascending row indices in [0, n_rows);  hook_out[c * n_hooks(hooked) + i] = buffer of hook i for capture c
+ *   noise_pred_scratch   (2B|B,H,W,4) fp16, overwritten by every forward
+ *   state           device block of gdf_sample_state_bytes(plan batch, lat_h, lat_w, n_rows) bytes, 256-byte aligned, shared by both plans:
+ *                   the forwards' fp16 input, their timestep buffer, the steps block (gdf_op_guided_step, gdf_ops.h) and the fp32 ring of
+ *                   the last five combined noise predictions.  It belongs to neither plan's workspace
+ *   ws_plain, ws_hooked   >= gdf_plan_workspace_bytes of the respective plan
+ * The table is uploaded once per call; every forward and every update is enqueued on `stream` with no host synchronisation, no
+ * device-to-host read and no host-to-device copy between steps.  The update (csrc/dit.hip guided_step_kernel) picks its row with a
+ * device-side step counter: with graph replay enabled all plain rows replay ONE graph of forward ops + update; a capture row replays a
+ * graph of its own (keyed on its hook buffers) or runs eagerly. */
+size_t gdf_sample_state_bytes(int batch, int lat_h, int lat_w, int n_rows);
+int gdf_sample(gdf_plan* plain, gdf_plan* hooked, float* latents_f32, int n_rows, const float* table, float guidance, const void* ctx,
+               const void* add_text_embeds, const float* add_time_ids, const int* capture_rows, int n_capture, void* const* hook_out,
+               void* noise_pred_scratch, void* state, void* ws_plain, void* ws_hooked, void* stream);
+/* gdf_sample's update alone (documented in gdf_ops.h; declared here as well so that the Python binding table covers it) */
+int gdf_op_guided_step(float* latents_f32, const void* noise_pred, float* history, void* latents_f16, float* timesteps, void* steps, int B,
+                       int H, int W, int prime, void* stream);
+
 /* hipGraph replay: with enable != 0 every forward on a NON-default stream is served by one hipGraphLaunch of the plan's op
  * program, recorded once per distinct set of buffer addresses (workspace, inputs, hooks, outputs; LRU of 12) after one eager
  * warm-up forward.  The graph is BUILT with the graph API (kernel nodes in launch order, csrc/launch.h) — no stream is ever put into

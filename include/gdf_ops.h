@@ -306,6 +306,27 @@ int gdf_op_attention_joint(const void* q, int ldq, const void* k, int ldk, const
 int gdf_op_latent_step(float* latents_f32, const void* noise_pred, void* latents_f16, float* timesteps, void* steps, int B, int H, int W,
                        int prime, void* stream);
 
+/* One launch of guided_step_kernel: the update between two forwards of a guided sampling run (gdf_sample, gdf.h) — classifier-free
+ * guidance, a scheduler step with up to five model outputs of history, and the next forward's input.  B counts the samples of the master;
+ * a guided run's forwards have batch 2B.
+ *   latents_f32  (B, 4, H, W) fp32 NCHW master, updated in place
+ *   noise_pred   fp16 channels-last, read only: guided (2B, H, W, 4) with rows [0, B) unconditional and [B, 2B) conditional — the order of
+ *                torch.cat([negative, positive]) —, unguided (B, H, W, 4)
+ *   history      (5, B, 4, H, W) fp32: ring of the last five combined noise predictions; step k writes slot k mod 5
+ *   latents_f16  fp16 NCHW out, c_in[next] * x': guided (2B, 4, H, W), the same values in both halves; unguided (B, 4, H, W)
+ *   timesteps    fp32 out, 2B (guided) or B entries: the next row's timestep in every slot
+ *   steps        device block  int32 {step, ticket, n_rows, guided}, float g, three unused 32-bit words, then
+ *                float rows[n_rows][8] = {timestep, c_in, c_sample, w0, w1, w2, w3, w4};  ticket must be 0 before the first launch
+ * Step k, all in fp32:  e = e_u + g (e_c - e_u)  (unguided: e = noise_pred);  history[k mod 5] = e;
+ *                       x' = c_sample x + sum_{j<5} w_j history[(k - j) mod 5];  a term with w_j == 0 is skipped, so a slot no step has
+ * written is never read.  Row min(step + 1, n_rows - 1) supplies c_in and the timestep; then step + 1 is stored.  A step outside
+ * [0, n_rows) writes nothing.  prime = 1: no update (noise_pred and history untouched, the master not written), row 0 supplies c_in and
+ * the timestep, step becomes 0.
+ * Replaces, per UNet call, the guidance combine, `scheduler.step` and `scheduler.scale_model_input` of a text-to-image loop such as the
+ * reference's generate_with_extraction.py. */
+int gdf_op_guided_step(float* latents_f32, const void* noise_pred, float* history, void* latents_f16, float* timesteps, void* steps, int B,
+                       int H, int W, int prime, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
