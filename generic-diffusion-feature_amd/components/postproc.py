@@ -66,7 +66,9 @@ def resize_concat(feats, size=None):
 
 
 def avg_pool(feat, r):
-    """(B, C, H, W) fp16 -> (B, C, H/r, W/r) fp16 (channels-last storage for device tensors), mean over r x r windows."""
+    """(B, C, H, W) fp16 -> (B, C, H // r, W // r) fp16 (channels-last storage for device tensors): F.adaptive_avg_pool2d to that size.
+    Where r divides H and W that is the mean over r x r windows; otherwise output row o averages the source rows
+    [floor(o H / OH), ceil((o + 1) H / OH)) (columns likewise), on the device and on the host alike."""
     if r <= 1:
         return feat
     tgt = (feat.shape[2] // r, feat.shape[3] // r)

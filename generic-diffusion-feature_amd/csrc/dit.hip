@@ -356,7 +356,7 @@ __global__ void vae_finish_kernel(const float* h, int HW, int L, const half_t* w
   for (int c = 0; c < L2; ++c) hv[c] = h[(size_t)i * L2 + c];
   for (int o = 0; o < L2; ++o) {
     if (wq) {
-      float a = bq[o];
+      float a = bq ? bq[o] : 0.f;
       for (int c = 0; c < L2; ++c) a += (float)wq[o * L2 + c] * hv[c];
       m[o] = a;
     } else {
@@ -487,7 +487,12 @@ hipError_t launch_relayout_rows_padk(const void* src, int src_f32, half_t* dst, 
 
 __global__ void silu_vec_kernel(const float* x, float* out, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) { const float v = x[i]; out[i] = v / (1.0f + expf(-v)); }
+  if (i < n) {
+    const float v = x[i];
+    const float d = 1.0f + expf(-v);
+    // v < -88.7: expf(-v) overflows and v / inf would flush a normal number (silu(-90) = -7.4e-38) to -0; v * e^v is the same quotient there
+    out[i] = d < __builtin_inff() ? v / d : v * expf(v);
+  }
 }
 
 hipError_t launch_silu_vec(const float* x, float* out, long n, hipStream_t s) {

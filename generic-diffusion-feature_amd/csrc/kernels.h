@@ -37,7 +37,8 @@ __device__ __forceinline__ half_t f32_to_e16(float v, int bf) {          // roun
   return bf ? __builtin_bit_cast(half_t, (__bf16)v) : (half_t)v;
 }
 __device__ __forceinline__ half_t f32_to_f16_sat(float v) {              // fp16 with saturation instead of +-inf (NaN stays NaN)
-  return (half_t)__builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f);
+  // (v_med3_f32 alone answers min3 for a NaN operand, i.e. -65504: the NaN is passed round it)
+  return (half_t)(v != v ? v : __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f));
 }
 #endif
 
@@ -255,7 +256,7 @@ hipError_t launch_rope_table(const float* ids, int S, int n_axes, const int* axe
                              float* sin_t, int row0, hipStream_t s);
 // in-place row softmax of fp16 scores: x[r][0..n) = softmax(scale * x[r][0..n)) (fp32 math), rows of ld halves
 hipError_t launch_softmax_rows(half_t* x, int ld, int R, int n, float scale, hipStream_t s);
-// VAE tail: moments = quant_conv(h) (1x1, [2L][2L] fp16 weights, fp32 bias; wq == NULL: identity), mean / logvar split,
+// VAE tail: moments = quant_conv(h) (1x1, [2L][2L] fp16 weights, fp32 bias or NULL = 0; wq == NULL: identity), mean / logvar split,
 // logvar clamp(-30, 20), z = mean + exp(0.5 logvar) * eps (eps == NULL: mode), lat = scaling * z,
 // out = in_scale * (noise_a * lat + noise_b * noise) (noise == NULL: no noise) -> NCHW fp16 (B, L, H, W).  h: fp32 [B*HW][2L].
 hipError_t launch_vae_finish(const float* h, int B, int HW, int L, const half_t* wq, const float* bq, const half_t* eps,
@@ -311,7 +312,8 @@ hipError_t launch_small_linear(const float* x, int ldx, int M, int K, const half
 // [coff, coff + C) of out (B, Ctot, S, S) fp16 contiguous
 hipError_t launch_resize_concat(const half_t* s16, const float* s32, long sb, long sc, long sy, long sx, int B, int C, int H, int W,
                                 half_t* out, int Ctot, int coff, int S, hipStream_t s);
-// r x r mean of a channels-last hook (B,C,H,W; strides sb, 1, sy, sx) -> (B, H/r, W/r, C) fp16
+// adaptive_avg_pool2d to (H/r, W/r) of a channels-last hook (B,C,H,W; strides sb, 1, sy, sx) -> (B, H/r, W/r, C) fp16: the r x r mean
+// where r divides H and W, ATen's longer windows [floor(o H / OH), ceil((o + 1) H / OH)) otherwise
 hipError_t launch_avg_pool(const half_t* src, long sb, long sy, long sx, int B, int C, int H, int W, int r, half_t* out, hipStream_t s);
 // mean over heads and over n <= 32 maps (B, heads, Q, K) fp16 -> (B, Q, K) fp32
 hipError_t launch_maps_mean(const half_t* const* maps, int n, int B, int heads, int Q, int K, float* out, hipStream_t s);

@@ -499,7 +499,9 @@ __global__ void sinusoid_kernel(const float* t, int n_per_row, int dim, float* o
   const int ti = (i / dim) % n_per_row;
   const int b = i / (dim * n_per_row);
   const int f = j < half ? j : j - half;
-  const float freq = expf(-9.210340371976184f * (float)f / (float)half);   // ln(10000)
+  // the frequency is rounded ONCE (float64 exponent and exp): in fp32 the three roundings of the exponent -ln(10000) f / half (magnitude up to 9.2)
+  // become a relative error of the frequency of up to 2^-19.5, i.e. 2.6 / 2^21 of the argument at timestep * 1000 (the MMDiT's scale)
+  const float freq = (float)exp(-9.210340371976184 * (double)f / (double)half);   // ln(10000)
   const float arg = t[b * n_per_row + ti] * tscale * freq;
   float v = j < half ? cosf(arg) : sinf(arg);
   if (round_f16) v = (float)(_Float16)v;

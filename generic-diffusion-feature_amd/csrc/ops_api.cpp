@@ -358,6 +358,56 @@ int gdf_op_copy2d(const void* s16, const float* s32, int lds, void* dst, int ldd
   return fin(launch_copy2d((const half_t*)s16, s32, lds, (half_t*)dst, ldd, R, C, (hipStream_t)stream), "copy2d");
 }
 
+int gdf_op_copy2d_ex(const void* s16, const float* s32, int lds, void* dst, int ldd, int R, int C, int src_bf16, int sat, int s_lo, float scale,
+                     void* stream) {
+  return fin(launch_copy2d((const half_t*)s16, s32, lds, (half_t*)dst, ldd, R, C, (hipStream_t)stream, src_bf16, sat, s_lo, scale), "copy2d_ex");
+}
+
+// ---- the glue kernels one at a time (tests/test_gpu_glue.py) ----
+int gdf_op_sinusoid(const float* t, int B, int n_per_row, int dim, float* out, int ldo, int col_off, int round_f16, float tscale, void* stream) {
+  return fin(launch_sinusoid(t, B, n_per_row, dim, out, ldo, col_off, round_f16, (hipStream_t)stream, tscale), "sinusoid");
+}
+int gdf_op_widen(const void* x, int src_bf16, int B, int n, float* out, int ldo, int col_off, void* stream) {
+  return fin(launch_widen((const half_t*)x, B, n, out, ldo, col_off, (hipStream_t)stream, src_bf16), "widen");
+}
+int gdf_op_silu_vec(const float* x, float* out, long n, void* stream) {
+  return fin(launch_silu_vec(x, out, n, (hipStream_t)stream), "silu_vec");
+}
+int gdf_op_add_table(const float* table, const float* vec, int ldvec, int period, int B, long n, float* out, long ldo, void* stream) {
+  return fin(launch_add_table(table, vec, ldvec, period, B, n, out, ldo, (hipStream_t)stream), "add_table");
+}
+int gdf_op_pack_latents(const void* x_nchw, int B, int Cin, int H, int W, void* nhwc8, void* hook_nhwc, void* stream) {
+  return fin(launch_pack_latents((const half_t*)x_nchw, B, Cin, H, W, (half_t*)nhwc8, (half_t*)hook_nhwc, (hipStream_t)stream), "pack_latents");
+}
+int gdf_op_patchify(const void* x_nchw, int B, int Cin, int H, int W, int p, int kpad, void* out, void* stream) {
+  return fin(launch_patchify((const half_t*)x_nchw, B, Cin, H, W, p, kpad, (half_t*)out, (hipStream_t)stream), "patchify");
+}
+int gdf_op_unpatchify(const void* x, int B, int Cout, int gh, int gw, int p, void* out_nchw, void* stream) {
+  return fin(launch_unpatchify((const half_t*)x, B, Cout, gh, gw, p, (half_t*)out_nchw, (hipStream_t)stream), "unpatchify");
+}
+int gdf_op_vae_finish(const float* h, int B, int HW, int L, const void* wq, const float* bq, const void* eps, const void* noise, float scaling,
+                      float noise_a, float noise_b, float in_scale, void* out, void* stream) {
+  return fin(launch_vae_finish(h, B, HW, L, (const half_t*)wq, bq, (const half_t*)eps, (const half_t*)noise, scaling, noise_a, noise_b, in_scale,
+                               (half_t*)out, (hipStream_t)stream), "vae_finish");
+}
+int gdf_op_vae_dec_prepare(const void* latents, const void* noise_pred, int B, int HW, int L, float c_sample, float c_eps, float inv_scaling,
+                           const void* wq, const float* bq, void* nhwc8, void* stream) {
+  return fin(launch_vae_dec_prepare((const half_t*)latents, (const half_t*)noise_pred, B, HW, L, c_sample, c_eps, inv_scaling, (const half_t*)wq, bq,
+                                    (half_t*)nhwc8, (hipStream_t)stream), "vae_dec_prepare");
+}
+int gdf_op_relayout_rows_padk(const void* src, int src_f32, void* dst, int R, int ksrc, int kdst, void* stream) {
+  return fin(launch_relayout_rows_padk(src, src_f32, (half_t*)dst, R, ksrc, kdst, (hipStream_t)stream), "relayout_rows_padk");
+}
+int gdf_op_relayout_conv(const void* src, int src_dtype, void* dst, int O, int I, int T, int ipad, int tpad, int cblk, void* stream) {
+  return fin(launch_relayout_conv(src, src_dtype, (half_t*)dst, O, I, T, ipad, tpad, (hipStream_t)stream, cblk), "relayout_conv");
+}
+int gdf_op_relayout_rows(const void* src, int src_dtype, void* dst, int R, int K, int row_off, int geglu, int dst_bf16, void* stream) {
+  return fin(launch_relayout_rows(src, src_dtype, (half_t*)dst, R, K, row_off, geglu, (hipStream_t)stream, dst_bf16), "relayout_rows");
+}
+int gdf_op_relayout_vec(const void* src, int src_dtype, float* dst, int R, int row_off, int geglu, void* stream) {
+  return fin(launch_relayout_vec(src, src_dtype, dst, R, row_off, geglu, (hipStream_t)stream), "relayout_vec");
+}
+
 int gdf_op_relayout_conv3(const void* w, void* dst, int O, int I, void* stream) {
   return fin(launch_relayout_conv(w, 0, (half_t*)dst, O, I, 9, I, 9, (hipStream_t)stream, 64), "relayout_conv3");
 }
@@ -371,6 +421,11 @@ int gdf_op_relayout_geglu(const void* w, const float* bias, void* w_dst, float* 
 int gdf_op_small_linear(const float* x, int ldx, int M, int K, const void* W, const float* bias, int N, int silu_in,
                         int accumulate, float* out, int ldo, void* stream) {
   return fin(launch_small_linear(x, ldx, M, K, (const half_t*)W, bias, N, silu_in, accumulate, out, ldo, (hipStream_t)stream), "small_linear");
+}
+
+int gdf_op_small_linear_ex(const float* x, int ldx, int M, int K, const void* W, int w_bf16, const float* bias, int N, int silu_in,
+                           int accumulate, float* out, int ldo, void* stream) {
+  return fin(launch_small_linear(x, ldx, M, K, (const half_t*)W, bias, N, silu_in, accumulate, out, ldo, (hipStream_t)stream, w_bf16), "small_linear_ex");
 }
 
 int gdf_op_softmax_rows(void* x, int ld, int R, int n, float scale, void* stream) {

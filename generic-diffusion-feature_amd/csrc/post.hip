@@ -64,9 +64,11 @@ hipError_t launch_resize_concat(const half_t* s16, const float* s32, long sb, lo
   return hipGetLastError();
 }
 
-// r x r mean of a channels-last hook: src (B, C, H, W) fp16 with strides (sb, 1, sy, sx) -> out (B, H/r, W/r, C) fp16
-// (returned to the caller as the (B, C, H/r, W/r) channels-last view, like every hook); fp32 accumulation, 16 B per lane
-__global__ __launch_bounds__(256) void avg_pool_kernel(const half_t* src, long sb, long sy, long sx, int C, int OH, int OW, int r,
+// `feature_resize`: F.adaptive_avg_pool2d to (OH, OW) = (H / r, W / r) of a channels-last hook: src (B, C, H, W) fp16 with strides
+// (sb, 1, sy, sx) -> out (B, OH, OW, C) fp16 (returned to the caller as the (B, C, OH, OW) channels-last view, like every hook); fp32
+// accumulation, 16 B per lane.  ATen's windows: output row o averages source rows [floor(o H / OH), ceil((o + 1) H / OH)) — exactly
+// r rows where r divides H, otherwise longer windows that may overlap and together cover every row; columns likewise.
+__global__ __launch_bounds__(256) void avg_pool_kernel(const half_t* src, long sb, long sy, long sx, int C, int H, int W, int OH, int OW,
                                                        half_t* out, long total) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;      // (b, oy, ox, c8)
   if (i >= total) return;
@@ -74,14 +76,16 @@ __global__ __launch_bounds__(256) void avg_pool_kernel(const half_t* src, long s
   const int c = (int)(i % C8) * 8;
   const int ox = (int)((i / C8) % OW), oy = (int)((i / ((long)C8 * OW)) % OH);
   const long b = i / ((long)C8 * OW * OH);
+  const int y0 = (int)((long)oy * H / OH), y1 = (int)((((long)oy + 1) * H + OH - 1) / OH);     // y1 <= H, x1 <= W
+  const int x0 = (int)((long)ox * W / OW), x1 = (int)((((long)ox + 1) * W + OW - 1) / OW);
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int dy = 0; dy < r; ++dy)
-    for (int dx = 0; dx < r; ++dx) {
-      const f16x8 v = *(const f16x8*)(src + b * sb + (long)(oy * r + dy) * sy + (long)(ox * r + dx) * sx + c);
+  for (int y = y0; y < y1; ++y)
+    for (int x = x0; x < x1; ++x) {
+      const f16x8 v = *(const f16x8*)(src + b * sb + (long)y * sy + (long)x * sx + c);
 #pragma unroll
       for (int e = 0; e < 8; ++e) acc[e] += (float)v[e];
     }
-  const float inv = 1.0f / (float)(r * r);
+  const float inv = 1.0f / (float)((y1 - y0) * (x1 - x0));
   f16x8 o;
 #pragma unroll
   for (int e = 0; e < 8; ++e) o[e] = (_Float16)(acc[e] * inv);
@@ -93,7 +97,7 @@ hipError_t launch_avg_pool(const half_t* src, long sb, long sy, long sx, int B, 
   const int OH = H / r, OW = W / r;
   const long total = (long)B * OH * OW * (C / 8);
   if (total <= 0) return hipSuccess;
-  hipLaunchKernelGGL(avg_pool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, sb, sy, sx, C, OH, OW, r, out, total);
+  hipLaunchKernelGGL(avg_pool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, sb, sy, sx, C, H, W, OH, OW, out, total);
   return hipGetLastError();
 }
 

@@ -210,6 +210,57 @@ int gdf_op_layernorm(const void* x16, const float* x32, int ld, int R, int C, fl
 /* strided fp16/fp32 -> fp16 2-D copy (the hook-store kernel). */
 int gdf_op_copy2d(const void* s16, const float* s32, int lds, void* dst, int ldd, int R, int C, void* stream);
 
+/* The same kernel with every argument of its launcher: src_bf16: s16 holds bf16; sat: the fp16 store saturates at +-65504 instead of
+ * overflowing to +-inf (NaN stays NaN); s_lo > 0: the 16-bit source is a split (hi, lo) pair, lo s_lo elements after hi in the row, and
+ * dst = fp16(hi + lo); dst = fp16(scale * src).  Any of these selects the MMDiT hook form copy2d_kernel<true>.  C, lds and ldd all
+ * multiples of 8: 16-byte lanes; otherwise one element per lane. */
+int gdf_op_copy2d_ex(const void* s16, const float* s32, int lds, void* dst, int ldd, int R, int C, int src_bf16, int sat, int s_lo, float scale,
+                     void* stream);
+
+/* ---- embedding, packing, patch-layout and VAE head / tail kernels (csrc/norm.hip, csrc/dit.hip), one launch each ---- */
+
+/* get_timestep_embedding(flip_sin_to_cos = True, downscale_freq_shift = 0): t fp32 [B][n_per_row] ->
+ * out[b][col_off + i * dim + j] = j < dim / 2 ? cos(a) : sin(a), a = t[b][i] * tscale * exp(-ln(10000) * (j mod dim / 2) / (dim / 2)),
+ * fp32 rows of ldo; round_f16: every value rounded to fp16 first (the reference's fp16 embedding). */
+int gdf_op_sinusoid(const float* t, int B, int n_per_row, int dim, float* out, int ldo, int col_off, int round_f16, float tscale, void* stream);
+/* out[b][col_off + j] = x[b][j]: 16-bit rows [B][n] (fp16, src_bf16 = 1: bf16) widened into fp32 rows of ldo. */
+int gdf_op_widen(const void* x, int src_bf16, int B, int n, float* out, int ldo, int col_off, void* stream);
+/* out[i] = x[i] / (1 + exp(-x[i])), fp32. */
+int gdf_op_silu_vec(const float* x, float* out, long n, void* stream);
+/* out[b][i] = table[i] + vec[b][i mod period], fp32; vec rows of ldvec, out rows of ldo (ada_norm_single's scale_shift_table). */
+int gdf_op_add_table(const float* table, const float* vec, int ldvec, int period, int B, long n, float* out, long ldo, void* stream);
+/* latents NCHW fp16 (B, Cin <= 8, H, W) -> NHWC pixels of 8 fp16 channels (channels from Cin up zero: the conv_in operand) and, if
+ * hook_nhwc != NULL, the plain NHWC copy (B, H, W, Cin). */
+int gdf_op_pack_latents(const void* x_nchw, int B, int Cin, int H, int W, void* nhwc8, void* hook_nhwc, void* stream);
+/* latents NCHW fp16 (B, Cin, H, W) -> patch rows [B * (H / p) * (W / p)][kpad] fp16, column (c * p + py) * p + px (the Conv2d weight
+ * order), columns from Cin * p * p up zero.  H % p == 0, W % p == 0, Cin * p * p <= kpad. */
+int gdf_op_patchify(const void* x_nchw, int B, int Cin, int H, int W, int p, int kpad, void* out, void* stream);
+/* token rows [B * gh * gw][p * p * Cout] fp16, column (py * p + px) * Cout + c -> NCHW fp16 (B, Cout, gh * p, gw * p)
+ * (the `nhwpqc -> nchpwq` einsum of transformer_2d.py:563-570). */
+int gdf_op_unpatchify(const void* x, int B, int Cout, int gh, int gw, int p, void* out_nchw, void* stream);
+/* VAE encoder tail: moments = quant_conv(h) (1x1: wq fp16 [2L][2L], bq fp32 [2L] or NULL = 0; wq == NULL: identity) of h fp32 [B * HW][2L],
+ * (mean | logvar) split, z = mean + exp(0.5 * clamp(logvar, -30, 20)) * eps (eps == NULL: the mode), lat = scaling * z,
+ * out = in_scale * (noise_a * lat + noise_b * noise) (noise == NULL: in_scale * lat) -> NCHW fp16 (B, L, HW); eps, noise NCHW fp16.  L <= 8. */
+int gdf_op_vae_finish(const float* h, int B, int HW, int L, const void* wq, const float* bq, const void* eps, const void* noise, float scaling,
+                      float noise_a, float noise_b, float in_scale, void* out, void* stream);
+/* VAE decoder head: z = (c_sample * latents + c_eps * noise_pred) * inv_scaling (noise_pred == NULL: no second term), y = post_quant_conv(z)
+ * (1x1: wq fp16 [L][L], bq fp32 [L] or NULL = 0; wq == NULL: identity) -> NHWC pixels of 8 fp16 channels, channels from L up zero.
+ * latents, noise_pred NCHW fp16 (B, L, HW).  L <= 8. */
+int gdf_op_vae_dec_prepare(const void* latents, const void* noise_pred, int B, int HW, int L, float c_sample, float c_eps, float inv_scaling,
+                           const void* wq, const float* bq, void* nhwc8, void* stream);
+
+/* ---- weight re-layouts of model load time; src_dtype: 0 fp16, 1 fp32, 2 bf16 ---- */
+/* dst[r][0..kdst) = fp16(src[r][0..ksrc)) zero padded; src fp16 or fp32 (src_f32). */
+int gdf_op_relayout_rows_padk(const void* src, int src_f32, void* dst, int R, int ksrc, int kdst, void* stream);
+/* OIHW weights src[O][I][T] (T = kh * kw) -> fp16 dst[O][tpad][ipad] (cblk = 0: dst[o][t][i] = src[o][i][t]) or, cblk > 0,
+ * dst[O][ipad / cblk][tpad][cblk] (dst[o][i / cblk][t][i % cblk]); i >= I and t >= T are zero.  ipad % cblk == 0. */
+int gdf_op_relayout_conv(const void* src, int src_dtype, void* dst, int O, int I, int T, int ipad, int tpad, int cblk, void* stream);
+/* dst[map(r)][k] = e16(src[r][k]), r < R, rows of K; geglu = 0: map(r) = r + row_off; geglu = g: the [g h | g gate] interleave of the
+ * [h rows | gate rows] matrix (R / 2 a multiple of g; row_off is not used).  dst fp16, or bf16 (dst_bf16), rounded to nearest even. */
+int gdf_op_relayout_rows(const void* src, int src_dtype, void* dst, int R, int K, int row_off, int geglu, int dst_bf16, void* stream);
+/* the same row mapping for a vector, to fp32: dst[map(r)] = src[r]. */
+int gdf_op_relayout_vec(const void* src, int src_dtype, float* dst, int R, int row_off, int geglu, void* stream);
+
 /* weight re-layout helpers used by the tests: OIHW -> OHWI, GEGLU row interleave. */
 int gdf_op_relayout_conv3(const void* w_oihw_f16, void* dst, int O, int I, void* stream);
 int gdf_op_relayout_geglu(const void* w_f16, const float* bias, void* w_dst, float* bias_dst, int R, int K, int group /*16*/, void* stream);
@@ -219,6 +270,10 @@ int gdf_op_relayout_geglu(const void* w_f16, const float* bias, void* w_dst, flo
  * `linear(silu(temb))`, stacked over all blocks: N = 1.06 M columns -> LDS-staged wide kernel).                          */
 int gdf_op_small_linear(const float* x, int ldx, int M, int K, const void* W, const float* bias, int N, int silu_in,
                         int accumulate, float* out, int ldo, void* stream);
+
+/* The same launch with the weights' storage type: w_bf16 = 1: W holds bf16 (the MMDiT's bf16 models). */
+int gdf_op_small_linear_ex(const float* x, int ldx, int M, int K, const void* W, int w_bf16, const float* bias, int N, int silu_in,
+                           int accumulate, float* out, int ldo, void* stream);
 
 /* in-place row softmax of fp16 scores: x[r][0..n) = softmax(scale * x[r][0..n)) with fp32 math (VAE mid-block attention,
  * attention_processor.py:3311-3313 run as explicit GEMMs; n <= 16384, n % 8 == 0). */
@@ -234,8 +289,10 @@ int gdf_op_sincos_pos_embed(float* out, int C, int gh, int gw, int base_size, fl
  * [coff, coff + C) of out (B, Ctot, S, S) fp16 contiguous; one call per layer performs F.interpolate + torch.cat(dim=1). */
 int gdf_op_resize_concat(const void* src, int src_f32, long sb, long sc, long sy, long sx, int B, int C, int H, int W, void* out,
                          int Ctot, int coff, int S, void* stream);
-/* `feature_resize` (components/feature_extractor.py:51-53): r x r mean (adaptive_avg_pool2d to (H/r, W/r)) of a channels-last
- * hook (strides sb, 1, sy, sx; C % 8 == 0) -> (B, H/r, W/r, C) fp16, fp32 accumulation. */
+/* `feature_resize` (components/feature_extractor.py:51-53): adaptive_avg_pool2d to (OH, OW) = (H / r, W / r) (integer division) of a
+ * channels-last hook (strides sb, 1, sy, sx; C % 8 == 0) -> (B, OH, OW, C) fp16, fp32 accumulation.  Output row o averages source rows
+ * [floor(o H / OH), ceil((o + 1) H / OH)), columns likewise: the r x r window where r divides the size, otherwise longer windows that may
+ * overlap and cover every row and column.  H < r or W < r is an error. */
 int gdf_op_avg_pool(const void* src, long sb, long sy, long sx, int B, int C, int H, int W, int r, void* out, void* stream);
 /* aggregated `attn` feature (components/attention.py:238-244, 141-161): mean over heads (rounded to fp16 like the
  * reference's `attention_probs.mean(1)`), then mean over the n <= 32 maps (B, heads, Q, K) fp16 of one (category, size)

@@ -62,11 +62,29 @@ OPS = {
     "gdf_op_conv3x3_gn_info": (C.c_char_p, [ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(ci)]),
     "gdf_op_layernorm": (ci, [vp, vp, ci, ci, ci, fp, vp, vp, vp, vp]),
     "gdf_op_copy2d": (ci, [vp, vp, ci, vp, ci, ci, ci, vp]),
+    "gdf_op_copy2d_ex": (ci, [vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, fp, vp]),
+    "gdf_op_sinusoid": (ci, [vp, ci, ci, ci, vp, ci, ci, ci, fp, vp]),
+    "gdf_op_widen": (ci, [vp, ci, ci, ci, vp, ci, ci, vp]),
+    "gdf_op_silu_vec": (ci, [vp, vp, C.c_long, vp]),
+    "gdf_op_add_table": (ci, [vp, vp, ci, ci, ci, C.c_long, vp, C.c_long, vp]),
+    "gdf_op_pack_latents": (ci, [vp, ci, ci, ci, ci, vp, vp, vp]),
+    "gdf_op_patchify": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp]),
+    "gdf_op_unpatchify": (ci, [vp, ci, ci, ci, ci, ci, vp, vp]),
+    "gdf_op_vae_finish": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, fp, fp, fp, fp, vp, vp]),
+    "gdf_op_vae_dec_prepare": (ci, [vp, vp, ci, ci, ci, fp, fp, fp, vp, vp, vp, vp]),
+    "gdf_op_relayout_rows_padk": (ci, [vp, ci, vp, ci, ci, ci, vp]),
+    "gdf_op_relayout_conv": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, ci, vp]),
+    "gdf_op_relayout_rows": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, vp]),
+    "gdf_op_relayout_vec": (ci, [vp, ci, vp, ci, ci, ci, vp]),
     "gdf_op_relayout_conv3": (ci, [vp, vp, ci, ci, vp]),
     "gdf_op_relayout_geglu": (ci, [vp, vp, vp, vp, ci, ci, ci, vp]),
     "gdf_op_sincos_pos_embed": (ci, [vp, ci, ci, ci, ci, fp, vp]),
     "gdf_op_softmax_rows": (ci, [vp, ci, ci, ci, fp, vp]),
     "gdf_op_small_linear": (ci, [vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, vp]),
+    "gdf_op_small_linear_ex": (ci, [vp, ci, ci, ci, vp, ci, vp, ci, ci, ci, vp, ci, vp]),
+    "gdf_op_resize_concat": (ci, [vp, ci, C.c_long, C.c_long, C.c_long, C.c_long, ci, ci, ci, ci, vp, ci, ci, ci, vp]),
+    "gdf_op_avg_pool": (ci, [vp, C.c_long, C.c_long, C.c_long, ci, ci, ci, ci, ci, vp, vp]),
+    "gdf_op_maps_mean": (ci, [C.POINTER(vp), ci, ci, ci, ci, ci, vp, vp]),
     "gdf_op_set_e16": (ci, [ci]),
     "gdf_op_gemm_dit": (ci, [vp, ci, vp, vp, ci, vp, ci, ci, ci, ci, ci, vp, ci, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp]),
     "gdf_op_quant_rows_fp8": (ci, [vp, ci, ci, ci, ci, vp, ci, vp, vp]),
