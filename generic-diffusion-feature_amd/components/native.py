@@ -64,6 +64,14 @@ SIGNATURES = {
     "gdf_plan_hook_copied": (C.c_int, [C.c_void_p, C.c_int]),
     "gdf_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdf_forward_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdf_plan_residual_count": (C.c_int, [C.c_void_p]),
+    "gdf_plan_residual_bytes": (C.c_size_t, [C.c_void_p]),
+    "gdf_plan_residual_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int64 * 4)]),
+    "gdf_residual_count": (C.c_int, [C.POINTER(ArchDesc)]),
+    "gdf_residual_bytes": (C.c_size_t, [C.POINTER(ArchDesc), C.c_int, C.c_int, C.c_int]),
+    "gdf_residual_info": (C.c_int, [C.POINTER(ArchDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int64 * 4)]),
     "gdf_plan_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_int]),
@@ -259,6 +267,19 @@ def arch_desc(cfg):
     a.addition_time_embed_dim = cfg["addition_time_embed_dim"]
     a.add_in_dim = cfg["add_in_dim"]
     return a
+
+
+def residual_layout(cfg, batch, lat_h, lat_w):
+    """The ControlNet residual block of architecture `cfg` at (batch, lat_h, lat_w) (include/gdf.h, gdf_forward_res) ->
+    ([(byte offset, (B, C, H, W))] with the mid block's tensor last, bytes of the block).  Host arithmetic: needs the library, no GPU."""
+    lib = load_library()
+    a = arch_desc(cfg)
+    out = []
+    for i in range(lib.gdf_residual_count(C.byref(a))):
+        off, shape = C.c_size_t(), (C.c_int64 * 4)()
+        _check(lib.gdf_residual_info(C.byref(a), batch, lat_h, lat_w, i, C.byref(off), C.byref(shape)), "residual_info")
+        out.append((off.value, tuple(shape)))
+    return out, lib.gdf_residual_bytes(C.byref(a), batch, lat_h, lat_w)
 
 
 def config_from_diffusers(uc):
@@ -819,10 +840,10 @@ class NativeUNet(_NativeModel):
         return ".norm" in name or name.startswith("conv_norm_out")
 
     # ---- plans ------------------------------------------------------------------------------------
-    def _plan(self, batch, h, w, n_ctx, hook_ids, shared_ctx=False, split=None, early_exit=None):
+    def _plan(self, batch, h, w, n_ctx, hook_ids, shared_ctx=False, split=None, early_exit=None, residuals=False):
         split = self.split_for(hook_ids, lat=min(h, w)) if split is None else split
         early_exit = self.early_exit if early_exit is None else bool(early_exit)
-        key = (batch, h, w, n_ctx, tuple(hook_ids), self.stream_fp32, early_exit, bool(shared_ctx), split, self.cus)
+        key = (batch, h, w, n_ctx, tuple(hook_ids), self.stream_fp32, early_exit, bool(shared_ctx), split, self.cus, bool(residuals))
         p = self._plans.get(key)
         if p is None:
             ids = (C.c_char_p * max(1, len(hook_ids)))(*[s.encode() for s in hook_ids])
@@ -830,6 +851,7 @@ class NativeUNet(_NativeModel):
             opts.reserved[0] = int(bool(shared_ctx))
             opts.reserved[1] = 1 if split == SPLIT_ALL else (split << 8)
             opts.reserved[2] = int(self.cus)
+            opts.reserved[3] = int(bool(residuals))
             ph = C.c_void_p()
             _check(self.lib.gdf_plan_create(self.handle, batch, h, w, n_ctx, ids, len(hook_ids), C.byref(opts),
                                             C.byref(ph)), "plan_create")
@@ -843,12 +865,20 @@ class NativeUNet(_NativeModel):
 
     # ---- forward ------------------------------------------------------------------------------------
     def forward_raw(self, sample, timestep, encoder_hidden_states, text_embeds=None, time_ids=None, hook_ids=None,
-                    profile=False, shared_ctx=False):
+                    profile=False, shared_ctx=False, residuals=None):
         """Returns (noise_pred (B,4,H,W) view, OrderedDict id -> hook tensor). Inputs must live on self.device.
         shared_ctx=True promises that every row-block of encoder_hidden_states equals the first one (one prompt repeated
-        over the batch, as FeatureExtractor.extract does): the text K/V projections are then computed once per call."""
+        over the batch, as FeatureExtractor.extract does): the text K/V projections are then computed once per call.
+        residuals: the ControlNet residual block (gdf_forward_res, include/gdf.h): a flat fp16 device tensor of
+        residual_layout(B, H, W)[1] bytes laid out as that function says (pack_residuals builds one from NCHW tensors)."""
         dev = self.device
         B, _, H, W = sample.shape
+        if residuals is not None:
+            if profile:
+                raise NotImplementedError("per-op profiling of a forward with residuals: time its kernel with gdf_plan_set_timing instead")
+            need = self.residual_layout(B, H, W)[1]
+            if residuals.dtype != torch.float16 or residuals.dim() != 1 or residuals.numel() * 2 != need:
+                raise ValueError(f"the residual block must be a flat fp16 tensor of {need} bytes for batch {B}, latent {H}x{W}")
         ctx = encoder_hidden_states
         t = _timestep_on_device(timestep, B, dev)
         txt = tid = None
@@ -864,20 +894,23 @@ class NativeUNet(_NativeModel):
             raise ValueError("encoder_hidden_states shape mismatch")
         ids = list(hook_ids) if hook_ids is not None else self.requested_ids()
         self.last_split = self.split_for(ids, lat=min(H, W))
-        plan = self._plan(B, H, W, ctx.shape[1], ids, shared_ctx, self.last_split)
+        has_res = residuals is not None
+        plan = self._plan(B, H, W, ctx.shape[1], ids, shared_ctx, self.last_split, residuals=has_res)
         f16, f32 = torch.float16, torch.float32
-        call = self._launch(plan, self.lib.gdf_forward, self.lib.gdf_plan_profile, "forward", profile)
-        noise, out, prof = plan.run(dev, [("sample", sample, f16), ("t", t, f32), ("ctx", ctx, f16), ("txt", txt, f16),
-                                          ("tid", tid, f32)], (B, H, W, self.cfg["out_channels"]), call, profile=profile)
+        fwd = self.lib.gdf_forward_res if has_res else self.lib.gdf_forward
+        inputs = [("sample", sample, f16), ("t", t, f32), ("ctx", ctx, f16), ("txt", txt, f16), ("tid", tid, f32)]
+        if has_res:
+            inputs.append(("res", residuals, f16))        # (staged like every input: a stable address for the plan's graph)
+        call = self._launch(plan, fwd, self.lib.gdf_plan_profile, "forward", profile)
+        noise, out, prof = plan.run(dev, inputs, (B, H, W, self.cfg["out_channels"]), call, profile=profile)
         noise_nchw = noise.permute(0, 3, 1, 2)
         if profile:
             return noise_nchw, out, prof
         if self.verify and getattr(self, "auto_split", False) and self.stream_fp32 and tuple(ids) not in self._verified:
             def run(mask):
-                pl = self._plan(B, H, W, ctx.shape[1], ids, shared_ctx, mask)
-                cl = self._launch(pl, self.lib.gdf_forward, self.lib.gdf_plan_profile, "forward", False)
-                n_, o_, _ = pl.run(dev, [("sample", sample, f16), ("t", t, f32), ("ctx", ctx, f16), ("txt", txt, f16), ("tid", tid, f32)],
-                                   (B, H, W, self.cfg["out_channels"]), cl)
+                pl = self._plan(B, H, W, ctx.shape[1], ids, shared_ctx, mask, residuals=has_res)    # (every level sees the same residual block)
+                cl = self._launch(pl, fwd, self.lib.gdf_plan_profile, "forward", False)
+                n_, o_, _ = pl.run(dev, inputs, (B, H, W, self.cfg["out_channels"]), cl)
                 return n_.permute(0, 3, 1, 2), o_
             noise_nchw, out = self._verify_level(run, ids, (noise_nchw, out))
         return noise_nchw, out
@@ -1028,17 +1061,51 @@ class NativeUNet(_NativeModel):
         # the master lives in the plan's staging buffer, which the next call overwrites: hand out a copy (ordered on the caller's stream)
         return plain.staged["x32"].clone(), captured
 
+    # ---- ControlNet residuals ---------------------------------------------------------------------------
+    def residual_layout(self, batch, lat_h, lat_w):
+        """([(byte offset, (B, C, H, W))], bytes) of the residual block of this UNet (module-level residual_layout)"""
+        return residual_layout(self.cfg, batch, lat_h, lat_w)
+
+    def pack_residuals(self, down_block_additional_residuals, mid_block_additional_residual):
+        """Torch (B, C, H, W) residuals of any ControlNet -> the flat fp16 block forward_raw takes (channels-last tensors at the offsets of
+        residual_layout).  ValueError on a wrong count or shape."""
+        down = list(down_block_additional_residuals)
+        mid = mid_block_additional_residual
+        if mid.dim() != 4:
+            raise ValueError(f"mid_block_additional_residual must be (B, C, H, W), got {tuple(mid.shape)}")
+        B = mid.shape[0]
+        n = self.cfg["layers_per_block"] * len(self.cfg["block_out_channels"]) + len(self.cfg["block_out_channels"])
+        if len(down) != n:
+            raise ValueError(f"down_block_additional_residuals has {len(down)} tensors, this UNet has {n} skips")
+        up = 1 << (len(self.cfg["block_out_channels"]) - 1)
+        lay, nbytes = self.residual_layout(B, mid.shape[2] * up, mid.shape[3] * up)
+        block = torch.zeros(nbytes // 2, dtype=torch.float16, device=self.device)
+        for i, (t, (off, shape)) in enumerate(zip(down + [mid], lay)):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{'mid residual' if i == n else 'down residual %d' % i} has shape {tuple(t.shape)}, expected {shape}")
+            b, c, h, w = shape
+            block[off // 2:off // 2 + b * c * h * w].view(b, h, w, c).copy_(t.permute(0, 2, 3, 1))
+        return block
+
     def __call__(self, sample, timestep=None, encoder_hidden_states=None, added_cond_kwargs=None,
                  down_block_additional_residuals=None, mid_block_additional_residual=None, return_dict=False,
                  **kwargs):
-        if down_block_additional_residuals is not None or mid_block_additional_residual is not None:
-            raise NotImplementedError("ControlNet residuals are outside the native hot path (SURVEY.md §2 #5)")
+        residuals = None
+        if down_block_additional_residuals is not None and mid_block_additional_residual is not None:    # `is_controlnet`, unet_2d_condition.py:1194
+            residuals = self.pack_residuals(down_block_additional_residuals, mid_block_additional_residual)
+            if residuals.numel() * 2 != self.residual_layout(*[sample.shape[i] for i in (0, 2, 3)])[1]:
+                raise ValueError("the residuals do not match the sample's batch and latent size")
+        elif down_block_additional_residuals is not None:
+            raise NotImplementedError("down_block_additional_residuals without mid_block_additional_residual is the deprecated T2I-Adapter "
+                                      "route of the reference (unet_2d_condition.py:1200-1210): not on the native path")
+        elif mid_block_additional_residual is not None:
+            raise ValueError("mid_block_additional_residual needs down_block_additional_residuals (unet_2d_condition.py:1194)")
         akw = added_cond_kwargs or {}
         ids = self.requested_ids()
         have = set(ids)
         ids = ids + [i for i in self.extra_hook_ids if i not in have]
         noise, hooks = self.forward_raw(sample, timestep, encoder_hidden_states, akw.get("text_embeds"),
-                                        akw.get("time_ids"), hook_ids=ids, shared_ctx=self.shared_ctx)
+                                        akw.get("time_ids"), hook_ids=ids, shared_ctx=self.shared_ctx, residuals=residuals)
         self.last_extra = {k: v for k, v in hooks.items() if k in set(self.extra_hook_ids)}
         if self.feature_store is not None:
             for hid, t in hooks.items():

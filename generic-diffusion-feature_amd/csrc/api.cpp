@@ -248,6 +248,40 @@ int gdf_forward(gdf_plan* p, const void* latents, const float* timesteps, const 
                       workspace, (hipStream_t)stream, nullptr, nullptr, nullptr, 0);
 }
 
+int gdf_forward_res(gdf_plan* p, const void* latents, const float* timesteps, const void* ctx, const void* add_text_embeds,
+                    const float* add_time_ids, const void* residuals, void* const* hook_out, void* noise_pred, void* workspace, void* stream) {
+  if (!p) { set_error("null plan"); return GDF_ERR_ARG; }
+  if (!residuals) { set_error("gdf_forward_res: residuals is NULL"); return GDF_ERR_ARG; }
+  return plan_forward(p->p, *p->p.model, latents, timesteps, ctx, add_text_embeds, add_time_ids, hook_out, noise_pred,
+                      workspace, (hipStream_t)stream, nullptr, nullptr, nullptr, 0, residuals);
+}
+
+// host arithmetic only (no device is touched): tests/test_controlnet_cpu.py calls these without a GPU
+int gdf_residual_count(const gdf_arch_desc* arch) {
+  return arch ? (int)residual_layout(*arch, 1, 1 << GDF_MAX_LEVELS, 1 << GDF_MAX_LEVELS).t.size() : 0;
+}
+size_t gdf_residual_bytes(const gdf_arch_desc* arch, int batch, int lat_h, int lat_w) {
+  return arch ? residual_layout(*arch, batch, lat_h, lat_w).bytes : 0;
+}
+int gdf_residual_info(const gdf_arch_desc* arch, int batch, int lat_h, int lat_w, int i, size_t* offset, int64_t shape[4]) {
+  if (!arch) { set_error("null argument"); return GDF_ERR_ARG; }
+  const ResidualLayout R = residual_layout(*arch, batch, lat_h, lat_w);
+  if (i < 0 || i >= (int)R.t.size()) { set_error("bad residual index"); return GDF_ERR_ARG; }
+  if (offset) *offset = R.t[i].off;
+  if (shape) { shape[0] = batch; shape[1] = R.t[i].C; shape[2] = R.t[i].H; shape[3] = R.t[i].W; }
+  return GDF_OK;
+}
+int gdf_plan_residual_count(const gdf_plan* p) {
+  return (p && p->p.takes_res) ? gdf_residual_count(&p->p.model->arch) : 0;
+}
+size_t gdf_plan_residual_bytes(const gdf_plan* p) {
+  return (p && p->p.takes_res) ? gdf_residual_bytes(&p->p.model->arch, p->p.batch, p->p.H, p->p.W) : 0;
+}
+int gdf_plan_residual_info(const gdf_plan* p, int i, size_t* offset, int64_t shape[4]) {
+  if (!p || !p->p.takes_res) { set_error("the plan takes no residuals (gdf_plan_opts.reserved[3])"); return GDF_ERR_ARG; }
+  return gdf_residual_info(&p->p.model->arch, p->p.batch, p->p.H, p->p.W, i, offset, shape);
+}
+
 int gdf_trajectory(gdf_plan* p, float* latents_f32, int n_steps, const float* table, const void* ctx, const void* add_text_embeds,
                    const float* add_time_ids, void* noise_pred_scratch, void* workspace, void* stream) {
   if (!p) { set_error("null plan"); return GDF_ERR_ARG; }

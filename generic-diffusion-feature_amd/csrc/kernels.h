@@ -319,6 +319,16 @@ hipError_t launch_avg_pool(const half_t* src, long sb, long sy, long sx, int B, 
 hipError_t launch_maps_mean(const half_t* const* maps, int n, int B, int heads, int Q, int K, float* out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
+// ControlNet conditioning (csrc/control.hip)
+// ------------------------------------------------------------------------------------------------
+// dst[r][0..C) += res[r][0..C) for up to RES_ADD_MAX tensors in ONE launch: dst fp16 rows of ld elements (a slice of a wider row: the pointer
+// carries the column offset), res fp16 contiguous [rows][C]; lo > 0: dst is a split (hi, lo) pair, lo `lo` elements after hi in the same row,
+// rewritten as the pair of hi + lo + res (fp32).  C, ld, lo multiples of 8, both pointers 16-byte aligned.
+enum { RES_ADD_MAX = 16 };
+struct ResAddDesc { half_t* dst; int ld; int lo; const half_t* res; int rows; int C; };
+hipError_t launch_residual_add(const ResAddDesc* d, int n, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
 // weight re-layout (model load time)
 // ------------------------------------------------------------------------------------------------
 // `src_f32` is the source dtype code of gdf_model_set_param: 0 fp16, 1 fp32, 2 bf16

@@ -483,8 +483,11 @@ struct B : PlanBuilder {   // UNet op program
     }
     int n_skips = (int)cats.size();   // == number of skip tensors
     int skip_idx = 0;                 // k-th produced skip is consumed by cats[n_skips-1-k]
+    struct ResDst { size_t off; int ld, lo, C; size_t rows; };
+    std::vector<ResDst> res_dst;  // every skip in production order: where the ControlNet residual adds land (below)
     auto skip_dst = [&](int C, int hh, int ww) -> Act {
       const Cat& c = cats[n_skips - 1 - skip_idx++];
+      res_dst.push_back({c.off + (size_t)c.ch * 2, (c.ch + c.cs) * px, sps ? c.ch + c.cs : 0, C, (size_t)Bn * hh * ww});
       return view_act(ws(c.off + (size_t)c.ch * 2), (c.ch + c.cs) * px, C, hh, ww, true, sps ? c.ch + c.cs : 0);
     };
 
@@ -563,6 +566,28 @@ struct B : PlanBuilder {   // UNet op program
       resnet("mid-repeat1", m.mid_res1, a1, a2);
       free_act(a1);
       cur = a2;
+      res_dst.push_back({cats[0].off, a2.ld, a2.lo, a2.C, rows(a2)});
+    }
+    // ---- ControlNet residuals (unet_2d_condition.py:1236-1245, 1269-1270) ----
+    // A skip is not a copy: it IS the skip slice of its concat buffer, and the down path went on reading that memory (the last skip is the
+    // mid block's input, read again by mid-repeat0's conv2 epilogue).  So all adds run here, behind the mid block and its hooks and in front of
+    // the first up resnet: the down and mid paths are untouched by construction, the up path sees skip + residual and mid + residual.  The fp32
+    // masters of the skips are read by the down path only and stay as they are.  An early exit in front of this point emits nothing.
+    if (opt.reserved[3] && !stop) {
+      const ResidualLayout rl = residual_layout(a, Bn, H, W);
+      if (rl.t.size() != res_dst.size() || res_dst.size() > (size_t)RES_ADD_MAX) { set_error("residual layout does not match the skip list"); bad = true; }
+      else {
+        for (size_t k = 0; k < res_dst.size(); ++k)
+          if (rl.t[k].C != res_dst[k].C || (size_t)Bn * rl.t[k].H * rl.t[k].W != res_dst[k].rows) { set_error("residual layout does not match the skip list"); bad = true; }
+        op("residual_add", 0, [=](const Bind& b, hipStream_t s) {
+          if (!b.base[BUF_RES]) return hipErrorInvalidValue;
+          ResAddDesc d[RES_ADD_MAX];
+          for (size_t k = 0; k < res_dst.size(); ++k)
+            d[k] = ResAddDesc{(half_t*)b.ws(res_dst[k].off), res_dst[k].ld, res_dst[k].lo, (const half_t*)(b.base[BUF_RES] + rl.t[k].off),
+                              (int)res_dst[k].rows, res_dst[k].C};
+          return launch_residual_add(d, (int)res_dst.size(), s);
+        }, "residual_add_kernel");
+      }
     }
     // ---- up path ----
     int ci = 0;
@@ -638,6 +663,24 @@ static TrajLayout traj_layout(const Plan& P) {
   return L;
 }
 
+ResidualLayout residual_layout(const GdfArch& a, int batch, int H, int W) {
+  ResidualLayout R;
+  const int L = a.n_levels;
+  if (batch < 1 || H < 1 || W < 1 || L < 1 || L > GDF_MAX_LEVELS || a.layers_per_block < 1) return R;
+  auto put = [&](int C, int h, int w) {
+    R.t.push_back({R.bytes, C, h, w});
+    R.bytes = (R.bytes + (size_t)batch * h * w * C * 2 + 255) & ~(size_t)255;
+  };
+  int h = H, w = W;
+  put(a.block_out_channels[0], h, w);                                          // conv_in
+  for (int lv = 0; lv < L; ++lv) {
+    for (int r = 0; r < a.layers_per_block; ++r) put(a.block_out_channels[lv], h, w);
+    if (lv != L - 1) { h /= 2; w /= 2; put(a.block_out_channels[lv], h, w); }  // downsampler
+  }
+  put(a.block_out_channels[L - 1], h, w);                                      // mid block
+  return R;
+}
+
 int plan_build(const Model& m, Plan& P, int batch, int H, int W, int n_ctx, const char* const* ids, int n_ids,
                const PlanOpts& opts, bool dry) {
   const int L = m.arch.n_levels;
@@ -662,6 +705,7 @@ int plan_build(const Model& m, Plan& P, int batch, int H, int W, int n_ctx, cons
     }
   }
   P.batch = batch; P.H = H; P.W = W; P.n_ctx = n_ctx; P.opts = opts;
+  P.takes_res = opts.reserved[3] != 0;
   B b(m, P, dry, opts);
   b.Bn = batch; b.n_ctx = n_ctx;
   // row N1's statistics half (round 5, ON by default): the resnet convs emit the GroupNorm partial sums of the fp16 image they store (gemm_body<..., GNS>:
@@ -749,8 +793,11 @@ int plan_read_timing(Plan& P, double* ms, long* launches, double* flops) {
 
 int plan_forward(Plan& P, const Model& m, const void* lat, const float* t, const void* ctx, const void* txt,
                  const float* tid, void* const* hook_out, void* noise, void* ws, hipStream_t s, float* ms,
-                 const char** names, double* flops, int cap) {
+                 const char** names, double* flops, int cap, const void* residuals) {
   if (m.kind != 0) { set_error("gdf_forward on a Flux model: use gdf_flux_forward"); return GDF_ERR_STATE; }
+  if (residuals && !P.takes_res) { set_error("gdf_forward_res needs a plan created with gdf_plan_opts.reserved[3] = 1"); return GDF_ERR_STATE; }
+  if (!residuals && P.takes_res) { set_error("this plan adds ControlNet residuals: run it with gdf_forward_res"); return GDF_ERR_STATE; }
+  if (((uintptr_t)residuals & 255) != 0) { set_error("the residual block must be 256-byte aligned"); return GDF_ERR_ARG; }
   if (m.n_set != (int)m.params.size()) { set_error("model weights incomplete"); return GDF_ERR_STATE; }
   Bind b;
   b.base[BUF_WS] = (char*)ws; b.base[BUF_WT] = (char*)m.weights; b.base[BUF_LAT] = (char*)lat; b.base[BUF_T] = (char*)t;
@@ -760,6 +807,7 @@ int plan_forward(Plan& P, const Model& m, const void* lat, const float* t, const
   if (P.hooks.size() && !hook_out) { set_error("hook_out is null"); return GDF_ERR_ARG; }
   if (P.writes_noise && !noise) { set_error("noise_pred buffer required (the plan runs conv_out)"); return GDF_ERR_ARG; }
   b.base[BUF_NOISE] = (char*)noise;
+  b.base[BUF_RES] = (char*)residuals;
   return plan_run(P, b, s, ms, names, flops, cap);
 }
 

@@ -122,7 +122,8 @@ struct Model {
 // TID = guidance, NOISE = output; IDS_IMG / IDS_TXT = img_ids / txt_ids
 // SAMPLE: the caller's state block of a guided sampling run (gdf_sample, sample_layout); a slot of its OWN, which only plan_sample fills —
 // the executor appends the guided update wherever it is set, so it must never alias an input of another front end
-enum { BUF_WS = 0, BUF_WT, BUF_LAT, BUF_T, BUF_CTX, BUF_TXT, BUF_TID, BUF_NOISE, BUF_IDS_IMG, BUF_IDS_TXT, BUF_SAMPLE, BUF_COUNT };
+// RES: the caller's ControlNet residual block (gdf_forward_res, residual_layout); null on every other call
+enum { BUF_WS = 0, BUF_WT, BUF_LAT, BUF_T, BUF_CTX, BUF_TXT, BUF_TID, BUF_NOISE, BUF_IDS_IMG, BUF_IDS_TXT, BUF_SAMPLE, BUF_RES, BUF_COUNT };
 enum { BUF_X32 = BUF_IDS_IMG };                 // UNet trajectory (gdf_trajectory): the caller's fp32 master latents; null on a plain forward
 enum { BUF_HOOK0 = 1 << 16 };                   // Ref.buf = BUF_HOOK0 + slot: the caller's hook buffer `slot` (an op's output IS the hook)
 struct Ref { int buf = BUF_WS; size_t off = 0; };
@@ -156,6 +157,7 @@ struct Plan {
   std::unordered_set<std::string> requested;
   bool want_maps = false;
   bool writes_noise = false;
+  bool takes_res = false;                     // UNet plans created with gdf_plan_opts.reserved[3]: run through gdf_forward_res
   size_t ws_bytes = 0;
   // UNet plans without hooks and without early exit (they exist for noise_pred): byte offset of the trajectory state at the end of the workspace
   // — the forwards' fp16 latent input (B, 4, H, W), their timestep buffer (B) and the latent_step block {step, ticket, n_rows, 0} + coefficient
@@ -196,7 +198,13 @@ int plan_build(const Model& m, Plan& P, int batch, int H, int W, int n_ctx, cons
                const PlanOpts& opts, bool dry);
 int plan_forward(Plan& P, const Model& m, const void* lat, const float* t, const void* ctx, const void* txt,
                  const float* tid, void* const* hook_out, void* noise, void* ws, hipStream_t s, float* ms,
-                 const char** names, double* flops, int cap);
+                 const char** names, double* flops, int cap, const void* residuals = nullptr);
+// The ControlNet residual block of an architecture at (batch, H, W): one fp16 channels-last (B, H, W, C) tensor per skip of the UNet in
+// diffusers' order (conv_in output; per level every resnet(+transformer) output, then the downsampler output) and, LAST, the mid block's;
+// every tensor at a 256-byte-aligned offset.  The one function both the consumer (UNet plans) and any producer compute the layout from.
+struct ResidualTensor { size_t off; int C, H, W; };
+struct ResidualLayout { std::vector<ResidualTensor> t; size_t bytes = 0; };
+ResidualLayout residual_layout(const GdfArch& a, int batch, int H, int W);
 // n_steps x (forward + latent_step) on one stream, nothing from the host in between (include/gdf.h gdf_trajectory)
 int plan_trajectory(Plan& P, const Model& m, float* x32, int n_steps, const float* table, const void* ctx, const void* txt, const float* tid,
                     void* noise, void* ws, hipStream_t s);

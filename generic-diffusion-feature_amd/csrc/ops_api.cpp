@@ -448,6 +448,14 @@ int gdf_op_maps_mean(const void* const* maps, int n, int B, int heads, int Q, in
   return fin(launch_maps_mean((const half_t* const*)maps, n, B, heads, Q, K, out, (hipStream_t)stream), "maps_mean");
 }
 
+int gdf_op_residual_add(const gdf_residual_add_item* items, int n, void* stream) {
+  if (n < 0 || n > RES_ADD_MAX || (n > 0 && !items)) { set_error("gdf_op_residual_add: 0 <= n <= 16 items"); return GDF_ERR_ARG; }
+  ResAddDesc d[RES_ADD_MAX];
+  for (int k = 0; k < n; ++k)
+    d[k] = ResAddDesc{(half_t*)items[k].dst, items[k].ld, items[k].lo, (const half_t*)items[k].res, items[k].rows, items[k].C};
+  return fin(launch_residual_add(d, n, (hipStream_t)stream), "residual_add");
+}
+
 // element type of the 16-bit operands of the MMDiT entry points below, per calling thread (GDF_F16 default)
 static thread_local int g_e16_bf = 0;
 int gdf_op_set_e16(int dtype) {

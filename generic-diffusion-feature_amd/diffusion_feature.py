@@ -69,7 +69,9 @@ class FeatureExtractor(nn.Module):
                  ):
         super().__init__()
         if control:
-            raise NotImplementedError("ControlNet conditioning is outside the native hot path (SURVEY.md §2 #5)")
+            raise NotImplementedError("control=: the native UNet takes ControlNet residuals (NativeUNet.__call__ with down_block_additional_residuals / "
+                                      "mid_block_additional_residual, gdf_forward_res), but this package has no ControlNet model or "
+                                      "preprocessor of its own yet (DESIGN.md 3.17, 7): run the ControlNet yourself and call pipe.unet")
         if attention:
             bad = [a for a in attention if a not in ATTENTION_CATEGORIES]
             if bad:
@@ -186,7 +188,8 @@ class FeatureExtractor(nn.Module):
         (reference :381-386), see _ddim_inverted_latents."""
         if use_control:
             raise NotImplementedError("use_control: ControlNet conditioning needs cv2, controlnet_aux and a ControlNet model class, none of which "
-                                      "the native path carries (SURVEY.md §2 #5)")
+                                      "the native path carries; its UNet side is native — NativeUNet.__call__ accepts the residuals of any "
+                                      "ControlNet (DESIGN.md 3.17)")
         if denoising_from:
             raise NotImplementedError("denoising_from is deprecated upstream and runs there only together with ControlNet (its denoising call "
                                       "reads the ControlNet branch's raw image, reference diffusion_feature.py:394); not native")

@@ -98,7 +98,9 @@ typedef struct gdf_plan_opts {
                           ln_attn 4, attn_out 8, ln_ff 16, ff_inner 32, res 64, out 128, sampler 256, attn2_out 512, upsampler 1024,
                           qkv 2048 / xqkv 4096 = round 5: the self- / cross-attention q, k, v stored as pairs, the flash kernel contracts over both halves); 1 = all.
                           reserved[2] = cus: the plan will run on a stream restricted to this many CUs (gdf_stream_create_cu_mask):
-                          tile selection, persistent grids and the XCD super-block order are sized for that partition. 0 = whole chip. */
+                          tile selection, persistent grids and the XCD super-block order are sized for that partition. 0 = whole chip.
+                          reserved[3] = residuals (UNet plans): the plan adds ControlNet residuals to its skip tensors and to the mid block's
+                          output and runs through gdf_forward_res (below).  0: the op program is exactly the one without this slot. */
 } gdf_plan_opts;
 
 int gdf_plan_create(gdf_model* m, int batch, int lat_h, int lat_w, int n_ctx,
@@ -131,6 +133,28 @@ int gdf_plan_hook_copied(const gdf_plan* p, int i);
 int gdf_forward(gdf_plan* p, const void* latents, const float* timesteps, const void* ctx,
                 const void* add_text_embeds, const float* add_time_ids,
                 void* const* hook_out, void* noise_pred, void* workspace, void* stream);
+
+/* ControlNet residuals: gdf_forward on a plan created with gdf_plan_opts.reserved[3] = 1, plus `residuals`, ONE contiguous device block
+ * (256-byte aligned, gdf_plan_residual_bytes) that holds `down_block_additional_residuals` and `mid_block_additional_residual` of
+ * UNet2DConditionModel.forward (unet_2d_condition.py:1050-1051, 1236-1245, 1269-1270):
+ *   tensor i < count - 1   the residual of the i-th skip in diffusers' order: the conv_in output; then per level every resnet (+ transformer)
+ *                          output and, on all but the last level, the downsampler output  (12 tensors for SD1.5 / 2.1, 9 for SDXL)
+ *   tensor count - 1       the mid block's residual
+ * each fp16 channels-last (B, H, W, C) at the 256-byte-aligned offset gdf_plan_residual_info reports (shape = logical B, C, H, W).  The
+ * block is read only.  Every skip gets its residual before the up path reads it and the mid output gets its own; the down path, the mid
+ * block and all their hooks are those of the plain forward, bit for bit (the adds run behind the mid block: csrc/model.cpp).  With split
+ * STREAM images the add is hi + lo + residual in fp32, re-split.  A plan whose early exit ends in front of the up path reads nothing.
+ * The layout depends on the architecture, the batch and the latent size alone: gdf_residual_* compute it without a plan or a device (a
+ * producer — a ControlNet's zero convs — writes the block through the same function). */
+int gdf_forward_res(gdf_plan* p, const void* latents, const float* timesteps, const void* ctx, const void* add_text_embeds,
+                    const float* add_time_ids, const void* residuals, void* const* hook_out, void* noise_pred, void* workspace,
+                    void* stream);
+int gdf_plan_residual_count(const gdf_plan* p);          /* 0 for a plan created without reserved[3] */
+size_t gdf_plan_residual_bytes(const gdf_plan* p);
+int gdf_plan_residual_info(const gdf_plan* p, int i, size_t* offset, int64_t shape[4]);
+int gdf_residual_count(const gdf_arch_desc* arch);
+size_t gdf_residual_bytes(const gdf_arch_desc* arch, int batch, int lat_h, int lat_w);
+int gdf_residual_info(const gdf_arch_desc* arch, int batch, int lat_h, int lat_w, int i, size_t* offset, int64_t shape[4]);
 
 /* A device-resident multi-step latent trajectory: n_steps x (one forward + one scheduler update), e.g. DDIM inversion
  * (/root/reference/feature/components/ddim_inversion.py:19-43).

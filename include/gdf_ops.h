@@ -299,6 +299,22 @@ int gdf_op_avg_pool(const void* src, long sb, long sy, long sx, int B, int C, in
  * group -> (B, Q, K) fp32; gdf_op_resize_concat then turns it into the (B, K, img/8, img/8) slice of the feature. */
 int gdf_op_maps_mean(const void* const* maps, int n, int B, int heads, int Q, int K, float* out, void* stream);
 
+/* ---- ControlNet conditioning (csrc/control.hip) ---- */
+
+/* One launch of residual_add_kernel over n <= 16 tensors: dst[r][0..C) += res[r][0..C), r < rows — the skip and mid-block adds of
+ * unet_2d_condition.py:1236-1245, 1269-1270, in place on the slices of the up-path concat buffers a UNet plan keeps its skips in.
+ *   dst   fp16 rows of ld elements; the pointer carries the slice's column offset (ld >= C)
+ *   lo    0: a plain image, dst = fp16(dst + res), one rounding.  > 0: dst is a split (hi, lo) pair, lo `lo` >= C elements after hi in the same
+ *         row; the new pair is hi' = fp16(v), lo' = fp16(v - hi') of v = hi + lo + res in fp32
+ *   res   fp16 contiguous [rows][C], read only
+ * C, ld and lo are multiples of 8 and both pointers 16-byte aligned (16 bytes per lane); anything else is an error and nothing is launched.
+ * Items with rows == 0 or C == 0 are skipped. */
+typedef struct gdf_residual_add_item {
+  void* dst; int ld; int lo;
+  const void* res; int rows; int C;
+} gdf_residual_add_item;
+int gdf_op_residual_add(const gdf_residual_add_item* items, int n, void* stream);
+
 /* ---- MMDiT (Flux) kernels (reference files cited in csrc/dit.hip, gdf_flux.h) ---- */
 
 /* Element type of the 16-bit operands ("e16": A, W, out16, q/k/v/o, y) of the MMDiT entry points below, per calling thread:
