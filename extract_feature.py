@@ -345,7 +345,8 @@ def main(argv=None):
     n_thr = min(32, max(2, (os.cpu_count() or 2) // (2 * ranks_here))) if args.loader_threads < 0 else args.loader_threads
     # flux / hunyuan pipelines take PIL images (reference :246-254); the UNet / PixArt versions go through df.preprocess_image, which is what the
     # loader threads run — the SAME function the serial path calls, so the latents are bit-identical either way
-    prefetch = n_thr > 0 and args.version not in ('flux', 'hunyuan') and not args.show_all_layers
+    # (--control: the preprocessors want the PIL images themselves, reference diffusion_feature.py:433 — the serial path hands them over)
+    prefetch = n_thr > 0 and args.version not in ('flux', 'hunyuan') and not args.show_all_layers and args.control is None
     loader = BatchLoader(paths, starts, hi, args.batch_size, df.preprocess_image, n_thr) if prefetch else None
     ok = False
     try:

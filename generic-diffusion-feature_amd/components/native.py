@@ -72,6 +72,12 @@ SIGNATURES = {
     "gdf_residual_count": (C.c_int, [C.POINTER(ArchDesc)]),
     "gdf_residual_bytes": (C.c_size_t, [C.POINTER(ArchDesc), C.c_int, C.c_int, C.c_int]),
     "gdf_residual_info": (C.c_int, [C.POINTER(ArchDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int64 * 4)]),
+    "gdf_controlnet_create": (C.c_int, [C.POINTER(ArchDesc), C.POINTER(C.c_int * 4), C.c_int, C.POINTER(C.c_void_p)]),
+    "gdf_controlnet_layout": (C.c_int, [C.POINTER(ArchDesc), C.POINTER(C.c_int * 4), C.c_int, C.POINTER(C.c_void_p)]),
+    "gdf_controlnet_plan_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PlanOpts), C.POINTER(C.c_void_p)]),
+    "gdf_controlnet_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdf_controlnet_residual_bytes": (C.c_size_t, [C.c_void_p]),
     "gdf_plan_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_int]),
@@ -292,7 +298,7 @@ def config_from_diffusers(uc):
     ahd = uc.attention_head_dim
     ahd = tuple(ahd) if isinstance(ahd, (list, tuple)) else (ahd,) * n
     text_time = getattr(uc, "addition_embed_type", None) == "text_time"
-    return dict(in_channels=uc.in_channels, out_channels=uc.out_channels, block_out_channels=boc,
+    return dict(in_channels=uc.in_channels, out_channels=getattr(uc, "out_channels", uc.in_channels), block_out_channels=boc,
                 has_attn=tuple(int("CrossAttn" in t) for t in uc.down_block_types), transformer_layers=tl, heads=ahd,
                 layers_per_block=getattr(uc, "layers_per_block", 2), cross_attention_dim=uc.cross_attention_dim,
                 use_linear_projection=int(bool(getattr(uc, "use_linear_projection", False))), time_embed_dim=boc[0] * 4,
@@ -1066,6 +1072,21 @@ class NativeUNet(_NativeModel):
         """([(byte offset, (B, C, H, W))], bytes) of the residual block of this UNet (module-level residual_layout)"""
         return residual_layout(self.cfg, batch, lat_h, lat_w)
 
+    def residual_buffer(self, batch, lat_h, lat_w, n_ctx, hook_ids=None, shared_ctx=False):
+        """The staged residual block of the plan forward_raw(residuals=...) will pick for these arguments: a flat fp16 tensor with a stable
+        address.  A producer that writes it in place (NativeControlNet.forward_raw(out=...)) and hands the same tensor to forward_raw saves
+        the staging copy; handing any other tensor (or reaching another plan) is as correct and costs that copy."""
+        ids = list(hook_ids) if hook_ids is not None else self.requested_ids()
+        plan = self._plan(batch, lat_h, lat_w, n_ctx, ids, shared_ctx, self.split_for(ids, lat=min(lat_h, lat_w)), residuals=True)
+        n = self.residual_layout(batch, lat_h, lat_w)[1] // 2
+        b = plan.staged.get("res")
+        if b is None or b.numel() != n:
+            if b is not None and plan.stream is not None:
+                plan.stream.synchronize()
+            with torch.cuda.device(self.device):
+                b = plan.staged["res"] = torch.empty(n, dtype=torch.float16, device=self.device)
+        return b
+
     def pack_residuals(self, down_block_additional_residuals, mid_block_additional_residual):
         """Torch (B, C, H, W) residuals of any ControlNet -> the flat fp16 block forward_raw takes (channels-last tensors at the offsets of
         residual_layout).  ValueError on a wrong count or shape."""
@@ -1114,6 +1135,153 @@ class NativeUNet(_NativeModel):
         if return_dict:
             return types.SimpleNamespace(sample=noise)
         return (noise,)
+
+
+# --------------------------------------------------------------------------------------------- #
+# ControlNet (include/gdf_control.h): diffusers' ControlNetModel over the encoder half of a UNet architecture
+# (reference components/controlnet.py:95-130)
+# --------------------------------------------------------------------------------------------- #
+COND_CHANNELS = (16, 32, 96, 256)        # conditioning_embedding_out_channels of every checkpoint the reference loads
+
+
+def controlnet_param_shapes(cfg, cond_channels=COND_CHANNELS, conditioning_channels=3):
+    """{name: shape} of a ControlNetModel state dict over architecture `cfg`, in libgdf's registration order (host arithmetic: no GPU)"""
+    lib = load_library()
+    a, cc, h = arch_desc(cfg), (C.c_int * 4)(*cond_channels), C.c_void_p()
+    _check(lib.gdf_controlnet_layout(C.byref(a), C.byref(cc), conditioning_channels, C.byref(h)), "controlnet_layout")
+    try:
+        out = {}
+        for i in range(lib.gdf_model_param_count(h)):
+            shp = (C.c_int64 * 4)()
+            nd = lib.gdf_model_param_shape(h, i, C.byref(shp))
+            out[lib.gdf_model_param_name(h, i).decode()] = tuple(shp[:nd])
+        return out
+    finally:
+        lib.gdf_model_destroy(h)
+
+
+class NativeControlNet(_NativeModel):
+    """ControlNetModel replacement running entirely in libgdf.so: the conditioning embedding (csrc/cond_embed.hip), the UNet's down and mid
+    program, and one 1x1 conv per skip written straight into the residual block NativeUNet.forward_raw(residuals=...) reads."""
+
+    def __init__(self, cfg, device="cuda", cond_channels=COND_CHANNELS, conditioning_channels=3, stream_fp32=True):
+        if not torch.cuda.is_available():
+            raise RuntimeError("NativeControlNet needs an MI355X (HIP device); there is no CPU fallback")
+        self.lib = load_library()
+        self.cfg = dict(cfg)
+        self.cond_channels = tuple(int(c) for c in cond_channels)
+        self.conditioning_channels = int(conditioning_channels)
+        if len(self.cond_channels) != 4:
+            raise ValueError("conditioning_embedding_out_channels must have four entries")
+        self.device = torch.device(device if str(device) != "cuda" else f"cuda:{torch.cuda.current_device()}")
+        self._arch = arch_desc(cfg)
+        h = C.c_void_p()
+        cc = (C.c_int * 4)(*self.cond_channels)
+        with torch.cuda.device(self.device):
+            _create(lambda: self.lib.gdf_controlnet_create(C.byref(self._arch), C.byref(cc), self.conditioning_channels, C.byref(h)),
+                    "controlnet_create")
+        self.handle = h
+        self.stream_fp32 = bool(stream_fp32)
+        self.feature_store = None
+        self._plans = {}
+        self.dtype = torch.float16
+        self.config = types.SimpleNamespace(conditioning_embedding_out_channels=self.cond_channels, conditioning_channels=self.conditioning_channels,
+                                            global_pool_conditions=False, cross_attention_dim=cfg["cross_attention_dim"])
+
+    def _is_norm(self, name):
+        return ".norm" in name
+
+    def residual_layout(self, batch, lat_h, lat_w):
+        return residual_layout(self.cfg, batch, lat_h, lat_w)
+
+    def _plan(self, batch, h, w, n_ctx, shared_ctx=False, split=0, direct=False):
+        """direct: the plan of the calls that write into a caller's block (out=); its result sets hold no block of their own"""
+        key = (batch, h, w, n_ctx, self.stream_fp32, bool(shared_ctx), split, bool(direct))
+        p = self._plans.get(key)
+        if p is None:
+            opts = PlanOpts(int(self.stream_fp32), 0)
+            opts.reserved[0] = int(bool(shared_ctx))
+            opts.reserved[1] = 1 if split == SPLIT_ALL else (split << 8)
+            ph = C.c_void_p()
+            _check(self.lib.gdf_controlnet_plan_create(self.handle, batch, h, w, n_ctx, C.byref(opts), C.byref(ph)), "controlnet_plan_create")
+            p = _Plan(self.lib, ph)
+            if len(self._plans) >= 8:
+                self._plans.pop(next(iter(self._plans)))
+            self._plans[key] = p
+        return p
+
+    def forward_raw(self, sample, timestep, encoder_hidden_states, text_embeds=None, time_ids=None, cond=None, shared_ctx=False, split=0,
+                    out=None, eager=False):
+        """-> the residual block: a flat fp16 tensor of residual_layout(B, H, W)[1] bytes (skips in diffusers' order, the mid block's last).
+        cond: the control image (B, conditioning_channels, 8 H, 8 W) in [0, 1], fp16 or fp32.  shared_ctx / split: as NativeUNet's plans
+        (split: a mask of SPLIT_CLASSES).  out: a flat fp16 device tensor of that size — the plan writes straight into it and it is returned."""
+        dev = self.device
+        B, _, H, W = sample.shape
+        if cond is None or cond.dim() != 4 or tuple(cond.shape) != (B, self.conditioning_channels, 8 * H, 8 * W):
+            raise ValueError(f"controlnet_cond must be ({B}, {self.conditioning_channels}, {8 * H}, {8 * W}), got "
+                             f"{None if cond is None else tuple(cond.shape)}")
+        if cond.dtype not in (torch.float16, torch.float32):
+            cond = cond.float()
+        ctx = encoder_hidden_states
+        t = _timestep_on_device(timestep, B, dev)
+        txt = tid = None
+        if self.cfg["addition_embed_text_time"]:
+            if text_embeds is None or time_ids is None:
+                raise ValueError("added_cond_kwargs with text_embeds and time_ids is required for this ControlNet")
+            txt, tid = text_embeds, time_ids
+            pooled = self.cfg["add_in_dim"] - 6 * self.cfg["addition_time_embed_dim"]
+            if tuple(txt.shape) != (B, pooled) or tuple(tid.shape) != (B, 6):
+                raise ValueError(f"text_embeds {tuple(txt.shape)} / time_ids {tuple(tid.shape)} do not match the model "
+                                 f"(expected ({B},{pooled}) / ({B},6))")
+        if ctx.shape[0] != B or ctx.shape[2] != self.cfg["cross_attention_dim"]:
+            raise ValueError("encoder_hidden_states shape mismatch")
+        need = self.residual_layout(B, H, W)[1]
+        if out is not None and (out.dtype != torch.float16 or out.dim() != 1 or out.numel() * 2 != need or not out.is_contiguous()
+                                or out.device != dev or out.data_ptr() % 256):
+            raise ValueError(f"out must be a flat, 256-byte aligned fp16 tensor of {need} bytes on {dev}")
+        plan = self._plan(B, H, W, ctx.shape[1], shared_ctx, int(split), direct=out is not None)
+        f16, f32 = torch.float16, torch.float32
+        inputs = [("sample", sample, f16), ("t", t, f32), ("ctx", ctx, f16), ("txt", txt, f16), ("tid", tid, f32), ("cond", cond, cond.dtype)]
+        code = GDF_F32 if cond.dtype == f32 else GDF_F16
+        lib = self.lib
+
+        def call(staged, hook_ptrs, out_ptr, ws_ptr, stream_ptr):
+            vp = lambda a: C.c_void_p(a.data_ptr() if a is not None else 0)
+            dst = C.c_void_p(out.data_ptr()) if out is not None else out_ptr
+            _check(lib.gdf_controlnet_forward(plan.handle, *[vp(a) for a in staged], code, dst, ws_ptr, stream_ptr), "controlnet_forward")
+        block, _, _ = plan.run(dev, inputs, (128,) if out is not None else (need // 2,), call, eager=eager)
+        return out if out is not None else block
+
+    def views(self, block, batch, lat_h, lat_w):
+        """-> ([NCHW views of the skips' residuals], NCHW view of the mid block's) of a flat block"""
+        v = [block[off // 2:off // 2 + b * c * h * w].view(b, h, w, c).permute(0, 3, 1, 2)
+             for off, (b, c, h, w) in self.residual_layout(batch, lat_h, lat_w)[0]]
+        return v[:-1], v[-1]
+
+    def __call__(self, sample, timestep=None, encoder_hidden_states=None, controlnet_cond=None, conditioning_scale=1.0, guess_mode=False,
+                 added_cond_kwargs=None, return_dict=False, **kwargs):
+        if conditioning_scale != 1 or guess_mode:
+            raise NotImplementedError("the native ControlNet runs conditioning_scale = 1, guess_mode = False (what the reference's extraction uses)")
+        akw = added_cond_kwargs or {}
+        block = self.forward_raw(sample, timestep, encoder_hidden_states, akw.get("text_embeds"), akw.get("time_ids"), controlnet_cond)
+        down, mid = self.views(block, sample.shape[0], sample.shape[2], sample.shape[3])
+        if return_dict:
+            return types.SimpleNamespace(down_block_res_samples=down, mid_block_res_sample=mid)
+        return down, mid
+
+
+def native_controlnet_from(module, device="cuda"):
+    """A NativeControlNet from any object with diffusers' ControlNetModel surface: `.config` and `.state_dict()`."""
+    c = module.config
+    if getattr(c, "global_pool_conditions", False):
+        raise ValueError("global_pool_conditions is not supported by the native ControlNet")
+    if getattr(c, "controlnet_conditioning_channel_order", "rgb") != "rgb":
+        raise ValueError("controlnet_conditioning_channel_order must be 'rgb'")
+    if getattr(c, "class_embed_type", None) is not None:
+        raise ValueError("class_embed_type is not supported by the native ControlNet")
+    cn = NativeControlNet(config_from_diffusers(c), device, tuple(getattr(c, "conditioning_embedding_out_channels", COND_CHANNELS)),
+                          getattr(c, "conditioning_channels", 3))
+    return cn.load_state_dict({k: v for k, v in module.state_dict().items()})
 
 
 # --------------------------------------------------------------------------------------------- #

@@ -59,6 +59,7 @@ int gdf_plan_create(gdf_model* m, int batch, int lat_h, int lat_w, int n_ctx, co
                     const gdf_plan_opts* opts, gdf_plan** out) {
   if (!m || !out || (n_hooks > 0 && !hook_ids)) { set_error("null argument"); return GDF_ERR_ARG; }
   if (m->m->kind != 0) { set_error("gdf_plan_create on a Flux model: use gdf_flux_plan_create"); return GDF_ERR_ARG; }
+  if (m->m->controlnet) { set_error("gdf_plan_create on a ControlNet model: use gdf_controlnet_plan_create"); return GDF_ERR_ARG; }
   gdf_plan_opts o{};
   o.stream_fp32 = 1;
   if (opts) o = *opts;
@@ -254,6 +255,50 @@ int gdf_forward_res(gdf_plan* p, const void* latents, const float* timesteps, co
   if (!residuals) { set_error("gdf_forward_res: residuals is NULL"); return GDF_ERR_ARG; }
   return plan_forward(p->p, *p->p.model, latents, timesteps, ctx, add_text_embeds, add_time_ids, hook_out, noise_pred,
                       workspace, (hipStream_t)stream, nullptr, nullptr, nullptr, 0, residuals);
+}
+
+// ---- ControlNet model (include/gdf_control.h) ----
+int gdf_controlnet_create(const gdf_arch_desc* arch, const int cond_channels[4], int conditioning_channels, gdf_model** out) {
+  if (!arch || !cond_channels || !out) { set_error("null argument"); return GDF_ERR_ARG; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device: libgdf has no CPU fallback"); return GDF_ERR_HIP; }
+  Model* m = controlnet_create(*arch, cond_channels, conditioning_channels);
+  if (!m) return GDF_ERR_ARG;
+  *out = new gdf_model{m};
+  return GDF_OK;
+}
+int gdf_controlnet_layout(const gdf_arch_desc* arch, const int cond_channels[4], int conditioning_channels, gdf_model** out) {
+  if (!arch || !cond_channels || !out) { set_error("null argument"); return GDF_ERR_ARG; }
+  Model* m = controlnet_create(*arch, cond_channels, conditioning_channels, /*layout_only=*/true);
+  if (!m) return GDF_ERR_ARG;
+  *out = new gdf_model{m};
+  return GDF_OK;
+}
+int gdf_controlnet_plan_create(gdf_model* m, int batch, int lat_h, int lat_w, int n_ctx, const gdf_plan_opts* opts, gdf_plan** out) {
+  if (!m || !out) { set_error("null argument"); return GDF_ERR_ARG; }
+  if (m->m->kind != 0 || !m->m->controlnet) { set_error("gdf_controlnet_plan_create needs a model of gdf_controlnet_create"); return GDF_ERR_ARG; }
+  if (!m->m->weights) { set_error("this model is a parameter table without weights (gdf_controlnet_layout)"); return GDF_ERR_STATE; }
+  gdf_plan_opts o{};
+  o.stream_fp32 = 1;
+  if (opts) o = *opts;
+  o.early_exit = 0; o.reserved[3] = 0;        // no hooks to stop behind, and the block is written, not read
+  gdf_plan* p = new gdf_plan();
+  p->owner = m;
+  p->p.model = m->m;
+  const int rc = plan_build(*m->m, p->p, batch, lat_h, lat_w, n_ctx, nullptr, 0, o, false);
+  if (rc != GDF_OK) { delete p; return rc; }
+  *out = p;
+  return GDF_OK;
+}
+int gdf_controlnet_forward(gdf_plan* p, const void* latents, const float* timesteps, const void* ctx, const void* add_text_embeds,
+                           const float* add_time_ids, const void* cond_image, int cond_dtype, void* residual_block_out, void* workspace,
+                           void* stream) {
+  if (!p) { set_error("null plan"); return GDF_ERR_ARG; }
+  return controlnet_forward(p->p, *p->p.model, latents, timesteps, ctx, add_text_embeds, add_time_ids, cond_image, cond_dtype,
+                            residual_block_out, workspace, (hipStream_t)stream);
+}
+size_t gdf_controlnet_residual_bytes(const gdf_plan* p) {
+  return (p && p->p.model->kind == 0 && p->p.model->controlnet) ? gdf_residual_bytes(&p->p.model->arch, p->p.batch, p->p.H, p->p.W) : 0;
 }
 
 // host arithmetic only (no device is touched): tests/test_controlnet_cpu.py calls these without a GPU

@@ -328,6 +328,22 @@ enum { RES_ADD_MAX = 16 };
 struct ResAddDesc { half_t* dst; int ld; int lo; const half_t* res; int rows; int C; };
 hipError_t launch_residual_add(const ResAddDesc* d, int n, hipStream_t s);
 
+// The conditioning embedding's 3x3 convs, padding 1 (csrc/cond_embed.hip): x NHWC fp16 [B][H][W][ldx >= Cin], w as launch_cond_pack_weights packs
+// it, out NHWC fp16 [B][OH][OW][ldo >= Cout], OH = (H - 1) / stride + 1; v = acc + bias, silu: v * sigmoid(v), add: v += out's old value; one
+// fp16 rounding.  (Cin, Cout) one of cond_conv_ok()'s pairs, stride 1 | 2 (even H and W at 2), ldx / ldo multiples of 8, pointers 16-byte aligned.
+// OH, OW, M and Kpad are filled in by the launcher.
+struct CondConvParams {
+  const half_t* x; const half_t* w; const float* bias; half_t* out;
+  int B, H, W, OH, OW, Cin, ldx, Cout, ldo, stride, silu, add, Kpad; unsigned M;
+};
+bool cond_conv_ok(int Cin, int Cout);
+size_t cond_conv_weight_bytes(int Cin, int Cout);
+hipError_t launch_cond_conv3x3(const CondConvParams& p, hipStream_t s);
+// OIHW src[O][I][3][3] (dtype 0 fp16, 1 fp32, 2 bf16) -> fp16 [k / 8][O][8], k = tap * cin_pad + c, zero padded to a multiple of 32 in k
+hipError_t launch_cond_pack_weights(const void* src, int dtype, half_t* dst, int O, int I, int cin_pad, hipStream_t s);
+// control image NCHW (B, C <= 8, H, W) fp16 (dtype 0) or fp32 (1) -> NHWC pixels of 8 fp16 channels, channels from C up zero
+hipError_t launch_cond_pack_image(const void* x, int dtype, int B, int C, int H, int W, half_t* nhwc8, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------------
 // weight re-layout (model load time)
 // ------------------------------------------------------------------------------------------------

@@ -84,7 +84,8 @@ struct ModelBuilder : WeightBuilder {
     return v;
   }
 
-  void build() {
+  // cond != nullptr: a ControlNetModel — the same walk up to the mid block, then the conditioning embedding and the 1x1 convs instead of the up path
+  void build(const int* cond = nullptr, int cond_in = 0) {
     const GdfArch& a = m.arch;
     const int L = a.n_levels, nl = a.layers_per_block, te = a.time_embed_dim;
     const int* boc = a.block_out_channels;
@@ -103,7 +104,7 @@ struct ModelBuilder : WeightBuilder {
     for (int lv = 0; lv < L; ++lv) {
       if (!a.has_attn[lv] && lv != L - 1) continue;
       int cnt = 0;
-      if (a.has_attn[lv]) cnt += (nl + (nl + 1)) * a.transformer_layers[lv];
+      if (a.has_attn[lv]) cnt += (cond ? nl : nl + (nl + 1)) * a.transformer_layers[lv];
       if (lv == L - 1) cnt += a.transformer_layers[lv];
       if (!cnt) continue;
       KvGroup* g = nullptr;
@@ -134,6 +135,30 @@ struct ModelBuilder : WeightBuilder {
     m.mid_res0 = resnet("mid_block.resnets.0", cm, cm);
     m.mid_vit = vit("mid_block.attentions.0", cm, a.heads[L - 1], a.transformer_layers[L - 1]);
     m.mid_res1 = resnet("mid_block.resnets.1", cm, cm);
+    if (cond) {
+      m.controlnet = true; m.cond_image_channels = cond_in;
+      auto cconv = [&](const std::string& n, int co, int ci_src, int stride, int silu) {
+        CondW w; w.cin = (ci_src + 7) / 8 * 8; w.cout = co; w.stride = stride; w.silu = silu;
+        w.w = take(cond_conv_weight_bytes(w.cin, co)); w.b = take(co * 4);
+        reg(n + ".weight", {co, ci_src, 3, 3}, PK_COND, w.w, co, ci_src, w.cin); reg(n + ".bias", {co}, PK_VEC, w.b);
+        m.cond_embed.push_back(w);
+      };
+      const std::string ce = "controlnet_cond_embedding";
+      cconv(ce + ".conv_in", cond[0], cond_in, 1, 1);
+      for (int i = 0; i < 3; ++i) {
+        cconv(ce + ".blocks." + std::to_string(2 * i), cond[i], cond[i], 1, 1);
+        cconv(ce + ".blocks." + std::to_string(2 * i + 1), cond[i + 1], cond[i], 2, 1);
+      }
+      cconv(ce + ".conv_out", boc[0], cond[3], 1, 0);
+      const ResidualLayout rl = residual_layout(a, 1, 1 << GDF_MAX_LEVELS, 1 << GDF_MAX_LEVELS);
+      for (size_t k = 0; k + 1 < rl.t.size(); ++k)
+        m.zero_convs.push_back(lin("controlnet_down_blocks." + std::to_string(k), rl.t[k].C, rl.t[k].C, true, true));
+      m.zero_convs.push_back(lin("controlnet_mid_block", cm, cm, true, true));
+      m.temb_all = lin_alloc(m.temb_total, te, true);
+      for (auto& t : m.temb_regs) lin_rows(t.name, m.temb_all, t.cout, t.off, false, true);
+      m.weight_bytes = cur;
+      return;
+    }
     int prev = boc[L - 1];
     for (int i = 0; i < L; ++i) {
       LevelW lw;
@@ -163,7 +188,17 @@ struct ModelBuilder : WeightBuilder {
   }
 };
 
-Model* model_create(const GdfArch& arch) {
+static Model* model_create_impl(const GdfArch& arch, const int* cond, int cond_in, bool layout_only);
+Model* model_create(const GdfArch& arch) { return model_create_impl(arch, nullptr, 0, false); }
+Model* controlnet_create(const GdfArch& arch, const int cond_channels[4], int conditioning_channels, bool layout_only) {
+  static const int want[4] = {16, 32, 96, 256};
+  if (!cond_channels || memcmp(cond_channels, want, sizeof want) != 0) {
+    set_error("conditioning_embedding_out_channels must be (16, 32, 96, 256): the conditioning-embedding kernel has no other widths"); return nullptr;
+  }
+  if (conditioning_channels < 1 || conditioning_channels > 8) { set_error("conditioning_channels must be 1..8"); return nullptr; }
+  return model_create_impl(arch, cond_channels, conditioning_channels, layout_only);
+}
+static Model* model_create_impl(const GdfArch& arch, const int* cond, int cond_in, bool layout_only) {
   if (arch.n_levels < 2 || arch.n_levels > 4) { set_error("n_levels must be 2..4"); return nullptr; }
   for (int i = 0; i < arch.n_levels; ++i) {
     if (arch.block_out_channels[i] % 64) { set_error("block_out_channels must be multiples of 64"); return nullptr; }
@@ -179,7 +214,8 @@ Model* model_create(const GdfArch& arch) {
   Model* m = new Model();
   m->arch = arch;
   ModelBuilder b(*m);
-  b.build();
+  b.build(cond, cond_in);
+  if (layout_only) return m;                   // the parameter table alone (gdf_controlnet_layout): no device is touched, weights stays null
   {
     CaptureExclusive g;
     const hipError_t me = hipMalloc(&m->weights, m->weight_bytes);
@@ -189,6 +225,7 @@ Model* model_create(const GdfArch& arch) {
     }
     hipMemset(m->weights, 0, m->weight_bytes);
   }
+  if (m->controlnet) return m;                 // a ControlNet registers no hooks
   // hook ids (dry plan walk)
   PlanOpts o{}; o.stream_fp32 = 1;
   Plan dry;
@@ -217,6 +254,7 @@ int model_set_param(Model* m, const char* name, const void* src, int dtype, hipS
   auto it = m->index.find(name);
   if (it == m->index.end()) { set_error(std::string("unknown parameter: ") + name); return GDF_ERR_ARG; }
   ParamRec& p = m->params[it->second];
+  if (!m->weights) { set_error("this model is a parameter table without weights (gdf_controlnet_layout)"); return GDF_ERR_STATE; }
   if (dtype != GDF_F16 && dtype != GDF_F32 && dtype != GDF_BF16) { set_error("dtype must be GDF_F16, GDF_F32 or GDF_BF16"); return GDF_ERR_ARG; }
   const int f32 = dtype;                       // source dtype code of the relayout kernels: 0 fp16, 1 fp32, 2 bf16
   char* base = (char*)m->weights;
@@ -227,6 +265,7 @@ int model_set_param(Model* m, const char* name, const void* src, int dtype, hipS
     case PK_VEC_GEGLU: e = launch_relayout_vec(src, f32, (float*)(base + p.dst), p.a0, 0, geglu_group(p.a0), s); break;
     case PK_CONV3: e = launch_relayout_conv(src, f32, (half_t*)(base + p.dst), p.a0, p.a1, 9, p.a1, 9, s, 64); break;
     case PK_CONV_IN: e = launch_relayout_conv(src, f32, (half_t*)(base + p.dst), p.a0, p.a1, 9, 8, 16, s); break;
+    case PK_COND: e = launch_cond_pack_weights(src, f32, (half_t*)(base + p.dst), p.a0, p.a1, p.a2, s); break;
     case PK_ROWS:
       e = launch_relayout_rows(src, f32, (half_t*)(base + p.dst), p.a0, p.a1, p.a2, 0, s, m->bf16);
       if (e == hipSuccess && m->fp8 && (p.a1 % 128) == 0)       // 'fp8-mx' plans: the e4m3 copy + per-output-channel scales of these rows
@@ -467,7 +506,8 @@ struct B : PlanBuilder {   // UNet op program
     const int px = pxc(SP_STREAM); const bool sps = spl(SP_STREAM);
     struct Cat { size_t off, bytes; int ch, cs, H, W; };
     std::vector<Cat> cats;        // in up-path consumption order
-    {
+    const bool cn = m.controlnet; // a ControlNet has no up path: its skips are ordinary activations, each followed by its 1x1 conv into the residual block
+    if (!cn) {
       int prev = boc[L - 1];
       int hh = H >> (L - 1), ww = W >> (L - 1);
       for (int i = 0; i < L; ++i) {
@@ -486,10 +526,52 @@ struct B : PlanBuilder {   // UNet op program
     struct ResDst { size_t off; int ld, lo, C; size_t rows; };
     std::vector<ResDst> res_dst;  // every skip in production order: where the ControlNet residual adds land (below)
     auto skip_dst = [&](int C, int hh, int ww) -> Act {
+      if (cn) return new_act(C, hh, ww, true);
       const Cat& c = cats[n_skips - 1 - skip_idx++];
       res_dst.push_back({c.off + (size_t)c.ch * 2, (c.ch + c.cs) * px, sps ? c.ch + c.cs : 0, C, (size_t)Bn * hh * ww});
       return view_act(ws(c.off + (size_t)c.ch * 2), (c.ch + c.cs) * px, C, hh, ww, true, sps ? c.ch + c.cs : 0);
     };
+
+    // ---- ControlNet: the conditioning embedding of the control image (B, 3, 8 H, 8 W), always plain fp16 (an 8-bit image is exact in fp16), and the
+    //      1x1 conv behind every skip, written straight into the caller's residual block at residual_layout's offsets ----
+    const ResidualLayout rl_out = cn ? residual_layout(a, Bn, H, W) : ResidualLayout{};
+    size_t n_zero = 0;
+    auto zero_conv = [&](const Act& x) {
+      if (!cn || stop) return;
+      if (n_zero >= rl_out.t.size() || n_zero >= m.zero_convs.size() || rl_out.t[n_zero].C != x.C || rl_out.t[n_zero].H != x.H || rl_out.t[n_zero].W != x.W) {
+        set_error("residual layout does not match the skip list"); bad = true; return;
+      }
+      Epi e; e.bias = wt(m.zero_convs[n_zero].b); e.has_bias = true;
+      e.out16 = Ref{BUF_RES_OUT, rl_out.t[n_zero].off}; e.has_o16 = true; e.ldo16 = x.C;
+      reads_image(e, x);
+      gemm("control_out", x.h, x.ld, rows(x), m.zero_convs[n_zero], x.C, x.C, 0, e, x.lo);
+      ++n_zero;
+    };
+    size_t cemb = NPOS; const size_t cemb_b = (size_t)Bn * H * W * boc[0] * 2;
+    if (cn) {
+      int ih = 8 * H, iw = 8 * W;
+      size_t src_b = (size_t)Bn * ih * iw * 16, src = tmp(src_b);
+      const int cic = m.cond_image_channels;
+      op("cond_pack_image", 0, [=](const Bind& b, hipStream_t s) {
+        if (!b.base[BUF_COND]) return hipErrorInvalidValue;
+        return launch_cond_pack_image(b.base[BUF_COND], b.f[1] != 0.f ? 1 : 0, Bq, cic, ih, iw, (half_t*)b.ws(src), s);
+      }, "cond_pack_image_kernel");
+      for (const CondW& w : m.cond_embed) {
+        const int oh = ih / w.stride, ow = iw / w.stride;
+        const size_t dst_b = (size_t)Bn * oh * ow * w.cout * 2, dst = tmp(dst_b);
+        const Ref Wr = wt(w.w), br = wt(w.b);
+        const int cin = w.cin, cout = w.cout, st = w.stride, silu = w.silu, hh0 = ih, ww0 = iw;
+        op("cond_conv", 2.0 * (double)Bn * oh * ow * cout * 9 * cin, [=](const Bind& b, hipStream_t s) {
+          CondConvParams q{};
+          q.x = (const half_t*)b.ws(src); q.w = (const half_t*)b.p(Wr); q.bias = (const float*)b.p(br); q.out = (half_t*)b.ws(dst);
+          q.B = Bq; q.H = hh0; q.W = ww0; q.Cin = cin; q.ldx = cin; q.Cout = cout; q.ldo = cout; q.stride = st; q.silu = silu;
+          return launch_cond_conv3x3(q, s);
+        }, "cond_conv3x3_kernel");
+        untmp(src, src_b);
+        src = dst; src_b = dst_b; ih = oh; iw = ow;
+      }
+      cemb = src;                  // conv_out's image: fp16 [B H W][C0], added by conv_in's epilogue below
+    }
 
     // ---- conv_in ----
     const size_t lat8_b = (size_t)Bn * H * W * 16;
@@ -506,6 +588,8 @@ struct B : PlanBuilder {   // UNet op program
     Act cur = skip_dst(boc[0], H, W);
     if (!stop) {
       Epi e; e.bias = wt(m.conv_in.b); e.has_bias = true; out_to(e, cur);
+      // `sample = conv_in(sample) + controlnet_cond_embedding(cond)`: one fp32 add in the epilogue; image and fp32 master hold the same sum
+      if (cn) { e.res16 = ws(cemb); e.has_r16 = true; e.ldres = boc[0]; }
       Epi ee = e;
       const Ref Wr = wt(m.conv_in.w); const int N = boc[0];
       const size_t M = (size_t)Bn * H * W;
@@ -520,7 +604,11 @@ struct B : PlanBuilder {   // UNet op program
       }, gk.o16_lo > 0 ? gemm_kernel_name(gk) : nullptr);
     }
     untmp(lat8, lat8_b);
+    if (cn) untmp(cemb, cemb_b);
     gather("unet-after-conv-in", cur);                                                      // :1172-1173
+    zero_conv(cur);
+    // the input of a consumed layer: a UNet keeps its fp16 image (it IS the skip slice of a concat buffer), a ControlNet is done with it
+    auto consumed = [&](Act& x) { if (cn) free_act(x); else free_master(x); };
 
     // ---- down path ----
     int hh = H, ww = W;
@@ -532,7 +620,7 @@ struct B : PlanBuilder {   // UNet op program
         if (attn) {
           Act mid = new_act(boc[lv], hh, ww, true);
           resnet(id, lw.res[r], cur, mid);
-          free_master(cur);
+          consumed(cur);
           Act nxt = skip_dst(boc[lv], hh, ww);
           vit(id + "-vit", lw.vit[r], mid, nxt);
           free_act(mid);
@@ -540,33 +628,43 @@ struct B : PlanBuilder {   // UNet op program
         } else {
           Act nxt = skip_dst(boc[lv], hh, ww);
           resnet(id, lw.res[r], cur, nxt);
-          free_master(cur);
+          consumed(cur);
           cur = nxt;
         }
+        zero_conv(cur);
       }
       if (lw.has_sampler && !stop) {
         Act nxt = skip_dst(boc[lv], hh / 2, ww / 2);
         Epi e; e.bias = wt(lw.sampler.b); e.has_bias = true; out_to(e, nxt);
         conv3("downsample", cur.h, cur.ld, cur.C, hh, ww, 2, false, lw.sampler, e, spl(SP_SAMPLER) ? cur.lo : 0);  // downsampling.py:132-152
-        free_master(cur);
+        consumed(cur);
         cur = nxt; hh /= 2; ww /= 2;
         gather("down-level" + std::to_string(lv) + "-downsampler-out", cur);
+        zero_conv(cur);
       }
     }
     // ---- mid ----
     if (!stop) {
       Act a0 = new_act(boc[L - 1], hh, ww, true);
       resnet("mid-repeat0", m.mid_res0, cur, a0);
-      free_master(cur);
+      consumed(cur);
       Act a1 = new_act(boc[L - 1], hh, ww, true);
       vit("mid-vit", m.mid_vit, a0, a1);
       free_act(a0);
       // mid output feeds cats[0] channel slice [0, ch)
-      Act a2 = view_act(ws(cats[0].off), (cats[0].ch + cats[0].cs) * px, boc[L - 1], hh, ww, false, sps ? cats[0].ch + cats[0].cs : 0);
+      Act a2 = cn ? new_act(boc[L - 1], hh, ww, false)
+                  : view_act(ws(cats[0].off), (cats[0].ch + cats[0].cs) * px, boc[L - 1], hh, ww, false, sps ? cats[0].ch + cats[0].cs : 0);
       resnet("mid-repeat1", m.mid_res1, a1, a2);
       free_act(a1);
       cur = a2;
-      res_dst.push_back({cats[0].off, a2.ld, a2.lo, a2.C, rows(a2)});
+      if (!cn) res_dst.push_back({cats[0].off, a2.ld, a2.lo, a2.C, rows(a2)});
+    }
+    if (cn) {                        // ControlNetModel.forward ends here: the mid block's 1x1 conv is the last tensor of the block
+      zero_conv(cur);
+      if (n_zero != rl_out.t.size()) { set_error("residual layout does not match the skip list"); bad = true; }
+      free_act(cur);
+      (void)tsin; (void)t1; (void)emb;
+      return;
     }
     // ---- ControlNet residuals (unet_2d_condition.py:1236-1245, 1269-1270) ----
     // A skip is not a copy: it IS the skip slice of its concat buffer, and the down path went on reading that memory (the last skip is the
@@ -705,7 +803,7 @@ int plan_build(const Model& m, Plan& P, int batch, int H, int W, int n_ctx, cons
     }
   }
   P.batch = batch; P.H = H; P.W = W; P.n_ctx = n_ctx; P.opts = opts;
-  P.takes_res = opts.reserved[3] != 0;
+  P.takes_res = opts.reserved[3] != 0 && !m.controlnet;
   B b(m, P, dry, opts);
   b.Bn = batch; b.n_ctx = n_ctx;
   // row N1's statistics half (round 5, ON by default): the resnet convs emit the GroupNorm partial sums of the fp16 image they store (gemm_body<..., GNS>:
@@ -795,6 +893,7 @@ int plan_forward(Plan& P, const Model& m, const void* lat, const float* t, const
                  const float* tid, void* const* hook_out, void* noise, void* ws, hipStream_t s, float* ms,
                  const char** names, double* flops, int cap, const void* residuals) {
   if (m.kind != 0) { set_error("gdf_forward on a Flux model: use gdf_flux_forward"); return GDF_ERR_STATE; }
+  if (m.controlnet) { set_error("this is a ControlNet plan: run it with gdf_controlnet_forward"); return GDF_ERR_STATE; }
   if (residuals && !P.takes_res) { set_error("gdf_forward_res needs a plan created with gdf_plan_opts.reserved[3] = 1"); return GDF_ERR_STATE; }
   if (!residuals && P.takes_res) { set_error("this plan adds ControlNet residuals: run it with gdf_forward_res"); return GDF_ERR_STATE; }
   if (((uintptr_t)residuals & 255) != 0) { set_error("the residual block must be 256-byte aligned"); return GDF_ERR_ARG; }
@@ -809,6 +908,23 @@ int plan_forward(Plan& P, const Model& m, const void* lat, const float* t, const
   b.base[BUF_NOISE] = (char*)noise;
   b.base[BUF_RES] = (char*)residuals;
   return plan_run(P, b, s, ms, names, flops, cap);
+}
+
+int controlnet_forward(Plan& P, const Model& m, const void* lat, const float* t, const void* ctx, const void* txt, const float* tid,
+                       const void* cond, int cond_dtype, void* res_out, void* ws, hipStream_t s) {
+  if (m.kind != 0 || !m.controlnet) { set_error("gdf_controlnet_forward needs a plan created with gdf_controlnet_plan_create"); return GDF_ERR_STATE; }
+  if (m.n_set != (int)m.params.size()) { set_error("model weights incomplete"); return GDF_ERR_STATE; }
+  if (!lat || !t || !ctx || !ws || !cond || !res_out) { set_error("null input pointer"); return GDF_ERR_ARG; }
+  if (m.arch.addition_embed_text_time && (!txt || !tid)) { set_error("this ControlNet needs add_text_embeds and add_time_ids"); return GDF_ERR_ARG; }
+  if (cond_dtype != GDF_F16 && cond_dtype != GDF_F32) { set_error("the control image is GDF_F16 or GDF_F32"); return GDF_ERR_ARG; }
+  if (((uintptr_t)res_out & 255) != 0) { set_error("the residual block must be 256-byte aligned"); return GDF_ERR_ARG; }
+  if (((uintptr_t)cond & (cond_dtype == GDF_F32 ? 3 : 1)) != 0) { set_error("misaligned control image"); return GDF_ERR_ARG; }
+  Bind b;
+  b.base[BUF_WS] = (char*)ws; b.base[BUF_WT] = (char*)m.weights; b.base[BUF_LAT] = (char*)lat; b.base[BUF_T] = (char*)t;
+  b.base[BUF_CTX] = (char*)ctx; b.base[BUF_TXT] = (char*)txt; b.base[BUF_TID] = (char*)tid;
+  b.base[BUF_COND] = (char*)cond; b.base[BUF_RES_OUT] = (char*)res_out;
+  b.f[1] = cond_dtype == GDF_F32 ? 1.f : 0.f;        // part of the graph key: the pack kernel reads the image by this type
+  return plan_run(P, b, s, nullptr, nullptr, nullptr, 0);
 }
 
 // ---- explicit graph construction (launch.h): the recorder of the calling thread, kernel / event-record nodes in one chain ----

@@ -31,9 +31,12 @@ struct BlockW { NormW ln1, ln2, ln3; LinW qkv, o1, q2, kv2, o2, ff1, ff2; int kv
 // text K/V projection weights of all transformer blocks with the same width live contiguously: one grouped GEMM per width
 struct KvGroup { int C = 0, count = 0, next = 0; size_t base = 0, stride = 0; };
 struct VitW { NormW gn; LinW pin, pout; std::vector<BlockW> blocks; int c = 0, heads = 0; };
+// one conv of a ControlNet's conditioning embedding (cond_embed.hip): fp16 [9 cin / 8][cout][8] (k padded to 32), fp32 bias
+struct CondW { size_t w = 0, b = 0; int cin = 0, cout = 0, stride = 1, silu = 1; };
 struct LevelW { std::vector<ResnetW> res; std::vector<VitW> vit; std::vector<int> skip_c; bool has_sampler = false; ConvW sampler; };
 
-enum ParamKind { PK_VEC, PK_VEC_OFF, PK_VEC_GEGLU, PK_CONV3, PK_CONV_IN, PK_ROWS, PK_ROWS_GEGLU, PK_ROWS_PADK };
+enum ParamKind { PK_VEC, PK_VEC_OFF, PK_VEC_GEGLU, PK_CONV3, PK_CONV_IN, PK_ROWS, PK_ROWS_GEGLU, PK_ROWS_PADK,
+                 PK_COND /* a conditioning-embedding conv: a0 = Cout, a1 = Cin of the checkpoint, a2 = Cin of the kernel (launch_cond_pack_weights) */ };
 struct ParamRec {
   std::string name; int ndim = 0; int64_t shape[4] = {0, 0, 0, 0};
   int kind = 0; size_t dst = 0; int a0 = 0, a1 = 0, a2 = 0; bool set = false;
@@ -115,6 +118,12 @@ struct Model {
   NormW norm_out;
   std::vector<std::string> hook_names;
   std::vector<KvGroup> kv_groups;
+  // ControlNetModel (kind 0 with this flag; gdf_control.h): the UNet's conv_in, embeddings, down and mid blocks, plus the conditioning embedding
+  // (conv_in, blocks.0..5, conv_out) and one 1x1 conv per skip tensor and for the mid block's output; no up path, no hooks
+  bool controlnet = false;
+  std::vector<CondW> cond_embed;
+  std::vector<LinW> zero_convs;               // controlnet_down_blocks.k, then controlnet_mid_block (the order of residual_layout)
+  int cond_image_channels = 0;
 };
 
 // ---- plan ----------------------------------------------------------------------------------------
@@ -123,7 +132,9 @@ struct Model {
 // SAMPLE: the caller's state block of a guided sampling run (gdf_sample, sample_layout); a slot of its OWN, which only plan_sample fills —
 // the executor appends the guided update wherever it is set, so it must never alias an input of another front end
 // RES: the caller's ControlNet residual block (gdf_forward_res, residual_layout); null on every other call
-enum { BUF_WS = 0, BUF_WT, BUF_LAT, BUF_T, BUF_CTX, BUF_TXT, BUF_TID, BUF_NOISE, BUF_IDS_IMG, BUF_IDS_TXT, BUF_SAMPLE, BUF_RES, BUF_COUNT };
+// COND / RES_OUT: a ControlNet plan's control image and the residual block it WRITES (gdf_controlnet_forward); null on every other call
+enum { BUF_WS = 0, BUF_WT, BUF_LAT, BUF_T, BUF_CTX, BUF_TXT, BUF_TID, BUF_NOISE, BUF_IDS_IMG, BUF_IDS_TXT, BUF_SAMPLE, BUF_RES, BUF_COND, BUF_RES_OUT,
+       BUF_COUNT };
 enum { BUF_X32 = BUF_IDS_IMG };                 // UNet trajectory (gdf_trajectory): the caller's fp32 master latents; null on a plain forward
 enum { BUF_HOOK0 = 1 << 16 };                   // Ref.buf = BUF_HOOK0 + slot: the caller's hook buffer `slot` (an op's output IS the hook)
 struct Ref { int buf = BUF_WS; size_t off = 0; };
@@ -192,6 +203,10 @@ int plan_set_timing(Plan& P, const char* label);
 int plan_read_timing(Plan& P, double* ms, long* launches, double* flops);
 
 Model* model_create(const GdfArch& arch);
+// a ControlNetModel over the encoder half of `arch` (include/gdf_control.h)
+Model* controlnet_create(const GdfArch& arch, const int cond_channels[4], int conditioning_channels, bool layout_only = false);
+int controlnet_forward(Plan& P, const Model& m, const void* lat, const float* t, const void* ctx, const void* txt, const float* tid,
+                       const void* cond, int cond_dtype, void* res_out, void* ws, hipStream_t s);
 void model_destroy(Model* m);
 int model_set_param(Model* m, const char* name, const void* src, int dtype, hipStream_t s);
 int plan_build(const Model& m, Plan& P, int batch, int H, int W, int n_ctx, const char* const* ids, int n_ids,

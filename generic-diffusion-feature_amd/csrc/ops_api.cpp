@@ -456,6 +456,36 @@ int gdf_op_residual_add(const gdf_residual_add_item* items, int n, void* stream)
   return fin(launch_residual_add(d, n, (hipStream_t)stream), "residual_add");
 }
 
+int gdf_op_cond_conv3x3(const void* x, int B, int H, int W, int Cin, int ldx, const void* w_packed, const float* bias, int Cout, int stride,
+                        int silu, void* out, int ldo, int add_into, void* stream) {
+  auto bad = [](const char* msg) { set_error(std::string("gdf_op_cond_conv3x3: ") + msg); return GDF_ERR_ARG; };
+  if (!cond_conv_ok(Cin, Cout)) return bad("(Cin, Cout) is none of 8->16, 16->16, 16->32, 32->32, 32->96, 96->96, 96->256, 256->64n");
+  if (B < 1 || H < 1 || W < 1) return bad("empty image");
+  if (stride != 1 && stride != 2) return bad("stride is 1 or 2");
+  if (stride == 2 && ((H | W) & 1)) return bad("stride 2 needs even H and W");
+  if (ldx < Cin || ldo < Cout) return bad("leading dimension smaller than the channel count");
+  if ((ldx & 7) || (ldo & 7)) return bad("leading dimensions must be multiples of 8");
+  if (!x || !w_packed || !out || (((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)out | (uintptr_t)bias) & 15)) return bad("null or misaligned pointer (16 bytes)");
+  if ((size_t)B * ((H - 1) / stride + 1) * ((W - 1) / stride + 1) >= (1ull << 31)) return bad("2^31 output pixels or more");
+  CondConvParams p{};
+  p.x = (const half_t*)x; p.w = (const half_t*)w_packed; p.bias = bias; p.out = (half_t*)out;
+  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.ldx = ldx; p.Cout = Cout; p.ldo = ldo; p.stride = stride; p.silu = silu ? 1 : 0; p.add = add_into ? 1 : 0;
+  return fin(launch_cond_conv3x3(p, (hipStream_t)stream), "cond_conv3x3");
+}
+size_t gdf_op_cond_weight_bytes(int Cin, int Cout) { return cond_conv_ok(Cin, Cout) ? cond_conv_weight_bytes(Cin, Cout) : 0; }
+int gdf_op_cond_pack_weights(const void* w_oihw, int src_dtype, void* dst, int Cout, int Cin_src, int Cin, void* stream) {
+  if (!w_oihw || !dst || !cond_conv_ok(Cin, Cout) || Cin_src < 1 || Cin_src > Cin || src_dtype < 0 || src_dtype > 2) {
+    set_error("gdf_op_cond_pack_weights: bad arguments"); return GDF_ERR_ARG;
+  }
+  return fin(launch_cond_pack_weights(w_oihw, src_dtype, (half_t*)dst, Cout, Cin_src, Cin, (hipStream_t)stream), "cond_pack_weights");
+}
+int gdf_op_cond_pack_image(const void* x_nchw, int src_dtype, int B, int C, int H, int W, void* nhwc8, void* stream) {
+  if (!x_nchw || !nhwc8 || B < 1 || H < 1 || W < 1 || C < 1 || C > 8 || (src_dtype != GDF_F16 && src_dtype != GDF_F32) || ((uintptr_t)nhwc8 & 15)) {
+    set_error("gdf_op_cond_pack_image: bad arguments"); return GDF_ERR_ARG;
+  }
+  return fin(launch_cond_pack_image(x_nchw, src_dtype, B, C, H, W, (half_t*)nhwc8, (hipStream_t)stream), "cond_pack_image");
+}
+
 // element type of the 16-bit operands of the MMDiT entry points below, per calling thread (GDF_F16 default)
 static thread_local int g_e16_bf = 0;
 int gdf_op_set_e16(int dtype) {

@@ -9,7 +9,8 @@ the layer-selection config surface (JSON path | dict | None) and the version / d
 In scope are the single-timestep path and, for the UNet versions, `use_ddim_inversion` (the inversion steps run as one device-resident
 trajectory, NativeUNet.trajectory) and `generate`: a classifier-free-guided text-to-image run with background extraction — the hooked
 layers keep the features of the UNet calls named by `set_background_extraction` (reference generate_with_extraction.py) — as one
-device-resident run (NativeUNet.sample).  `denoising_from` and ControlNet are not.
+device-resident run (NativeUNet.sample), and `control=` / `use_control`: ControlNet conditioning of the extraction forward with the
+ControlNet itself a native model (components/control.py, NativeControlNet).  `denoising_from` is not.
 """
 import copy
 import os
@@ -68,10 +69,9 @@ class FeatureExtractor(nn.Module):
                                    # 'vae-out' (which needs the model output) is requested
                  ):
         super().__init__()
-        if control:
-            raise NotImplementedError("control=: the native UNet takes ControlNet residuals (NativeUNet.__call__ with down_block_additional_residuals / "
-                                      "mid_block_additional_residual, gdf_forward_res), but this package has no ControlNet model or "
-                                      "preprocessor of its own yet (DESIGN.md 3.17, 7): run the ControlNet yourself and call pipe.unet")
+        if control and (version == 'flux' or version.startswith('pixart')):
+            raise NotImplementedError("control= exists for the UNet versions ('1-5', '2-1', 'xl', 'pgv2') only: the native ControlNet is the "
+                                      "encoder half of a UNet (include/gdf_control.h)")
         if attention:
             bad = [a for a in attention if a not in ATTENTION_CATEGORIES]
             if bad:
@@ -118,6 +118,11 @@ class FeatureExtractor(nn.Module):
                 raise NotImplementedError("split-operand plans exist for the UNet versions ('1-5', '2-1', 'xl', 'pgv2') only")
         self.pipe = pipe
         self.control_pipe = None
+        if control:                                                                      # reference :62-65
+            if not hasattr(pipe.unet, "residual_buffer"):
+                raise NotImplementedError("control= needs the native UNet (libgdf.so); this pipeline has none")
+            from components.control import ControlNetPipeline
+            self.control_pipe = ControlNetPipeline(pipe, control, device)
         self.attention_store = None
         # (version == 'flux' with attention=[...]: the reference registers an AttentionStore but its flux branch of extract()
         #  returns before the aggregation step (diffusion_feature.py:246-254 vs :492-500), so no 'attn' entry is ever produced —
@@ -180,16 +185,22 @@ class FeatureExtractor(nn.Module):
 
     # ------------------------------------------------------------------------------------------
     def extract(self, prompts, batch_size, image, image_type='image', t=50, denoising_from=None,
-                use_control=False, use_ddim_inversion=False):
+                use_control=False, use_ddim_inversion=False, control_image=None):
         """One single-timestep denoiser forward; returns {layer_id: (B,C,H,W) fp16}.
         image_type: 'image' (list of PIL), 'tensors' ((B,3,h,w) in [-1,1]) or — native extension —
         'latents' (pre-noised latents (B,4,H/8,W/8), skipping the VAE stage).
         use_ddim_inversion (UNet versions): the latents are the image's DDIM inversion up to timestep t instead of its noised encoding
-        (reference :381-386), see _ddim_inverted_latents."""
-        if use_control:
-            raise NotImplementedError("use_control: ControlNet conditioning needs cv2, controlnet_aux and a ControlNet model class, none of which "
-                                      "the native path carries; its UNet side is native — NativeUNet.__call__ accepts the residuals of any "
-                                      "ControlNet (DESIGN.md 3.17)")
+        (reference :381-386), see _ddim_inverted_latents.
+        use_control (UNet versions, an extractor built with control=[...]): the ControlNets see exactly the UNet's inputs and their residuals
+        enter the extraction forward (reference :408-465); the inversion forwards of use_ddim_inversion run without them, as in the reference.
+        control_image — native extension — hands over already-processed control images ((B, 3, h, w) in [0, 1] or PIL) instead of running
+        the preprocessor (cv2 / controlnet_aux) on `image`."""
+        control_pipe = getattr(self, "control_pipe", None) if use_control else None
+        if use_control and control_pipe is None:
+            raise NotImplementedError("use_control: this extractor was built without control=[...], it has no ControlNet to run")
+        if use_control and control_image is None and image_type != 'image':
+            raise ValueError("use_control derives the control images from the PIL images (image_type='image'); with tensors or latents pass "
+                             "control_image=")
         if denoising_from:
             raise NotImplementedError("denoising_from is deprecated upstream and runs there only together with ControlNet (its denoising call "
                                       "reads the ControlNet branch's raw image, reference diffusion_feature.py:394); not native")
@@ -199,6 +210,7 @@ class FeatureExtractor(nn.Module):
                                           "inversion loop calls pipe.unet (components/ddim_inversion.py:31)")
             if image_type == 'latents':
                 raise ValueError("use_ddim_inversion inverts an image: image_type must be 'image' or 'tensors'")
+        raw_image = list(image) if (control_pipe is not None and control_image is None) else None      # the preprocessors' input (reference :433)
         self.feature_store.reset()
         device = self.device
         if self.version == 'flux':                                                       # reference :246-254
@@ -305,9 +317,13 @@ class FeatureExtractor(nn.Module):
             # prompt_embeds.repeat(batch_size, 1, 1) above: ONE prompt for the whole batch -> the text K/V are computed once per call.  (Embeddings
             # that already carried several rows are not that case: the promise is only made for a (1, n, C) prompt.)
             self.pipe.unet.shared_ctx = prompts[0].shape[0] == 1
-        noise_pred = self.pipe.unet(latent_model_input, timestep=t, encoder_hidden_states=prompt_embeds.to(device),
-                                    added_cond_kwargs=added_cond_kwargs, down_block_additional_residuals=None,
-                                    mid_block_additional_residual=None, return_dict=False)[0]
+        if control_pipe is not None:                                                     # reference :408-439 (no classifier-free guidance here)
+            noise_pred = self._controlled_forward(control_pipe, raw_image, control_image, latent_model_input, t, prompt_embeds.to(device),
+                                                  added_cond_kwargs)
+        else:
+            noise_pred = self.pipe.unet(latent_model_input, timestep=t, encoder_hidden_states=prompt_embeds.to(device),
+                                        added_cond_kwargs=added_cond_kwargs, down_block_additional_residuals=None,
+                                        mid_block_additional_residual=None, return_dict=False)[0]
         if self.store_vae_output:                                                        # reference :477-485
             from components.models import native_vae_decoder, scheduler_step_scalars
             a, b = scheduler_step_scalars(self.pipe.scheduler, t)                         # scheduler.step(noise_pred, t, latents)[0]
@@ -319,6 +335,29 @@ class FeatureExtractor(nn.Module):
             self.feature_store.stored_feats['attn'] = aggregate_attention(maps, self.img_size // 8)
             self.pipe.unet.last_extra = {}
         return self.feature_store.stored_feats                                           # :517
+
+    def _controlled_forward(self, control_pipe, raw_image, control_image, latent_model_input, t, prompt_embeds, added_cond_kwargs):
+        """The extraction forward with ControlNet residuals: the ControlNets run on the UNet's own inputs with the UNet plan's shared-ctx
+        promise and operand split, write their block straight into that plan's staged residual buffer (no staging copy), and the UNet runs
+        with it; hooks reach the feature store as in NativeUNet.__call__."""
+        unet = self.pipe.unet
+        ids = unet.requested_ids()
+        have = set(ids)
+        ids = ids + [i for i in unet.extra_hook_ids if i not in have]
+        B, _, H, W = latent_model_input.shape
+        split = unet.split_for(ids, lat=min(H, W))
+        basic = [self._preprocess_basic(r) for r in raw_image] if raw_image is not None else None
+        out = unet.residual_buffer(B, H, W, prompt_embeds.shape[1], ids, unet.shared_ctx)
+        block = control_pipe.generate_control_info(basic, latent_model_input, t, prompt_embeds, added_cond_kwargs, control_image=control_image,
+                                                   shared_ctx=unet.shared_ctx, split=split, out=out)
+        noise, hooks = unet.forward_raw(latent_model_input, t, prompt_embeds, added_cond_kwargs.get("text_embeds"),
+                                        added_cond_kwargs.get("time_ids"), hook_ids=ids, shared_ctx=unet.shared_ctx, residuals=block)
+        unet.last_extra = {k: v for k, v in hooks.items() if k in set(unet.extra_hook_ids)}
+        if unet.feature_store is not None:
+            for hid, tns in hooks.items():
+                if hid in have:
+                    unet.feature_store.store(tns, hid)
+        return noise
 
     def _ddim_inverted_latents(self, image, prompts, prompt_embeds, added_cond_kwargs, t):
         """The reference's `ddim_inversion(self.pipe, image, device, prompts, 100, t)` (:385, components/ddim_inversion.py:7-45) on the native path:
@@ -360,6 +399,9 @@ class FeatureExtractor(nn.Module):
         if self.version == 'flux' or self.version.startswith('pixart'):
             raise NotImplementedError("generate exists for the UNet versions ('1-5', '2-1', 'xl', 'pgv2') only: the device-resident sampler "
                                       "drives pipe.unet")
+        if getattr(self, "control_pipe", None) is not None:
+            raise NotImplementedError("generate with a ControlNet is not native: the device-resident sampler runs the UNet without residuals; "
+                                      "build the extractor without control= to generate")
         if self.attention:
             raise NotImplementedError("generate does not produce the aggregated attention=[...] feature: the reference aggregates its "
                                       "AttentionStore once per extract() call, there is no per-encounter form to match")

@@ -156,6 +156,16 @@ int gdf_residual_count(const gdf_arch_desc* arch);
 size_t gdf_residual_bytes(const gdf_arch_desc* arch, int batch, int lat_h, int lat_w);
 int gdf_residual_info(const gdf_arch_desc* arch, int batch, int lat_h, int lat_w, int i, size_t* offset, int64_t shape[4]);
 
+/* The producer of such a block as a native model: documented in gdf_control.h; declared here as well so that the Python binding table
+ * covers it. */
+int gdf_controlnet_create(const gdf_arch_desc* arch, const int cond_channels[4], int conditioning_channels, gdf_model** out);
+int gdf_controlnet_layout(const gdf_arch_desc* arch, const int cond_channels[4], int conditioning_channels, gdf_model** out);
+int gdf_controlnet_plan_create(gdf_model* m, int batch, int lat_h, int lat_w, int n_ctx, const gdf_plan_opts* opts, gdf_plan** out);
+int gdf_controlnet_forward(gdf_plan* p, const void* latents, const float* timesteps, const void* ctx, const void* add_text_embeds,
+                           const float* add_time_ids, const void* cond_image, int cond_dtype, void* residual_block_out, void* workspace,
+                           void* stream);
+size_t gdf_controlnet_residual_bytes(const gdf_plan* p);
+
 /* A device-resident multi-step latent trajectory: n_steps x (one forward + one scheduler update), e.g. DDIM inversion
  * (/root/reference/feature/components/ddim_inversion.py:19-43).
  *   p             a plan created with ZERO hooks and early_exit = 0 (the reference pauses its feature store meanwhile,

@@ -315,6 +315,26 @@ typedef struct gdf_residual_add_item {
 } gdf_residual_add_item;
 int gdf_op_residual_add(const gdf_residual_add_item* items, int n, void* stream);
 
+/* One launch of cond_conv3x3_kernel (csrc/cond_embed.hip): a 3x3 convolution, padding 1, of the ControlNet conditioning embedding
+ * (`controlnet_cond_embedding` of diffusers' ControlNetModel: conv_in, blocks.0..5, conv_out).
+ *   x         NHWC fp16 [B][H][W][ldx >= Cin], read only
+ *   w_packed  the weights as gdf_op_cond_pack_weights lays them out (gdf_op_cond_weight_bytes bytes): fp16 [k / 8][Cout][8] with
+ *             k = tap * Cin + c, zero padded to a multiple of 32 in k
+ *   bias      fp32 [Cout] or NULL
+ *   out       NHWC fp16 [B][OH][OW][ldo >= Cout], OH = (H - 1) / stride + 1: out = fp16(act(acc + bias)) with fp32 accumulation, act = SiLU
+ *             when silu != 0; add_into != 0: out = fp16(act(acc + bias) + out) (the sum of `conv_in(sample) + controlnet_cond_embedding(cond)`)
+ * (Cin, Cout) is one of 8->16 (the 3-channel image packed to 8), 16->16, 16->32, 32->32, 32->96, 96->96, 96->256, 256->any multiple of 64;
+ * stride 1 or 2, at 2 with even H and W; ldx and ldo multiples of 8, ldx >= Cin, ldo >= Cout; every pointer 16-byte aligned.  Anything else is
+ * an error and nothing is launched.  Columns from Cout up of an out row are not written. */
+int gdf_op_cond_conv3x3(const void* x, int B, int H, int W, int Cin, int ldx, const void* w_packed, const float* bias, int Cout, int stride,
+                        int silu, void* out, int ldo, int add_into, void* stream);
+/* OIHW weights (Cout, Cin_src <= Cin, 3, 3) of dtype src_dtype (0 fp16, 1 fp32, 2 bf16) -> the packed layout; input channels from Cin_src up
+ * are zero (the first layer: Cin_src = 3, Cin = 8). */
+size_t gdf_op_cond_weight_bytes(int Cin, int Cout);
+int gdf_op_cond_pack_weights(const void* w_oihw, int src_dtype, void* dst, int Cout, int Cin_src, int Cin, void* stream);
+/* control image NCHW (B, C <= 8, H, W), fp16 (GDF_F16) or fp32 (GDF_F32) -> NHWC pixels of 8 fp16 channels, channels from C up zero. */
+int gdf_op_cond_pack_image(const void* x_nchw, int src_dtype, int B, int C, int H, int W, void* nhwc8, void* stream);
+
 /* ---- MMDiT (Flux) kernels (reference files cited in csrc/dit.hip, gdf_flux.h) ---- */
 
 /* Element type of the 16-bit operands ("e16": A, W, out16, q/k/v/o, y) of the MMDiT entry points below, per calling thread:
