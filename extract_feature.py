@@ -300,6 +300,15 @@ def init_data_parallel():
     return rank, world, f"cuda:{local}"
 
 
+def use_loader_threads(args, n_thr, device):
+    """The loader-thread input path (tensors from df.preprocess_image) or the serial one (PIL images)?  --control keeps the threads when every
+    choice's preprocessor runs on the device (components/control.py device_preprocessed: the Canny choices read the tensors); a host
+    preprocessor ('depth') wants the PIL images themselves (reference diffusion_feature.py:433) and the serial path hands them over."""
+    from components.control import device_preprocessed
+    return (n_thr > 0 and args.version not in ('flux', 'hunyuan') and not args.show_all_layers
+            and (args.control is None or device_preprocessed(args.control, device)))
+
+
 def main(argv=None):
     from PIL import Image
     args = parse_args(argv)
@@ -345,8 +354,7 @@ def main(argv=None):
     n_thr = min(32, max(2, (os.cpu_count() or 2) // (2 * ranks_here))) if args.loader_threads < 0 else args.loader_threads
     # flux / hunyuan pipelines take PIL images (reference :246-254); the UNet / PixArt versions go through df.preprocess_image, which is what the
     # loader threads run — the SAME function the serial path calls, so the latents are bit-identical either way
-    # (--control: the preprocessors want the PIL images themselves, reference diffusion_feature.py:433 — the serial path hands them over)
-    prefetch = n_thr > 0 and args.version not in ('flux', 'hunyuan') and not args.show_all_layers and args.control is None
+    prefetch = use_loader_threads(args, n_thr, device)
     loader = BatchLoader(paths, starts, hi, args.batch_size, df.preprocess_image, n_thr) if prefetch else None
     ok = False
     try:

@@ -1,8 +1,10 @@
 """ControlNet conditioning on the native path: the reference's ControlNetPipeline (/root/reference/feature/components/controlnet.py:87-136)
 with every model a NativeControlNet (components/native.py, include/gdf_control.h).
 
-What stays on the host, and optional: the preprocessors that turn an ordinary image into a control image (cv2.Canny, controlnet_aux's
-MidasDetector) — imported at first use; `control_image=` hands over already-processed control images and needs neither.
+The preprocessors turn an ordinary image into a control image.  On a HIP device 'canny' / 'canny-xl' run there (device_canny: components/native.py
+canny, csrc/canny.hip — cv2.Canny(image, 100, 200) restated) on the image batch the VAE encoder is about to read; that is the
+product path, with no CPU fallback and whether or not cv2 is installed.  What stays on the host, and optional: controlnet_aux's MidasDetector
+('depth') and, on any other device, cv2.Canny — imported at first use; `control_image=` hands over already-processed control images and needs none.
 What the reference does per call and this does too: preprocess every image, VaeImageProcessor(do_convert_rgb=True, do_normalize=False)
 -> (B, 3, h, w) in [0, 1] `.half()`, run every ControlNet on the UNet's own inputs (conditioning_scale 1, guess_mode off), add the
 residuals of several ControlNets elementwise in fp16.  Here the residuals are ONE flat fp16 block (gdf_forward_res's layout), so the merge is
@@ -45,6 +47,26 @@ def depth_preprocessor():
 PREPROCESSORS = {"canny": canny_preprocessor, "canny-xl": canny_preprocessor, "depth": depth_preprocessor}
 
 
+def device_canny(source):
+    """The device form of canny_preprocessor + control_tensor: `source` — the (B, 3, S, S) tensor in [-1, 1] preprocess_image made (it quantises
+    to the very bytes of the RGB image it came from) or uint8 (B, S, S, 3) image bytes, on the HIP device — -> (B, 3, S, S) fp16 of 0.0 / 1.0,
+    the three-channel edge image divided by 255.  Queued on the current stream."""
+    from components import native
+    return native.canny(source, 100, 200, out='control')
+
+
+DEVICE_PREPROCESSORS = {"canny": device_canny, "canny-xl": device_canny}       # the choices whose preprocessor runs on a HIP device
+
+
+def is_hip_device(device):
+    return torch.device(device).type == "cuda"
+
+
+def device_preprocessed(choices, device="cuda"):
+    """True when every choice's preprocessor runs on `device`: nobody needs the PIL images (the CLI's loader-thread path stays on)"""
+    return bool(choices) and is_hip_device(device) and all(c in DEVICE_PREPROCESSORS for c in choices)
+
+
 def control_tensor(images, height, width):
     """Control images -> (B, 3, height, width) fp16 in [0, 1], as VaeImageProcessor(do_convert_rgb=True, do_normalize=False).preprocess
     followed by `.half()` gives it: PIL images are converted to RGB, resized (lanczos, the processor's default) where their size differs and
@@ -83,6 +105,18 @@ class ControlNetPipeline:
         if len(self.control) != len(self.choices):
             raise ValueError("one model per choice")
         self._pre = {}
+        self.on_device = is_hip_device(device)
+
+    def device_route(self, choice):
+        return self.on_device and choice in DEVICE_PREPROCESSORS
+
+    def needs_pil(self):
+        """some choice's preprocessor runs on the host and wants the PIL images"""
+        return not all(self.device_route(c) for c in self.choices)
+
+    def needs_source(self):
+        """some choice's preprocessor runs on the device and wants the image batch there"""
+        return any(self.device_route(c) for c in self.choices)
 
     def _load(self, pipe, choice, index):
         from components.native import NativeControlNet, native_controlnet_from
@@ -102,8 +136,20 @@ class ControlNetPipeline:
             self._pre[choice] = PREPROCESSORS[choice]()
         return self._pre[choice]
 
-    def control_images(self, choice, images, height, width, control_image=None):
-        """the control image batch of one ControlNet: `control_image` (already processed) or the preprocessor's output for `images`"""
+    def control_images(self, choice, images, height, width, control_image=None, source=None, shared=None):
+        """the control image batch of one ControlNet: `control_image` (already processed), the device preprocessor's output for `source` (on
+        the device already; `shared`: a dict that keeps one result per preprocessor for the ControlNets of one call), or the host
+        preprocessor's output for the PIL `images`"""
+        if control_image is None and self.device_route(choice):
+            if source is None:
+                raise ValueError("ControlNet conditioning needs the image batch on the device (image_type='image' or 'tensors') or control_image=")
+            pre = DEVICE_PREPROCESSORS[choice]
+            cond = shared.get(pre) if shared is not None else None
+            if cond is None:
+                cond = pre(source)
+                if shared is not None:
+                    shared[pre] = cond
+            return cond if tuple(cond.shape[-2:]) == (height, width) else control_tensor(cond, height, width)
         if control_image is None:
             if images is None:
                 raise ValueError("ControlNet conditioning needs the PIL images (image_type='image') or control_image=")
@@ -112,14 +158,18 @@ class ControlNetPipeline:
         return control_tensor(control_image, height, width)
 
     def generate_control_info(self, images, latents, t, prompt_embeds, added_cond_kwargs, control_image=None, shared_ctx=False, split=0,
-                              out=None):
+                              out=None, source=None):
         """-> the residual block (flat fp16, NativeUNet.forward_raw(residuals=...)) of all ControlNets for the UNet inputs `latents`, `t`,
-        `prompt_embeds`, `added_cond_kwargs`.  out: a flat fp16 tensor the (first) model writes straight into."""
+        `prompt_embeds`, `added_cond_kwargs`.  out: a flat fp16 tensor the (first) model writes straight into.
+        images: the PIL images of the host preprocessors; source: the image batch on the device for the device preprocessors (device_canny)."""
         akw = added_cond_kwargs or {}
         B, _, H, W = latents.shape
         block = None
+        shared = {}
         for choice, model in zip(self.choices, self.control):
-            cond = self.control_images(choice, images, H * self.vae_scale_factor, W * self.vae_scale_factor, control_image).to(self.device)
+            cond = self.control_images(choice, images, H * self.vae_scale_factor, W * self.vae_scale_factor, control_image, source, shared)
+            if control_image is not None or not self.device_route(choice):
+                cond = cond.to(self.device)
             if cond.shape[0] == 1 and B > 1:
                 cond = cond.expand(B, -1, -1, -1)
             b = model.forward_raw(latents, t, prompt_embeds, akw.get("text_embeds"), akw.get("time_ids"), cond, shared_ctx=shared_ctx, split=split,

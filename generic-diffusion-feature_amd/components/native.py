@@ -6,6 +6,7 @@ visible, construction raises.  PyTorch is only used for device memory, streams a
 """
 import collections
 import ctypes as C
+import math
 import os
 import time
 import types
@@ -164,6 +165,17 @@ SIGNATURES.update({
                                         C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_int]),
 })
 
+# the kernel-level entries of include/gdf_ops.h that the package itself calls (SIGNATURES stays the model-level headers' table): the device
+# Canny (csrc/canny.hip)
+GDF_CANNY_U8_HWC3, GDF_CANNY_U8_HW, GDF_CANNY_F32_NCHW, GDF_CANNY_F16_NCHW = 0, 1, 2, 3
+GDF_CANNY_DST_U8, GDF_CANNY_DST_F16_NCHW3 = 0, 1
+OP_SIGNATURES = {
+    "gdf_op_canny_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "gdf_op_canny_classify": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "gdf_op_canny_link": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gdf_op_canny": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 # operand-plan levels, the plan chooser and the verify ladder live in components/plan_levels.py (round 6); re-exported here for the callers
@@ -207,7 +219,7 @@ def load_library():
         raise RuntimeError(f"{_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = C.CDLL(_LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(OP_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError => header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -234,6 +246,41 @@ def _create(fn, what):
             torch.cuda.empty_cache()
             rc = fn()
     _check(rc, what)
+
+
+def canny(src, low=100, high=200, out='control'):
+    """cv2.Canny(image, low, high) on the device (gdf_op_canny, csrc/canny.hip), queued on the CURRENT stream; nothing is read back.
+    src: a tensor on a HIP device — uint8 (B, H, W, 3) (np.array of RGB PIL images) or (B, H, W), or fp32 / fp16 (B, 3, H, W) in [-1, 1], which is
+    quantised as the reference's restore_from_tensor_to_image does: preprocess_image's tensor gives the bytes it was made from.
+    out: 'control' -> fp16 (B, 3, H, W) of 0.0 / 1.0, what control_tensor makes of the reference's three-channel edge image and what
+    NativeControlNet.forward_raw(cond=) takes; 'u8' -> uint8 (B, H, W) of 0 / 255, cv2's output.
+    The workspace is an ordinary allocation of the caller's stream pool, freed (stream-ordered) on return.  There is no CPU fallback."""
+    if not (torch.is_tensor(src) and src.is_cuda):
+        raise RuntimeError("canny: the source must be a tensor on a HIP device; there is no CPU fallback")
+    if out not in ('control', 'u8'):
+        raise ValueError("canny: out is 'control' or 'u8'")
+    if src.dtype == torch.uint8 and src.dim() == 4 and src.shape[-1] == 3:
+        kind, (B, H, W) = GDF_CANNY_U8_HWC3, src.shape[:3]
+    elif src.dtype == torch.uint8 and src.dim() == 3:
+        kind, (B, H, W) = GDF_CANNY_U8_HW, src.shape
+    elif src.dtype in (torch.float32, torch.float16) and src.dim() == 4 and src.shape[1] == 3:
+        kind, (B, _, H, W) = (GDF_CANNY_F32_NCHW if src.dtype == torch.float32 else GDF_CANNY_F16_NCHW), src.shape
+    else:
+        raise ValueError(f"canny: uint8 (B, H, W, 3) or (B, H, W), or fp32 / fp16 (B, 3, H, W); got {src.dtype} {tuple(src.shape)}")
+    lib = load_library()
+    src = src.contiguous()
+    dev = src.device
+    with torch.cuda.device(dev):
+        nbytes = lib.gdf_op_canny_workspace_bytes(B, H, W)
+        if nbytes == 0:
+            raise ValueError(f"canny: {B} x {H} x {W} is empty or has 2^31 pixels or more (32-bit component labels)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        dst = (torch.empty((B, 3, H, W), dtype=torch.float16, device=dev) if out == 'control'
+               else torch.empty((B, H, W), dtype=torch.uint8, device=dev))
+        _check(lib.gdf_op_canny(C.c_void_p(src.data_ptr()), kind, B, H, W, math.floor(low), math.floor(high), C.c_void_p(dst.data_ptr()),
+                                GDF_CANNY_DST_F16_NCHW3 if out == 'control' else GDF_CANNY_DST_U8, C.c_void_p(ws.data_ptr()),
+                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "op_canny")
+    return dst
 
 
 # --------------------------------------------------------------------------------------------- #

@@ -345,6 +345,18 @@ hipError_t launch_cond_pack_weights(const void* src, int dtype, half_t* dst, int
 hipError_t launch_cond_pack_image(const void* x, int dtype, int B, int C, int H, int W, half_t* nhwc8, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
+// Canny edge detector, the 'canny' / 'canny-xl' ControlNet preprocessor (csrc/canny.hip)
+// ------------------------------------------------------------------------------------------------
+// src_kind 0 uint8 [B][H][W][3], 1 uint8 [B][H][W], 2 fp32 / 3 fp16 [B][3][H][W] in [-1, 1] (quantised on load); low <= high;
+// cls uint8 [B][H][W]: 2 strong, 0 candidate, 1 neither.  B H W < 2^31; src and cls 4-byte aligned.
+enum { CANNY_LINK_TILE = 32 };
+hipError_t launch_canny_classify(const void* src, int src_kind, int B, int H, int W, int low, int high, uint8_t* cls, hipStream_t s);
+// hysteresis: dst_kind 0 uint8 [B][H][W] 0 / 255, 1 fp16 [B][3][H][W] 0.0 / 1.0; four launches; workspace canny_workspace_bytes(), 16-byte aligned
+hipError_t launch_canny_link(const uint8_t* cls, int B, int H, int W, void* dst, int dst_kind, void* workspace, hipStream_t s);
+size_t canny_workspace_bytes(int B, int H, int W);
+uint8_t* canny_workspace_cls(void* workspace, int B, int H, int W);     // the class map of the fused entry, behind the linking stage's part
+
+// ------------------------------------------------------------------------------------------------
 // weight re-layout (model load time)
 // ------------------------------------------------------------------------------------------------
 // `src_f32` is the source dtype code of gdf_model_set_param: 0 fp16, 1 fp32, 2 bf16

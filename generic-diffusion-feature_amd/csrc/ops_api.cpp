@@ -486,6 +486,45 @@ int gdf_op_cond_pack_image(const void* x_nchw, int src_dtype, int B, int C, int 
   return fin(launch_cond_pack_image(x_nchw, src_dtype, B, C, H, W, (half_t*)nhwc8, (hipStream_t)stream), "cond_pack_image");
 }
 
+// shared argument check of the gdf_op_canny_* entries: sizes, the 32-bit label range, kinds and alignment
+static int canny_check(const char* what, int B, int H, int W, const void* src, int src_kind, const void* cls, const void* dst, int dst_kind,
+                       const void* workspace) {
+  auto bad = [&](const char* msg) { set_error(std::string(what) + ": " + msg); return GDF_ERR_ARG; };
+  if (B < 1 || H < 1 || W < 1) return bad("B, H, W >= 1");
+  if ((size_t)B * H * W >= (1ull << 31)) {
+    set_error(std::string(what) + ": B * H * W >= 2^31 pixels (32-bit component labels); split the batch");
+    return GDF_ERR_UNSUPPORTED;
+  }
+  if (src_kind < GDF_CANNY_U8_HWC3 || src_kind > GDF_CANNY_F16_NCHW) return bad("src_kind is GDF_CANNY_U8_HWC3, _U8_HW, _F32_NCHW or _F16_NCHW");
+  if (dst_kind != GDF_CANNY_DST_U8 && dst_kind != GDF_CANNY_DST_F16_NCHW3) return bad("dst_kind is GDF_CANNY_DST_U8 or GDF_CANNY_DST_F16_NCHW3");
+  if (!src || !cls || !dst || !workspace) return bad("null pointer");
+  if ((uintptr_t)src & 3) return bad("src must be 4-byte aligned");
+  if (((uintptr_t)cls | (uintptr_t)dst | (uintptr_t)workspace) & 15) return bad("cls, dst and workspace must be 16-byte aligned");
+  return GDF_OK;
+}
+static const char canny_ok_ptr[16] __attribute__((aligned(16))) = {0};   // stands in for the pointers an entry does not take
+
+size_t gdf_op_canny_workspace_bytes(int B, int H, int W) {
+  if (B < 1 || H < 1 || W < 1 || (size_t)B * H * W >= (1ull << 31)) return 0;
+  return canny_workspace_bytes(B, H, W);
+}
+int gdf_op_canny_classify(const void* src, int src_kind, int B, int H, int W, int low, int high, void* cls, void* stream) {
+  if (int rc = canny_check("gdf_op_canny_classify", B, H, W, src, src_kind, cls, canny_ok_ptr, GDF_CANNY_DST_U8, canny_ok_ptr)) return rc;
+  if (low > high) std::swap(low, high);
+  return fin(launch_canny_classify(src, src_kind, B, H, W, low, high, (uint8_t*)cls, (hipStream_t)stream), "canny_classify");
+}
+int gdf_op_canny_link(const void* cls, int B, int H, int W, void* dst, int dst_kind, void* workspace, void* stream) {
+  if (int rc = canny_check("gdf_op_canny_link", B, H, W, canny_ok_ptr, GDF_CANNY_U8_HW, cls, dst, dst_kind, workspace)) return rc;
+  return fin(launch_canny_link((const uint8_t*)cls, B, H, W, dst, dst_kind, workspace, (hipStream_t)stream), "canny_link");
+}
+int gdf_op_canny(const void* src, int src_kind, int B, int H, int W, int low, int high, void* dst, int dst_kind, void* workspace, void* stream) {
+  if (int rc = canny_check("gdf_op_canny", B, H, W, src, src_kind, canny_ok_ptr, dst, dst_kind, workspace)) return rc;
+  if (low > high) std::swap(low, high);
+  uint8_t* cls = canny_workspace_cls(workspace, B, H, W);
+  if (int rc = fin(launch_canny_classify(src, src_kind, B, H, W, low, high, cls, (hipStream_t)stream), "canny_classify")) return rc;
+  return fin(launch_canny_link(cls, B, H, W, dst, dst_kind, workspace, (hipStream_t)stream), "canny_link");
+}
+
 // element type of the 16-bit operands of the MMDiT entry points below, per calling thread (GDF_F16 default)
 static thread_local int g_e16_bf = 0;
 int gdf_op_set_e16(int dtype) {

@@ -10,7 +10,8 @@ In scope are the single-timestep path and, for the UNet versions, `use_ddim_inve
 trajectory, NativeUNet.trajectory) and `generate`: a classifier-free-guided text-to-image run with background extraction — the hooked
 layers keep the features of the UNet calls named by `set_background_extraction` (reference generate_with_extraction.py) — as one
 device-resident run (NativeUNet.sample), and `control=` / `use_control`: ControlNet conditioning of the extraction forward with the
-ControlNet itself a native model (components/control.py, NativeControlNet).  `denoising_from` is not.
+ControlNet itself a native model (components/control.py, NativeControlNet) and the Canny preprocessor in front of it a device kernel
+(csrc/canny.hip).  `denoising_from` is not.
 """
 import copy
 import os
@@ -151,6 +152,13 @@ class FeatureExtractor(nn.Module):
             return self.pipe.image_processor.preprocess(self._preprocess_basic(x))
         return self.pipe.image_processor.preprocess([x[i] for i in range(x.shape[0])])
 
+    def restore_from_tensor_to_image(self, x):
+        """(B, 3, h, w) in [-1, 1] -> list of RGB PIL images (reference :143-144, VaeImageProcessor.postprocess with do_denormalize): to fp32,
+        (x / 2 + 0.5).clamp(0, 1) * 255 rounded half to even — the quantisation the device Canny applies when it reads such a tensor itself"""
+        from PIL import Image
+        u = ((x.detach().float().cpu() / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous().numpy()
+        return [Image.fromarray(a) for a in u]
+
     def encode_prompt(self, prompt_str=None, prompt_file=None):
         assert prompt_str != None and prompt_file == None or prompt_str == None and prompt_file != None
         if prompt_file:
@@ -193,13 +201,17 @@ class FeatureExtractor(nn.Module):
         (reference :381-386), see _ddim_inverted_latents.
         use_control (UNet versions, an extractor built with control=[...]): the ControlNets see exactly the UNet's inputs and their residuals
         enter the extraction forward (reference :408-465); the inversion forwards of use_ddim_inversion run without them, as in the reference.
+        The control images come from `image`, PIL or tensors (reference :259-263): on a HIP device the 'canny' choices read the (B, 3, S, S)
+        batch this call makes for the VAE encoder anyway (components/control.py device_canny); the host preprocessors ('depth') get the PIL
+        images, restored from a tensor as the reference restores them.
         control_image — native extension — hands over already-processed control images ((B, 3, h, w) in [0, 1] or PIL) instead of running
-        the preprocessor (cv2 / controlnet_aux) on `image`."""
+        any preprocessor."""
         control_pipe = getattr(self, "control_pipe", None) if use_control else None
         if use_control and control_pipe is None:
             raise NotImplementedError("use_control: this extractor was built without control=[...], it has no ControlNet to run")
-        if use_control and control_image is None and image_type != 'image':
-            raise ValueError("use_control derives the control images from the PIL images (image_type='image'); with tensors or latents pass "
+        if use_control and control_image is None and (image_type == 'latents' or (image_type != 'image' and not hasattr(control_pipe, 'needs_source'))):
+            # (latents carry no image; and a control pipeline that is not components/control.py's cannot say which form of the images it wants)
+            raise ValueError("use_control derives the control images from the images (image_type='image' or 'tensors'); with latents pass "
                              "control_image=")
         if denoising_from:
             raise NotImplementedError("denoising_from is deprecated upstream and runs there only together with ControlNet (its denoising call "
@@ -210,7 +222,12 @@ class FeatureExtractor(nn.Module):
                                           "inversion loop calls pipe.unet (components/ddim_inversion.py:31)")
             if image_type == 'latents':
                 raise ValueError("use_ddim_inversion inverts an image: image_type must be 'image' or 'tensors'")
-        raw_image = list(image) if (control_pipe is not None and control_image is None) else None      # the preprocessors' input (reference :433)
+        # the preprocessors' input (reference :259-263, :433): the PIL images for the host ones, restored from a tensor where tensors came in; the
+        # device ones read `control_source`, set below once the batch for the VAE exists
+        derive = control_pipe is not None and control_image is None
+        raw_image, control_source = None, None
+        if derive and control_pipe.needs_pil():
+            raw_image = list(image) if image_type == 'image' else self.restore_from_tensor_to_image(image)
         self.feature_store.reset()
         device = self.device
         if self.version == 'flux':                                                       # reference :246-254
@@ -277,9 +294,19 @@ class FeatureExtractor(nn.Module):
             if image_type == 'image':                                                    # :358-364
                 image = torch.concat(_map_threads(self.preprocess_image, list(image)), dim=0)
             elif tuple(image.shape[-2:]) != (self.img_size, self.img_size):
+                if derive and control_pipe.needs_source():
+                    # the reference, literally (:259-263, :433): restore to PIL, _preprocess_basic (PIL's resize, not the bilinear one below), and
+                    # those bytes go to the device
+                    import numpy as np
+                    basic = [self._preprocess_basic(r) for r in (raw_image if raw_image is not None else self.restore_from_tensor_to_image(image))]
+                    control_source = torch.from_numpy(np.stack([np.array(b) for b in basic])).to(device)
                 # (bilinear resampling at scale 1 samples exactly the pixel centres: the identity, so tensors that already have the target
                 #  size — e.g. the CLI's loader threads, which ran preprocess_image themselves — skip the launch)
                 image = F.interpolate(image, (self.img_size, self.img_size), mode='bilinear')
+            if derive and control_source is None and control_pipe.needs_source():
+                # the batch the VAE encoder reads, moved to the device once and shared: preprocess_image's 2 (u / 255) - 1 quantises back to the
+                # bytes u of _preprocess_basic(image), so the PIL images are not resized a second time for Canny
+                image = control_source = image.to(device, non_blocking=True)
             if use_ddim_inversion:                                                       # :381-386 (the feature store has nothing to pause:
                 latents = self._ddim_inverted_latents(image, prompts, prompt_embeds, added_cond_kwargs, t)    # the trajectory's plan has no hooks)
             else:
@@ -319,7 +346,7 @@ class FeatureExtractor(nn.Module):
             self.pipe.unet.shared_ctx = prompts[0].shape[0] == 1
         if control_pipe is not None:                                                     # reference :408-439 (no classifier-free guidance here)
             noise_pred = self._controlled_forward(control_pipe, raw_image, control_image, latent_model_input, t, prompt_embeds.to(device),
-                                                  added_cond_kwargs)
+                                                  added_cond_kwargs, control_source)
         else:
             noise_pred = self.pipe.unet(latent_model_input, timestep=t, encoder_hidden_states=prompt_embeds.to(device),
                                         added_cond_kwargs=added_cond_kwargs, down_block_additional_residuals=None,
@@ -336,10 +363,11 @@ class FeatureExtractor(nn.Module):
             self.pipe.unet.last_extra = {}
         return self.feature_store.stored_feats                                           # :517
 
-    def _controlled_forward(self, control_pipe, raw_image, control_image, latent_model_input, t, prompt_embeds, added_cond_kwargs):
+    def _controlled_forward(self, control_pipe, raw_image, control_image, latent_model_input, t, prompt_embeds, added_cond_kwargs, source=None):
         """The extraction forward with ControlNet residuals: the ControlNets run on the UNet's own inputs with the UNet plan's shared-ctx
         promise and operand split, write their block straight into that plan's staged residual buffer (no staging copy), and the UNet runs
-        with it; hooks reach the feature store as in NativeUNet.__call__."""
+        with it; hooks reach the feature store as in NativeUNet.__call__.
+        raw_image: the PIL images of the host preprocessors (None when no choice has one); source: the device preprocessors' image batch."""
         unet = self.pipe.unet
         ids = unet.requested_ids()
         have = set(ids)
@@ -349,7 +377,7 @@ class FeatureExtractor(nn.Module):
         basic = [self._preprocess_basic(r) for r in raw_image] if raw_image is not None else None
         out = unet.residual_buffer(B, H, W, prompt_embeds.shape[1], ids, unet.shared_ctx)
         block = control_pipe.generate_control_info(basic, latent_model_input, t, prompt_embeds, added_cond_kwargs, control_image=control_image,
-                                                   shared_ctx=unet.shared_ctx, split=split, out=out)
+                                                   shared_ctx=unet.shared_ctx, split=split, out=out, source=source)
         noise, hooks = unet.forward_raw(latent_model_input, t, prompt_embeds, added_cond_kwargs.get("text_embeds"),
                                         added_cond_kwargs.get("time_ids"), hook_ids=ids, shared_ctx=unet.shared_ctx, residuals=block)
         unet.last_extra = {k: v for k, v in hooks.items() if k in set(unet.extra_hook_ids)}

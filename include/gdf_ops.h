@@ -335,6 +335,26 @@ int gdf_op_cond_pack_weights(const void* w_oihw, int src_dtype, void* dst, int C
 /* control image NCHW (B, C <= 8, H, W), fp16 (GDF_F16) or fp32 (GDF_F32) -> NHWC pixels of 8 fp16 channels, channels from C up zero. */
 int gdf_op_cond_pack_image(const void* x_nchw, int src_dtype, int B, int C, int H, int W, void* nhwc8, void* stream);
 
+/* ---- Canny edge detector on the device (csrc/canny.hip): the preprocessor of the 'canny' / 'canny-xl' ControlNets, OpenCV 4.x
+ * cv::Canny(src8u, low, high, apertureSize = 3, L2gradient = false) restated in integer arithmetic.  Stream-ordered, caller-owned
+ * buffers, no device -> host read; the number of launches depends on nothing but the entry called.
+ *   src_kind  GDF_CANNY_U8_HWC3  uint8 [B][H][W][3] (np.array of an RGB PIL image)      GDF_CANNY_U8_HW  uint8 [B][H][W]
+ *             GDF_CANNY_F32_NCHW / GDF_CANNY_F16_NCHW  [B][3][H][W] in [-1, 1], quantised on load as the reference's restore_from_tensor_to_image
+ *             does: to fp32, rint(clamp(x / 2 + 0.5, 0, 1) * 255), half to even
+ *   low, high the thresholds (swapped when low > high); a pixel is examined when its magnitude > low, strong when > high
+ *   cls       uint8 [B][H][W], OpenCV's map values: 2 strong, 0 candidate (kept by the non-maximum suppression, not strong), 1 neither
+ *   dst_kind  GDF_CANNY_DST_U8  uint8 [B][H][W] 0 / 255 (cv2's output)      GDF_CANNY_DST_F16_NCHW3  fp16 [B][3][H][W] 0.0 / 1.0: the control tensor of
+ *             the three-channel edge image
+ *   workspace gdf_op_canny_workspace_bytes(B, H, W) bytes, the caller's; nothing is kept in it between calls
+ * H, W >= 1 (1 x 1 is legal); B H W < 2^31 (32-bit labels), anything larger is GDF_ERR_UNSUPPORTED; src 4-byte, cls / dst / workspace 16-byte aligned.
+ * gdf_op_canny_link takes any class map (values 0 / 1 / 2), also ones no image produces; gdf_op_canny = classify into the workspace, then link. */
+enum { GDF_CANNY_U8_HWC3 = 0, GDF_CANNY_U8_HW = 1, GDF_CANNY_F32_NCHW = 2, GDF_CANNY_F16_NCHW = 3 };
+enum { GDF_CANNY_DST_U8 = 0, GDF_CANNY_DST_F16_NCHW3 = 1 };
+size_t gdf_op_canny_workspace_bytes(int B, int H, int W);
+int gdf_op_canny_classify(const void* src, int src_kind, int B, int H, int W, int low, int high, void* cls, void* stream);
+int gdf_op_canny_link(const void* cls, int B, int H, int W, void* dst, int dst_kind, void* workspace, void* stream);
+int gdf_op_canny(const void* src, int src_kind, int B, int H, int W, int low, int high, void* dst, int dst_kind, void* workspace, void* stream);
+
 /* ---- MMDiT (Flux) kernels (reference files cited in csrc/dit.hip, gdf_flux.h) ---- */
 
 /* Element type of the 16-bit operands ("e16": A, W, out16, q/k/v/o, y) of the MMDiT entry points below, per calling thread:
