@@ -6,6 +6,7 @@ extract_feature.py (/root/reference/extract_feature.py:18-43 flags, :113-148 out
   --sample_name_first <output_dir>/<name>/<layer_id>.npy
   --aggregate_output  <output_dir>/<name>.npy                       all layers nearest-resized to the largest H,W and
                                                                     concatenated over channels
+  --t T1 T2 ...       <output_dir>/t<T>/<one of the layouts above>  one tree per timestep (a single --t T: no t<T>/ level)
   <name> = original file stem (--use_original_filename; parent-dir/stem with --nested_input_dir) or <split><index>.
 
 The reference's own script also runs unchanged against this package (it only needs `import diffusion_feature`);
@@ -47,7 +48,9 @@ def parse_args(argv=None):
     p.add_argument('--img_size', type=int, default=1024)
     # extraction settings
     p.add_argument('--batch_size', '-b', type=int, default=2)
-    p.add_argument('--t', type=int, help='timestep at which features are extracted')
+    p.add_argument('--t', type=int, nargs='+',
+                   help='timestep at which features are extracted.  Several values (native extension, UNet versions, at most 8): every batch is '
+                        'VAE-encoded once and extracted at all of them in one call; the tree of timestep T is written under <output_dir>/tT/')
     p.add_argument('--denoising_from', type=int, default=None)
     p.add_argument('--use_ddim_inversion', action='store_true')
     # io settings
@@ -78,7 +81,13 @@ def parse_args(argv=None):
     p.add_argument('--gpus', type=int, default=1,
                    help='native extension (not in the reference CLI): data-parallel over N GPUs of this node.  Started as a plain process '
                         '(`python3 extract_feature.py --gpus 8 ...`) the script starts its N ranks itself; under torchrun it must equal WORLD_SIZE')
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.t is not None:
+        if len(args.t) == 1:
+            args.t = args.t[0]                      # one value: an int, the single-timestep path and the output tree without t<T>/ directories
+        elif len(set(args.t)) != len(args.t):
+            p.error(f"--t {' '.join(map(str, args.t))}: repeated timesteps would write to the same t<T>/ directory")
+    return args
 
 
 def sample_name(path, nested):
@@ -122,7 +131,8 @@ class HostWriter:
             e, self.err = self.err, None
             raise e
 
-    def submit(self, feats, names):
+    def submit(self, feats, names, subdir=None):
+        """subdir: write this batch's tree under <output_dir>/<subdir>/ (the per-timestep trees of --t T1 T2 ...)"""
         self._check()
         host = {}
         if self.stream is not None:
@@ -155,7 +165,7 @@ class HostWriter:
                 rest = [v for v in seen if v.is_cuda]
             for v in rest:
                 v.record_stream(self.stream)
-        self.q.put((host, names, ev))                            # blocks while `depth` batches are still being written
+        self.q.put((host, names, ev, subdir))                    # blocks while `depth` batches are still being written
 
     def flush(self):
         self.q.join()
@@ -167,19 +177,20 @@ class HostWriter:
         self.thread.join()
         self._check()
 
-    def _write(self, host, names, ev):
+    def _write(self, host, names, ev, subdir=None):
         if ev is not None:
             ev.synchronize()
         a = self.args
+        root = os.path.join(a.output_dir, subdir) if subdir else a.output_dir
         jobs = []
         for j, name in enumerate(names):
             for k, v in host.items():
                 if k is None:                                       # aggregated: <output_dir>/<name>.npy
-                    path = os.path.join(a.output_dir, name)
+                    path = os.path.join(root, name)
                 elif a.sample_name_first:
-                    path = os.path.join(a.output_dir, name, k)
+                    path = os.path.join(root, name, k)
                 else:
-                    path = os.path.join(a.output_dir, k, name)
+                    path = os.path.join(root, k, name)
                 os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
                 jobs.append((path, v[j].numpy()))
         # np.save of a C-contiguous array is one header + one write(): it releases the GIL, a few writers in parallel keep up with
@@ -379,7 +390,11 @@ def main(argv=None):
                     return
                 names = [sample_name(p, args.nested_input_dir) if args.use_original_filename else f'{args.split}{i + j}'
                          for j, p in enumerate(chunk)]
-                writer.submit(feats, names)
+                if isinstance(args.t, list):                           # (K*B, ...) timestep-major -> one tree per timestep, views only
+                    for tk, sub in zip(args.t, diffusion_feature.split_timesteps(feats, len(args.t))):
+                        writer.submit(sub, names, subdir=f't{tk}')
+                else:
+                    writer.submit(feats, names)
                 if rank == 0:
                     print(f'{min(i + len(chunk), hi) - lo}/{hi - lo}', end='\r')
         ok = True

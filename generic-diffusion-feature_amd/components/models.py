@@ -320,6 +320,31 @@ def native_prepare_latents(pipe, image, timestep, batch_size, num_images_per_pro
     return lat.to(dtype)
 
 
+def native_prepare_latents_multi(pipe, image, timesteps, batch_size, dtype, device, generator=None, schedulers=None):
+    """`native_prepare_latents` for K timesteps of the same B images from ONE VAE encode (NativeVAEEncoder.encode_multi): returns
+    (K*B, L, h, w) TIMESTEP-MAJOR — rows k*B:(k+1)*B are the B images noised for timesteps[k] (each entry what the single call takes: a
+    one-element or (B,) tensor).
+    The random draws are DEFINED as those of native_prepare_latents at batch K*B: eps = randn((K*B, L, h, w)), then noise = randn(...), both
+    fp32 on the device, so every (image, timestep) row has its own posterior sample and its own noise, and the single call on the images
+    tiled K times draws the same numbers.  (a, b) per timestep come from scheduler_noise_scalars: PNDM, Euler and DPM-Solver alike.
+    schedulers: the scheduler object that PICKED timesteps[k], one per timestep (None: pipe.scheduler for all).  It matters: diffusers'
+    img2img `get_timesteps` leaves `begin_index` on the scheduler it ran on, and Euler / DPM-Solver `add_noise` then reads the sigma AT
+    that index whatever timestep it is given — asking one scheduler for all K timesteps would noise every row for the last one picked."""
+    enc = pipe.native_vae
+    f = 1 << (len(enc.cfg["block_out_channels"]) - 1)
+    B, _, H, W = image.shape
+    K = len(timesteps)
+    shape = (K * B, enc.cfg["latent_channels"], H // f, W // f)
+    eps = torch.randn(shape, generator=generator, device=device, dtype=torch.float32)
+    noise = torch.randn(shape, generator=generator, device=device, dtype=torch.float32)
+    if schedulers is not None and len(schedulers) != K:
+        raise ValueError("schedulers must hold one scheduler per timestep")
+    ab = [scheduler_noise_scalars(schedulers[k] if schedulers is not None else pipe.scheduler, t) for k, t in enumerate(timesteps)]
+    lat = enc.encode_multi(image, eps=eps, noise=noise, scaling_factor=float(pipe.vae.config.scaling_factor),
+                           noise_a=[a for a, _ in ab], noise_b=[b for _, b in ab], input_scale=[1.0] * K)
+    return lat.to(dtype)
+
+
 class SyntheticPipe:
     """Offline stand-in for the diffusers img2img pipeline object (`pipe`) used by FeatureExtractor."""
     synthetic_weights = True                      # seeded N(0, 1/fan_in) weights: the statistics the operand-plan table was made on
@@ -382,6 +407,11 @@ class SyntheticPipe:
         """prepare_latents of the img2img pipelines on the native VAE encoder (random-weight AutoencoderKL offline)."""
         g = generator or torch.Generator(device=device).manual_seed(1234)
         return native_prepare_latents(self, image.to(device), timestep, batch_size, num_images_per_prompt, dtype, device, g)
+
+    def prepare_latents_multi(self, image, timesteps, batch_size, dtype, device, generator=None, schedulers=None):
+        """prepare_latents for several timesteps of the same images (native_prepare_latents_multi); the same default generator."""
+        g = generator or torch.Generator(device=device).manual_seed(1234)
+        return native_prepare_latents_multi(self, image.to(device), timesteps, batch_size, dtype, device, g, schedulers)
 
 
 class SyntheticPixartPipe(SyntheticPipe):
@@ -556,7 +586,8 @@ def _img2img_get_timesteps(self, num_inference_steps, strength, device, denoisin
 
 
 def _native_vae_from_diffusers(pipe, device):
-    """pipe.native_vae = the AutoencoderKL encoder half in libgdf.so with pipe.vae's weights; pipe.prepare_latents = native_prepare_latents"""
+    """pipe.native_vae = the AutoencoderKL encoder half in libgdf.so with pipe.vae's weights; pipe.prepare_latents = native_prepare_latents,
+    pipe.prepare_latents_multi = native_prepare_latents_multi"""
     vc = pipe.vae.config
     enc = NativeVAEEncoder(dict(in_channels=vc.in_channels, latent_channels=vc.latent_channels,
                                 block_out_channels=tuple(vc.block_out_channels), layers_per_block=vc.layers_per_block,
@@ -567,6 +598,7 @@ def _native_vae_from_diffusers(pipe, device):
     #  cyclic collector at an arbitrary later allocation — in whatever thread that happens to run — together with its multi-GB device arenas)
     import weakref
     pipe.prepare_latents = types.MethodType(native_prepare_latents, weakref.proxy(pipe))
+    pipe.prepare_latents_multi = types.MethodType(native_prepare_latents_multi, weakref.proxy(pipe))
     return pipe
 
 

@@ -114,6 +114,9 @@ class FluxDesc(C.Structure):
                 ("mlp_ratio", C.c_int), ("compute_dtype", C.c_int)]
 
 
+MAX_TIMESTEPS = 8                    # GDF_MAX_TIMESTEPS (include/gdf.h; tests/test_multi_t_cpu.py holds the two together)
+
+
 class VaeDesc(C.Structure):
     _fields_ = [("in_channels", C.c_int), ("latent_channels", C.c_int), ("n_levels", C.c_int),
                 ("block_out_channels", C.c_int * MAX_LEVELS), ("layers_per_block", C.c_int), ("use_quant_conv", C.c_int)]
@@ -125,6 +128,8 @@ SIGNATURES.update({
     "gdf_vae_plan_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "gdf_vae_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdf_vae_encode_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.POINTER(C.c_float),
+                                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
     "gdf_vae_plan_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_char_p),
                                        C.POINTER(C.c_double), C.c_int]),
@@ -495,6 +500,8 @@ class _Plan:
         self.staged = {}
         self.sets = []
         self.inflight = []
+        self.out_capacity = 0            # elements every set's output region holds at least (a plan whose calls differ in output size sets it ONCE,
+                                         # before its first run: NativeVAEEncoder._plan)
 
     def __del__(self):
         # The plan's buffers (workspace, staging, hook sets) are ordinary allocations of the CALLER's stream pool that only this plan's stream
@@ -583,7 +590,7 @@ class _Plan:
             hs = next((h for h in self.sets if h.free()), None)
             pooled = True
             if hs is None:
-                hs = _HookSet(self, n_out, dev)
+                hs = _HookSet(self, max(n_out, self.out_capacity), dev)
                 pooled = len(self.sets) < self.MAX_SETS        # more live result sets than that: one-off buffers, run eagerly
                 if pooled:
                     self.sets.append(hs)
@@ -1610,6 +1617,10 @@ class NativeVAEEncoder(_NativeModel):
             ph = C.c_void_p()
             _check(self.lib.gdf_vae_plan_create(self.handle, batch, h, w, C.byref(ph)), "vae_plan_create")
             p = _Plan(self.lib, ph)
+            # encode writes B latents, encode_multi up to MAX_TIMESTEPS * B: every output region of the plan holds the largest (16 MB for
+            # 16 images at 1024^2), so both calls share the plan's buffer sets and the graphs recorded on them
+            f = 1 << (len(self.cfg["block_out_channels"]) - 1)
+            p.out_capacity = MAX_TIMESTEPS * batch * self.cfg["latent_channels"] * (h // f) * (w // f)
             if len(self._plans) >= 4:
                 self._plans.pop(next(iter(self._plans)))
             self._plans[key] = p
@@ -1646,6 +1657,40 @@ class NativeVAEEncoder(_NativeModel):
         out, _, prof = plan.run(dev, [("image", image, f16), ("eps", eps, f16), ("noise", noise, f16)], (B, L, H // f, W // f), call,
                                 profile=profile)
         return (out, prof) if profile else out
+
+
+    def encode_multi(self, image, eps=None, noise=None, scaling_factor=0.18215, noise_a=(1.0,), noise_b=(0.0,), input_scale=(1.0,)):
+        """The same B images at K = len(noise_a) timesteps from ONE encoder pass (gdf_vae_encode_multi, on the plan and workspace encode uses).
+        image (B,3,H,W); eps / noise (K*B,L,H/f,W/f) or None, TIMESTEP-MAJOR: row k*B + b is image b at timestep k.  noise_a, noise_b,
+        input_scale: sequences of K floats.  Returns (K*B,L,H/f,W/f) fp16 whose rows k*B:(k+1)*B have the bits of
+        encode(image, eps[k*B:(k+1)*B], noise[k*B:(k+1)*B], scaling_factor, noise_a[k], noise_b[k], input_scale[k])."""
+        dev = self.device
+        B, _, H, W = image.shape
+        f = 1 << (len(self.cfg["block_out_channels"]) - 1)
+        L = self.cfg["latent_channels"]
+        K = len(noise_a)
+        if not 1 <= K <= MAX_TIMESTEPS:
+            raise ValueError(f"encode_multi takes 1..{MAX_TIMESTEPS} timesteps, got {K}")
+        if len(noise_b) != K or len(input_scale) != K:
+            raise ValueError("noise_a, noise_b and input_scale must have the same length")
+        out_shape = (K * B, L, H // f, W // f)
+        for t in (eps, noise):
+            if t is not None and tuple(t.shape) != out_shape:
+                raise ValueError("eps / noise must have the shape (K*B, L, H/f, W/f)")
+        plan = self._plan(B, H, W)
+        lib = self.lib
+        arr = lambda v: (C.c_float * K)(*[float(x) for x in v])
+        na, nb, sc = arr(noise_a), arr(noise_b), arr(input_scale)
+
+        def call(staged, hook_ptrs, out_ptr, ws_ptr, stream_ptr):
+            vp = lambda a: C.c_void_p(a.data_ptr() if a is not None else 0)
+            _check(lib.gdf_vae_encode_multi(plan.handle, vp(staged[0]), vp(staged[1]), vp(staged[2]), float(scaling_factor), K, na, nb, sc,
+                                            out_ptr, ws_ptr, stream_ptr), "vae_encode_multi")
+
+        f16 = torch.float16
+        # (staging buffers of their own names: eps / noise of encode have B rows, these K * B, and a plan serves both calls in turn)
+        out, _, _ = plan.run(dev, [("image", image, f16), ("eps_multi", eps, f16), ("noise_multi", noise, f16)], out_shape, call)
+        return out
 
 
 def _vae_desc(cfg):

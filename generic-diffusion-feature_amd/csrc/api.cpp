@@ -154,6 +154,13 @@ int gdf_vae_encode(gdf_plan* p, const void* image, const void* eps, const void* 
   return vae_encode(p->p, *p->p.model, image, eps, noise, scaling_factor, noise_a, noise_b, input_scale, latents_out, workspace,
                     (hipStream_t)stream, nullptr, nullptr, nullptr, 0);
 }
+int gdf_vae_encode_multi(gdf_plan* p, const void* image, const void* eps, const void* noise, float scaling_factor, int n_t,
+                         const float* noise_a, const float* noise_b, const float* input_scale, void* latents_out, void* workspace,
+                         void* stream) {
+  if (!p) { set_error("null plan"); return GDF_ERR_ARG; }
+  return vae_encode_multi(p->p, *p->p.model, image, eps, noise, scaling_factor, n_t, noise_a, noise_b, input_scale, latents_out, workspace,
+                          (hipStream_t)stream);
+}
 int gdf_vae_plan_profile(gdf_plan* p, const void* image, const void* eps, const void* noise, float scaling_factor, float noise_a,
                          float noise_b, float input_scale, void* latents_out, void* workspace, void* stream, float* ms,
                          const char** names, double* flops, int cap) {

@@ -345,15 +345,10 @@ hipError_t launch_softmax_rows(half_t* x, int ld, int R, int n, float scale, hip
   return hipGetLastError();
 }
 
-__global__ void vae_finish_kernel(const float* h, int HW, int L, const half_t* wq, const float* bq, const half_t* eps,
-                                  const half_t* noise, float scaling, float na, float nb, float in_scale, half_t* out, long total) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;      // (b, pixel)
-  if (i >= total) return;
-  const long b = i / HW;
-  const int pix = (int)(i - b * HW);
-  float m[16], hv[16];
-  const int L2 = 2 * L;
-  for (int c = 0; c < L2; ++c) hv[c] = h[(size_t)i * L2 + c];
+// quant_conv of one pixel's 2L moments (1x1: wq fp16 [2L][2L], bq fp32 or NULL = 0; wq == NULL: identity): m[0..L) = mean, m[L..2L) = logvar
+__device__ __forceinline__ void vae_moments(const float* h, size_t pixel, int L2, const half_t* wq, const float* bq, float* m) {
+  float hv[16];
+  for (int c = 0; c < L2; ++c) hv[c] = h[pixel * L2 + c];
   for (int o = 0; o < L2; ++o) {
     if (wq) {
       float a = bq ? bq[o] : 0.f;
@@ -363,13 +358,30 @@ __global__ void vae_finish_kernel(const float* h, int HW, int L, const half_t* w
       m[o] = hv[o];
     }
   }
+}
+
+// One latent element of the VAE tail — the ONE place its arithmetic is written: vae_finish_kernel and vae_finish_multi_kernel both call it, so
+// the same operands give the same bits in either (tests/test_gpu_vae_multi.py compares them bit for bit)
+__device__ __forceinline__ _Float16 vae_finish_value(float mean, float logvar, const half_t* eps, const half_t* noise, size_t oi,
+                                                      float scaling, float na, float nb, float in_scale) {
+  float z = mean;
+  if (eps) z += expf(0.5f * fminf(fmaxf(logvar, -30.0f), 20.0f)) * (float)eps[oi];
+  float lat = scaling * z;
+  if (noise) lat = na * lat + nb * (float)noise[oi];
+  return (_Float16)(in_scale * lat);
+}
+
+__global__ void vae_finish_kernel(const float* h, int HW, int L, const half_t* wq, const float* bq, const half_t* eps,
+                                  const half_t* noise, float scaling, float na, float nb, float in_scale, half_t* out, long total) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;      // (b, pixel)
+  if (i >= total) return;
+  const long b = i / HW;
+  const int pix = (int)(i - b * HW);
+  float m[16];
+  vae_moments(h, (size_t)i, 2 * L, wq, bq, m);
   for (int c = 0; c < L; ++c) {
     const size_t oi = ((size_t)b * L + c) * HW + pix;
-    float z = m[c];
-    if (eps) z += expf(0.5f * fminf(fmaxf(m[L + c], -30.0f), 20.0f)) * (float)eps[oi];
-    float lat = scaling * z;
-    if (noise) lat = na * lat + nb * (float)noise[oi];
-    out[oi] = (_Float16)(in_scale * lat);
+    out[oi] = vae_finish_value(m[c], m[L + c], eps, noise, oi, scaling, na, nb, in_scale);
   }
 }
 
@@ -381,6 +393,42 @@ hipError_t launch_vae_finish(const float* h, int B, int HW, int L, const half_t*
   if (total <= 0) return hipSuccess;
   hipLaunchKernelGGL(vae_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, h, HW, L, wq, bq, eps, noise,
                      scaling, noise_a, noise_b, in_scale, out, total);
+  return hipGetLastError();
+}
+
+// The tail for K timesteps of the same B images: the moments are read and quant_conv applied ONCE per (image, pixel); row r = k * B + b of
+// eps / noise / out (timestep-major) gets timestep k's scalars.  The K triples are kernel ARGUMENTS (uniform loads from the kernarg segment
+// indexed by k): no device table, so no host -> device copy in front of the launch.  t_stride = elements between two timesteps' row blocks.
+static_assert(GDF_MAX_TIMESTEPS == 8, "VaeTimesteps holds 8 triples");
+__global__ void vae_finish_multi_kernel(const float* h, int HW, int L, const half_t* wq, const float* bq, const half_t* eps,
+                                        const half_t* noise, float scaling, int K, VaeTimesteps ts, half_t* out, long total,
+                                        long t_stride) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;      // (b, pixel): consecutive lanes = consecutive pixels
+  if (i >= total) return;
+  const long b = i / HW;
+  const int pix = (int)(i - b * HW);
+  float m[16];
+  vae_moments(h, (size_t)i, 2 * L, wq, bq, m);
+  for (int k = 0; k < K; ++k) {
+    const float na = ts.noise_a[k], nb = ts.noise_b[k], is = ts.in_scale[k];
+    for (int c = 0; c < L; ++c) {
+      const size_t oi = (size_t)k * (size_t)t_stride + ((size_t)b * L + c) * HW + pix;
+      out[oi] = vae_finish_value(m[c], m[L + c], eps, noise, oi, scaling, na, nb, is);
+    }
+  }
+}
+
+hipError_t launch_vae_finish_multi(const float* h, int B, int HW, int L, const half_t* wq, const float* bq, const half_t* eps,
+                                   const half_t* noise, float scaling, int K, const float* noise_a, const float* noise_b,
+                                   const float* in_scale, half_t* out, long t_stride, hipStream_t s) {
+  if (L < 1 || L > 8 || K < 1 || K > GDF_MAX_TIMESTEPS || !noise_a || !noise_b || !in_scale) return hipErrorInvalidValue;
+  const long total = (long)B * HW;
+  if (total <= 0) return hipSuccess;
+  if (t_stride < total * L) return hipErrorInvalidValue;           // the K row blocks must not overlap
+  VaeTimesteps ts{};
+  for (int k = 0; k < K; ++k) { ts.noise_a[k] = noise_a[k]; ts.noise_b[k] = noise_b[k]; ts.in_scale[k] = in_scale[k]; }
+  hipLaunchKernelGGL(vae_finish_multi_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, h, HW, L, wq, bq, eps, noise,
+                     scaling, K, ts, out, total, t_stride);
   return hipGetLastError();
 }
 

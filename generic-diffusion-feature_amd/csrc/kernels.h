@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include "../../include/gdf.h"    // GDF_MAX_TIMESTEPS
 #include "launch.h"
 
 typedef _Float16 half_t;
@@ -262,6 +263,15 @@ hipError_t launch_softmax_rows(half_t* x, int ld, int R, int n, float scale, hip
 hipError_t launch_vae_finish(const float* h, int B, int HW, int L, const half_t* wq, const float* bq, const half_t* eps,
                              const half_t* noise, float scaling, float noise_a, float noise_b, float in_scale, half_t* out,
                              hipStream_t s);
+// The same tail for K timesteps of the same images (1 <= K <= GDF_MAX_TIMESTEPS): moments and quant_conv once per (image, pixel), then for every k
+// row r = k * B + b of eps / noise / out — each NCHW fp16, row block k starting k * t_stride ELEMENTS after block 0 (t_stride >= B * L * HW;
+// == for one pass over the whole batch, larger for a sub-batch pass of a bigger batch) — with the k-th (noise_a, noise_b, in_scale).
+// The three arrays are HOST pointers of K floats; they travel in the kernel arguments (VaeTimesteps).  Per element the arithmetic is
+// launch_vae_finish's, bit for bit.
+struct VaeTimesteps { float noise_a[GDF_MAX_TIMESTEPS], noise_b[GDF_MAX_TIMESTEPS], in_scale[GDF_MAX_TIMESTEPS]; };
+hipError_t launch_vae_finish_multi(const float* h, int B, int HW, int L, const half_t* wq, const float* bq, const half_t* eps,
+                                   const half_t* noise, float scaling, int K, const float* noise_a, const float* noise_b,
+                                   const float* in_scale, half_t* out, long t_stride, hipStream_t s);
 // VAE decoder head: z = (c_sample * latents + c_eps * noise_pred) * inv_scaling; y = post_quant_conv(z) (wq == NULL: identity)
 // -> NHWC fp16 padded to 8 channels.  latents / noise_pred NCHW fp16 (B, L, H, W); noise_pred may be NULL (plain decode)
 hipError_t launch_vae_dec_prepare(const half_t* lat, const half_t* eps, int B, int HW, int L, float ca, float cb, float inv_sf,

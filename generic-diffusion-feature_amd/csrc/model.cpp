@@ -1020,6 +1020,7 @@ static int run_ops_graph(Plan& P, const Bind& b, hipStream_t s, int evset = -1) 
   const int label = evset >= 0 ? P.timing_label : -1;
   for (auto& g : P.graphs) {
     bool same = g.evset == evset && g.label == label && memcmp(g.key.base, b.base, sizeof b.base) == 0 && memcmp(g.key.f, b.f, sizeof b.f) == 0 &&
+                memcmp(&g.key.mt, &b.mt, sizeof b.mt) == 0 &&
                 g.hook_ptrs.size() == nh;
     for (size_t i = 0; same && i < nh; ++i) same = g.hook_ptrs[i] == b.hooks[i];
     if (same) {

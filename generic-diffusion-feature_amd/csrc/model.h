@@ -142,6 +142,9 @@ struct Bind {
   char* base[BUF_COUNT] = {nullptr};
   void* const* hooks = nullptr;
   float f[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // run-time scalars (VAE: scaling_factor, noise_a, noise_b, input_scale)
+  // VAE encode for several timesteps (gdf_vae_encode_multi): n > 0 makes the tail op fan out — row block k of BUF_TXT / BUF_CTX / BUF_NOISE
+  // starts k * stride fp16 elements after block 0 and uses the k-th triple.  Part of the graph key, like f (no padding: compared bytewise)
+  struct MultiT { long n = 0, stride = 0; float noise_a[GDF_MAX_TIMESTEPS] = {}, noise_b[GDF_MAX_TIMESTEPS] = {}, in_scale[GDF_MAX_TIMESTEPS] = {}; } mt;
   void* p(const Ref& r) const { return (r.buf >= BUF_HOOK0 ? (char*)hooks[r.buf - BUF_HOOK0] : base[r.buf]) + r.off; }
   void* ws(size_t off) const { return base[BUF_WS] + off; }
   void* hook(int slot) const { return hooks[slot]; }
@@ -236,6 +239,9 @@ Model* vae_model_create(const gdf_vae_desc& d);
 int vae_plan_build(const Model& m, Plan& P, int batch, int img_h, int img_w, bool dry);
 int vae_encode(Plan& P, const Model& m, const void* image, const void* eps, const void* noise, float scaling, float noise_a,
                float noise_b, float in_scale, void* out, void* ws, hipStream_t s, float* ms, const char** names, double* flops, int cap);
+// n_t timesteps of the same images on the same plan: eps / noise / out (n_t * B, L, h, w) timestep-major, host coefficient arrays
+int vae_encode_multi(Plan& P, const Model& m, const void* image, const void* eps, const void* noise, float scaling, int n_t,
+                     const float* noise_a, const float* noise_b, const float* in_scale, void* out, void* ws, hipStream_t s);
 
 // ---- VAE decoder (`vae-out`, include/gdf_vae.h) ----
 Model* vae_decoder_create(const gdf_vae_desc& d);

@@ -390,6 +390,13 @@ int gdf_op_vae_finish(const float* h, int B, int HW, int L, const void* wq, cons
   return fin(launch_vae_finish(h, B, HW, L, (const half_t*)wq, bq, (const half_t*)eps, (const half_t*)noise, scaling, noise_a, noise_b, in_scale,
                                (half_t*)out, (hipStream_t)stream), "vae_finish");
 }
+int gdf_op_vae_finish_multi(const float* h, int B, int HW, int L, const void* wq, const float* bq, const void* eps, const void* noise,
+                            float scaling, int n_t, const float* noise_a, const float* noise_b, const float* in_scale, void* out, void* stream) {
+  if (n_t < 1 || n_t > GDF_MAX_TIMESTEPS) { set_error("vae_finish_multi: n_t must be 1.." + std::to_string(GDF_MAX_TIMESTEPS)); return GDF_ERR_ARG; }
+  if (!noise_a || !noise_b || !in_scale) { set_error("vae_finish_multi: null coefficient array"); return GDF_ERR_ARG; }
+  return fin(launch_vae_finish_multi(h, B, HW, L, (const half_t*)wq, bq, (const half_t*)eps, (const half_t*)noise, scaling, n_t, noise_a,
+                                     noise_b, in_scale, (half_t*)out, (long)B * L * HW, (hipStream_t)stream), "vae_finish_multi");
+}
 int gdf_op_vae_dec_prepare(const void* latents, const void* noise_pred, int B, int HW, int L, float c_sample, float c_eps, float inv_scaling,
                            const void* wq, const float* bq, void* nhwc8, void* stream) {
   return fin(launch_vae_dec_prepare((const half_t*)latents, (const half_t*)noise_pred, B, HW, L, c_sample, c_eps, inv_scaling, (const half_t*)wq, bq,

@@ -217,6 +217,11 @@ struct VB : PlanBuilder {
       const bool uq = d.use_quant_conv != 0;
       const Ref qw = wt(v.quant.w), qb = wt(v.quant.b);
       op("vae_sample_noise", 0, [=](const Bind& b, hipStream_t s) {
+        if (b.mt.n > 0)                                                    // gdf_vae_encode_multi: one pass over the moments, n timesteps out
+          return launch_vae_finish_multi((const float*)b.ws(mo), Bq, HW, Lc, uq ? (const half_t*)b.p(qw) : nullptr,
+                                         uq ? (const float*)b.p(qb) : nullptr, (const half_t*)b.base[BUF_TXT], (const half_t*)b.base[BUF_CTX],
+                                         b.f[0], (int)b.mt.n, b.mt.noise_a, b.mt.noise_b, b.mt.in_scale, (half_t*)b.base[BUF_NOISE],
+                                         b.mt.stride, s);
         return launch_vae_finish((const float*)b.ws(mo), Bq, HW, Lc, uq ? (const half_t*)b.p(qw) : nullptr,
                                  uq ? (const float*)b.p(qb) : nullptr, (const half_t*)b.base[BUF_TXT], (const half_t*)b.base[BUF_CTX],
                                  b.f[0], b.f[1], b.f[2], b.f[3], (half_t*)b.base[BUF_NOISE], s);
@@ -365,6 +370,35 @@ int vae_encode(Plan& P, const Model& m, const void* image, const void* eps, cons
     const int rc = plan_run(P, b, s, ms, names, flops, cap);
     if (rc != GDF_OK) return rc;
     if (ms) break;                                                                  // profile: one sub-batch pass
+  }
+  return GDF_OK;
+}
+
+// For images c0 .. c0 + chunk - 1 of a sub-batch pass the tail writes rows k * B + c0 + j: the eps / noise / out pointers advance by c0 latents
+// as in vae_encode, and the row blocks of two timesteps lie B latents apart whatever the chunk is.
+int vae_encode_multi(Plan& P, const Model& m, const void* image, const void* eps, const void* noise, float scaling, int n_t,
+                     const float* noise_a, const float* noise_b, const float* in_scale, void* out, void* ws, hipStream_t s) {
+  if (m.kind != 2) { set_error("gdf_vae_encode_multi on a non-VAE model"); return GDF_ERR_STATE; }
+  if (m.n_set != (int)m.params.size()) { set_error("model weights incomplete"); return GDF_ERR_STATE; }
+  if (!image || !out || !ws) { set_error("null input pointer"); return GDF_ERR_ARG; }
+  if (n_t < 1 || n_t > GDF_MAX_TIMESTEPS) { set_error("n_t must be 1.." + std::to_string(GDF_MAX_TIMESTEPS)); return GDF_ERR_ARG; }
+  if (!noise_a || !noise_b || !in_scale) { set_error("null coefficient array"); return GDF_ERR_ARG; }
+  const gdf_vae_desc& d = m.vae.d;
+  const size_t img_b = (size_t)d.in_channels * P.H * P.W * 2;
+  const int f = 1 << (d.n_levels - 1);
+  const size_t lat_b = (size_t)d.latent_channels * (P.H / f) * (P.W / f) * 2;
+  for (int c0 = 0; c0 < P.batch; c0 += P.chunk) {
+    Bind b;
+    b.base[BUF_WS] = (char*)ws; b.base[BUF_WT] = (char*)m.weights;
+    b.base[BUF_LAT] = (char*)image + (size_t)c0 * img_b;
+    b.base[BUF_TXT] = eps ? (char*)eps + (size_t)c0 * lat_b : nullptr;
+    b.base[BUF_CTX] = noise ? (char*)noise + (size_t)c0 * lat_b : nullptr;
+    b.base[BUF_NOISE] = (char*)out + (size_t)c0 * lat_b;
+    b.f[0] = scaling;
+    b.mt.n = n_t; b.mt.stride = (long)((size_t)P.batch * lat_b / 2);
+    for (int k = 0; k < n_t; ++k) { b.mt.noise_a[k] = noise_a[k]; b.mt.noise_b[k] = noise_b[k]; b.mt.in_scale[k] = in_scale[k]; }
+    const int rc = plan_run(P, b, s, nullptr, nullptr, nullptr, 0);
+    if (rc != GDF_OK) return rc;
   }
   return GDF_OK;
 }

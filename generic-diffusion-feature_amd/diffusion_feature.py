@@ -11,7 +11,8 @@ trajectory, NativeUNet.trajectory) and `generate`: a classifier-free-guided text
 layers keep the features of the UNet calls named by `set_background_extraction` (reference generate_with_extraction.py) — as one
 device-resident run (NativeUNet.sample), and `control=` / `use_control`: ControlNet conditioning of the extraction forward with the
 ControlNet itself a native model (components/control.py, NativeControlNet) and the Canny preprocessor in front of it a device kernel
-(csrc/canny.hip).  `denoising_from` is not.
+(csrc/canny.hip), and `t=[t1, ..., tK]`: K timesteps of the same images from one VAE encode and one UNet forward of K*B rows
+(_extract_multi, split_timesteps).  `denoising_from` is not.
 """
 import copy
 import os
@@ -205,7 +206,11 @@ class FeatureExtractor(nn.Module):
         batch this call makes for the VAE encoder anyway (components/control.py device_canny); the host preprocessors ('depth') get the PIL
         images, restored from a tensor as the reference restores them.
         control_image — native extension — hands over already-processed control images ((B, 3, h, w) in [0, 1] or PIL) instead of running
-        any preprocessor."""
+        any preprocessor.
+        t = [t1, ..., tK] — native extension, UNet versions, 1 <= K <= 8 — extracts the B images at K timesteps in one call: every feature is
+        (K*B, C, H, W), timestep-major (split_timesteps(feats, K) gives the K per-timestep dicts); see _extract_multi."""
+        if isinstance(t, (list, tuple)):                 # several timesteps of the same images: one VAE encode, one UNet forward of K*B rows
+            return self._extract_multi(prompts, batch_size, image, image_type, list(t), denoising_from, use_control, use_ddim_inversion)
         control_pipe = getattr(self, "control_pipe", None) if use_control else None
         if use_control and control_pipe is None:
             raise NotImplementedError("use_control: this extractor was built without control=[...], it has no ControlNet to run")
@@ -363,6 +368,100 @@ class FeatureExtractor(nn.Module):
             self.pipe.unet.last_extra = {}
         return self.feature_store.stored_feats                                           # :517
 
+    def _extract_multi(self, prompts, batch_size, image, image_type, ts, denoising_from, use_control, use_ddim_inversion):
+        """extract() for K timesteps of the same B images: the images are preprocessed and VAE-encoded ONCE (prepare_latents_multi: only the
+        encoder's last kernel fans out), then ONE UNet forward of batch K*B runs with a per-row timestep.  Rows k*B:(k+1)*B of every feature
+        belong to ts[k] (the [negative, positive] convention of generate()); duplicates in `ts` are allowed — each row has its own posterior
+        sample and noise.  The random draws are those of the single-timestep call at batch K*B (native_prepare_latents_multi).  Those rows have
+        the bits of the single-timestep pieces on the same draws: the VAE encode of the B images (plan batch B) with slice k of eps / noise
+        and timestep k's scalars, then extract(t=ts[k], image_type='latents') on the K*B stacked rows.  (NOT necessarily the bits of
+        extract(t=ts[k]) on the images tiled K times: that call encodes at plan batch K*B, and at small sizes the encoder's GEMMs split K
+        by M, i.e. sum in another order)
+        What a K*B-row batch of one timestep supports works here as well: feature_resize, '*-map' hooks, attention=[...], early_exit,
+        precise=, verify.  Each of the following is ONE trajectory or ONE scheduler step and is refused: use_ddim_inversion, use_control,
+        'vae-out', image_type='latents'; so are the flux / PixArt versions and a pipeline without the native VAE encoder."""
+        from components.native import MAX_TIMESTEPS
+        self.feature_store.reset()
+        K = len(ts)
+        if self.version == 'flux' or self.version.startswith('pixart'):
+            raise NotImplementedError("t=[...] exists for the UNet versions ('1-5', '2-1', 'xl', 'pgv2') only: the flux pipeline takes one "
+                                      "strength per call and the PixArt transformer's plan one timestep per batch")
+        if not 1 <= K <= MAX_TIMESTEPS:
+            raise ValueError(f"t=[...] takes 1..{MAX_TIMESTEPS} timesteps per call (the VAE tail kernel carries that many coefficient "
+                             f"triples in its arguments), got {K}")
+        if denoising_from:
+            raise NotImplementedError("denoising_from is not native (see extract)")
+        if use_ddim_inversion:
+            raise NotImplementedError("t=[...] with use_ddim_inversion: every timestep is the end of its own inversion trajectory, there is "
+                                      "no encode to share; call extract once per timestep")
+        if use_control:
+            raise NotImplementedError("t=[...] with use_control: the ControlNets run on one timestep's UNet inputs; call extract once per "
+                                      "timestep")
+        if self.store_vae_output:
+            raise NotImplementedError("t=[...] with 'vae-out' requested: the decoder takes ONE scheduler step's scalars; call extract once "
+                                      "per timestep")
+        if image_type == 'latents':
+            raise ValueError("t=[...] noises the images' encoding once per timestep: image_type must be 'image' or 'tensors' (latents are "
+                             "already noised for one timestep)")
+        if getattr(self.pipe, 'native_vae', None) is None or not hasattr(self.pipe, 'prepare_latents_multi'):
+            raise NotImplementedError("t=[...] shares one NATIVE VAE encode between the timesteps; this pipeline has no native VAE encoder "
+                                      "(GDF_NATIVE_VAE=0)")
+        device = self.device
+        n = K * batch_size
+        prompt_embeds, _neg, pooled, _negp = prompts
+        prompt_embeds = prompt_embeds.repeat(n, 1, 1)
+        if pooled is not None:
+            pooled = pooled.repeat(n, 1, 1).squeeze(1)
+
+        # every timestep through a fresh copy of the scheduler, as the single path picks its one (host-side bookkeeping: see extract)
+        schedulers, t_rows = [], []
+        for tk in ts:
+            sch = self.pipe.scheduler = copy.deepcopy(self.scheduler_backup)
+            sch.set_timesteps(1000, device='cpu')
+            timesteps, _ = self.pipe.get_timesteps(1000, tk / 1000, 'cpu')
+            schedulers.append(sch)
+            t_rows.append(timesteps[:1])
+
+        added_cond_kwargs = {}
+        if self.version in ('xl', 'pgv2'):
+            key = (self.img_size, n, str(prompt_embeds.dtype), str(device))
+            cache = self.__dict__.setdefault('_time_ids_cache', {})
+            if key not in cache:
+                add_time_ids = _get_add_time_ids(self.pipe, (self.img_size, self.img_size), (0, 0),
+                                                 (self.img_size, self.img_size), dtype=prompt_embeds.dtype)
+                cache[key] = add_time_ids.to(device).repeat(n, 1)
+            added_cond_kwargs = {"text_embeds": pooled.to(device), "time_ids": cache[key]}
+
+        if image_type == 'image':
+            image = torch.concat(_map_threads(self.preprocess_image, list(image)), dim=0)
+        elif tuple(image.shape[-2:]) != (self.img_size, self.img_size):
+            image = F.interpolate(image, (self.img_size, self.img_size), mode='bilinear')
+        # (a, b) of timestep k from the scheduler copy that picked it, as the single path's prepare_latents asks ITS copy: get_timesteps left
+        # begin_index on each, and diffusers' Euler / DPM-Solver add_noise reads the sigma at that index
+        latents = self.pipe.prepare_latents_multi(image, [tr.repeat(batch_size) for tr in t_rows], batch_size, prompt_embeds.dtype, device,
+                                                  schedulers=schedulers)
+        # scale_model_input per timestep, each on the scheduler copy that picked it: the torch ops of the single path on the same values
+        latent_model_input = torch.cat([sch.scale_model_input(latents[k * batch_size:(k + 1) * batch_size], t_rows[k])
+                                        for k, sch in enumerate(schedulers)], dim=0)
+        t_vec = torch.cat([tr.repeat(batch_size) for tr in t_rows])                     # host vector, one timestep per row
+
+        attn_ids = None
+        if self.attention and hasattr(self.pipe.unet, 'extra_hook_ids'):
+            attn_ids = attention_map_ids(self.pipe.unet.cfg, self.pipe.unet.hook_names(), self.attention, latents.shape[-1],
+                                         self.img_size // 32, self.img_size // 16)
+            self.pipe.unet.extra_hook_ids = [i for ids in attn_ids.values() for i in ids]
+        if hasattr(self.pipe.unet, 'shared_ctx'):
+            self.pipe.unet.shared_ctx = prompts[0].shape[0] == 1
+        self.pipe.unet(latent_model_input, timestep=t_vec, encoder_hidden_states=prompt_embeds.to(device),
+                       added_cond_kwargs=added_cond_kwargs, down_block_additional_residuals=None,
+                       mid_block_additional_residual=None, return_dict=False)
+        if attn_ids is not None:
+            extra = self.pipe.unet.last_extra
+            maps = {c: [extra[i] for i in ids if i in extra] for c, ids in attn_ids.items()}
+            self.feature_store.stored_feats['attn'] = aggregate_attention(maps, self.img_size // 8)
+            self.pipe.unet.last_extra = {}
+        return self.feature_store.stored_feats
+
     def _controlled_forward(self, control_pipe, raw_image, control_image, latent_model_input, t, prompt_embeds, added_cond_kwargs, source=None):
         """The extraction forward with ControlNet residuals: the ControlNets run on the UNet's own inputs with the UNet plan's shared-ctx
         promise and operand split, write their block straight into that plan's staged residual buffer (no staging copy), and the UNet runs
@@ -497,6 +596,22 @@ class FeatureExtractor(nn.Module):
 
     def get_background_extraction(self):
         return {k: v['feat'] for k, v in self.feature_store.feats.items()}
+
+
+def split_timesteps(feats, K):
+    """The K per-timestep dicts of an `extract(..., t=[t1, ..., tK])` result: entry k holds, for every id, rows k*B:(k+1)*B of the stored
+    (K*B, ...) tensor — VIEWS, no copies."""
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be >= 1")
+    out = [{} for _ in range(K)]
+    for hid, v in feats.items():
+        if v.shape[0] % K:
+            raise ValueError(f"'{hid}' has {v.shape[0]} rows: not a multiple of K = {K}")
+        B = v.shape[0] // K
+        for k in range(K):
+            out[k][hid] = v[k * B:(k + 1) * B]
+    return out
 
 
 DiffusionFeature = FeatureExtractor      # name used by BASELINE.json's north_star

@@ -29,6 +29,7 @@ enum { GDF_OK = 0, GDF_ERR_ARG = 1, GDF_ERR_HIP = 2, GDF_ERR_STATE = 3, GDF_ERR_
 enum { GDF_F16 = 0, GDF_F32 = 1, GDF_BF16 = 2, GDF_BF16X2 = 3, GDF_FP8MX = 4, GDF_F16S = 5 /* 3, 4, 5: gdf_flux_desc.compute_dtype only, see gdf_flux.h */ };
 
 #define GDF_MAX_LEVELS 4
+#define GDF_MAX_TIMESTEPS 8     /* timesteps of one gdf_vae_encode_multi / gdf_op_vae_finish_multi call: the triples travel in the kernel arguments */
 
 /* UNet2DConditionModel hyper-parameters (the `config.json` the reference downloads,
  * components/models.py:18-56; registered at unet_2d_condition.py:171-484). */

@@ -5,6 +5,8 @@
 #define GDF_OPS_H
 #include <stddef.h>
 #include <stdint.h>
+
+#include "gdf.h"    /* GDF_MAX_TIMESTEPS */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -243,6 +245,12 @@ int gdf_op_unpatchify(const void* x, int B, int Cout, int gh, int gw, int p, voi
  * out = in_scale * (noise_a * lat + noise_b * noise) (noise == NULL: in_scale * lat) -> NCHW fp16 (B, L, HW); eps, noise NCHW fp16.  L <= 8. */
 int gdf_op_vae_finish(const float* h, int B, int HW, int L, const void* wq, const float* bq, const void* eps, const void* noise, float scaling,
                       float noise_a, float noise_b, float in_scale, void* out, void* stream);
+/* The same tail for n_t timesteps of the same B images, 1 <= n_t <= GDF_MAX_TIMESTEPS: the moments are read and quant_conv applied once per
+ * (image, pixel); eps, noise and out are NCHW fp16 (n_t * B, L, HW), TIMESTEP-MAJOR — row k * B + b is image b at timestep k and uses
+ * noise_a[k], noise_b[k], in_scale[k].  The three arrays are HOST pointers of n_t floats (they travel in the kernel arguments: no device
+ * table, no copy).  Per element the result has the bits gdf_op_vae_finish gives for the same operands.  L <= 8. */
+int gdf_op_vae_finish_multi(const float* h, int B, int HW, int L, const void* wq, const float* bq, const void* eps, const void* noise,
+                            float scaling, int n_t, const float* noise_a, const float* noise_b, const float* in_scale, void* out, void* stream);
 /* VAE decoder head: z = (c_sample * latents + c_eps * noise_pred) * inv_scaling (noise_pred == NULL: no second term), y = post_quant_conv(z)
  * (1x1: wq fp16 [L][L], bq fp32 [L] or NULL = 0; wq == NULL: identity) -> NHWC pixels of 8 fp16 channels, channels from L up zero.
  * latents, noise_pred NCHW fp16 (B, L, HW).  L <= 8. */

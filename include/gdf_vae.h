@@ -50,6 +50,15 @@ int gdf_vae_plan_create(gdf_model* m, int batch, int img_h, int img_w, gdf_plan*
 int gdf_vae_encode(gdf_plan* p, const void* image, const void* eps, const void* noise, float scaling_factor,
                    float noise_a, float noise_b, float input_scale, void* latents_out, void* workspace, void* stream);
 
+/* The same encode for n_t timesteps of the same B images (1 <= n_t <= GDF_MAX_TIMESTEPS) on the SAME plan and workspace: the encoder runs
+ * once, only its last kernel fans out.  image (B,3,H,W); eps / noise (or NULL) and latents_out are (n_t * B, L, H/f, W/f) fp16 NCHW,
+ * TIMESTEP-MAJOR: row k * B + b is image b at timestep k, made with noise_a[k], noise_b[k], input_scale[k] (HOST arrays of n_t floats,
+ * read before the call returns).  Rows k * B .. k * B + B - 1 have the bits of gdf_vae_encode with the k-th scalars on the k-th eps /
+ * noise slices. */
+int gdf_vae_encode_multi(gdf_plan* p, const void* image, const void* eps, const void* noise, float scaling_factor, int n_t,
+                         const float* noise_a, const float* noise_b, const float* input_scale, void* latents_out, void* workspace,
+                         void* stream);
+
 /* Per-op timing of one sub-batch pass (diagnostics; synchronises). Same contract as gdf_plan_profile. */
 int gdf_vae_plan_profile(gdf_plan* p, const void* image, const void* eps, const void* noise, float scaling_factor,
                          float noise_a, float noise_b, float input_scale, void* latents_out, void* workspace, void* stream,
