@@ -320,6 +320,97 @@ def native_prepare_latents(pipe, image, timestep, batch_size, num_images_per_pro
     return lat.to(dtype)
 
 
+def flux_native_vae_enabled():
+    """GDF_FLUX_NATIVE_VAE=1: the Flux pipelines encode through the native 16-channel VAE (NativeVAEEncoder.encode_packed).  Off by default:
+    the synthetic pipe's average-pool stand-in (and every figure recorded with it) stays what it was until a real checkpoint's full-size
+    parity is on record."""
+    return os.environ.get("GDF_FLUX_NATIVE_VAE", "0") not in ("", "0")
+
+
+def flux_pack_index(L, h, w):
+    """(L, h, w) long tensor: the flat position of latent (c, y, x) inside one image's packed (S, 4L) token block,
+    (y//2 * (w//2) + x//2) * 4L + c*4 + (y%2)*2 + (x%2) — `FluxImg2ImgPipeline._pack_latents` as an index expression (the layout
+    csrc/dit.hip vae_finish_packed_kernel writes)."""
+    c = torch.arange(L).view(L, 1, 1)
+    y = torch.arange(h).view(1, h, 1)
+    x = torch.arange(w).view(1, 1, w)
+    return ((y // 2) * (w // 2) + x // 2) * (4 * L) + c * 4 + (y % 2) * 2 + (x % 2)
+
+
+def flux_scale_noise_sigma(scheduler, timestep):
+    """The sigma `FlowMatchEulerDiscreteScheduler.scale_noise(sample, timestep, noise)` would use — it returns sigma * noise +
+    (1 - sigma) * sample — as a host float, from the scheduler's own table.  The table INDEX is found the way scale_noise finds it, on the
+    host: the begin index the pipeline's get_timesteps set (or the step index once stepping has begun); only a scheduler without one is
+    searched for `timestep`.  The VALUE is the fp32 table entry, not its rounding to the latents' dtype.  A table the pipeline left on the
+    CPU costs no device read; one it moved to the device (set_timesteps(device=...)) costs the 4-byte read of that one entry."""
+    sig = scheduler.sigmas
+    begin = getattr(scheduler, "begin_index", getattr(scheduler, "_begin_index", None))
+    step = getattr(scheduler, "step_index", getattr(scheduler, "_step_index", None))
+    if begin is None:
+        t0 = timestep.flatten()[0] if torch.is_tensor(timestep) else timestep
+        st = scheduler.timesteps
+        idx = scheduler.index_for_timestep(t0.to(st.device) if torch.is_tensor(t0) else t0, st)
+    else:
+        idx = step if step is not None else begin
+    return float(sig[int(idx)])
+
+
+def native_flux_prepare_latents(pipe, image, timestep, batch_size, num_channels_latents, height, width, dtype, device, generator, latents=None):
+    """Drop-in for `FluxImg2ImgPipeline.prepare_latents` (diffusers pipeline_flux_img2img.py: `_encode_vae_image` = (vae.encode(image)
+    .sample() - shift_factor) * scaling_factor, `scheduler.scale_noise`, `_pack_latents`): one libgdf call (NativeVAEEncoder.encode_packed,
+    include/gdf_vae.h gdf_vae_encode_packed).  Returns (packed latents (B, S, 4L), latent_image_ids).
+    Random draws, in the pipeline's order: eps (the posterior sample of vae.encode, one row per IMAGE), then noise (randn_tensor, one row per
+    batch entry); both fp32 on the device in the latent NCHW shape, from `generator`.  sigma: flux_scale_noise_sigma; noise_a = 1 - sigma,
+    noise_b = sigma; shift_factor and scaling_factor from pipe.vae.config.  batch_size an integer multiple of the image count repeats the
+    images (and their eps) as the pipeline's torch.cat does.
+    dtype: the latents come out in the native transformer's 16-bit OPERAND type (fp16 under the default 'auto' mode) when that and `dtype`
+    differ only by fp16 versus bf16.  Nothing between prepare_latents and the transformer does arithmetic on the latents — the pipeline hands
+    them over as they are and NativeFluxTransformer casts them to its operand type first thing — so bf16 latents would only put a second,
+    coarser rounding (8 bits, then 11) in front of the same operand; written in the operand type they are the fp32 value rounded once.  (The
+    pipeline also casts the timestep to latents.dtype: fp16 holds sigma * 1000 more exactly than bf16.)  Any other `dtype` gets a plain cast.
+    One exception: while the transformer's first-forward activation range check is still armed (a real checkpoint's first call,
+    NativeFluxTransformer.arm_range_check) the operand type is not settled — that forward may re-load the model in 'bfloat16x2' — so that one
+    call hands the latents over in `dtype`, the pipeline's bf16, which either outcome takes as it is (bf16 -> fp16 is exact from 2^-17 up):
+    a model that falls back computes what one loaded in 'bfloat16x2' from the start computes, bit for bit."""
+    if latents is not None:
+        raise NotImplementedError("native_flux_prepare_latents: caller-supplied latents are not supported (the pipeline returns them unchanged; "
+                                  "unset GDF_FLUX_NATIVE_VAE for that path)")
+    if isinstance(generator, (list, tuple)):
+        raise NotImplementedError("native_flux_prepare_latents: one generator for the whole batch")
+    enc = pipe.native_vae
+    L = enc.cfg["latent_channels"]
+    if int(num_channels_latents) != L:
+        raise ValueError(f"the transformer expects {num_channels_latents} latent channels, the VAE has {L}")
+    f = 1 << (len(enc.cfg["block_out_channels"]) - 1)
+    image = image.to(device)
+    n_img, _, H, W = image.shape
+    h, w = H // f, W // f
+    if h % 2 or w % 2 or h * f != H or w * f != W:
+        raise ValueError(f"image size {H}x{W} does not give an even latent grid")
+    rep = 1
+    if batch_size > n_img:
+        if batch_size % n_img:
+            raise ValueError(f"Cannot duplicate `image` of batch size {n_img} to {batch_size} text prompts.")
+        rep = batch_size // n_img
+    eps = torch.randn((n_img, L, h, w), generator=generator, device=device, dtype=torch.float32)
+    noise = torch.randn((n_img * rep, L, h, w), generator=generator, device=device, dtype=torch.float32)
+    if rep > 1:
+        image, eps = image.repeat(rep, 1, 1, 1), eps.repeat(rep, 1, 1, 1)
+    vc = pipe.vae.config
+    sigma = flux_scale_noise_sigma(pipe.scheduler, timestep)
+    tr = getattr(pipe, "transformer", None)
+    io = getattr(tr, "io_dtype", None)
+    sixteen = (torch.float16, torch.bfloat16)
+    settled = io in sixteen and getattr(tr, "_range_check_sd", None) is None
+    out_dtype = io if settled else (dtype if dtype in sixteen else torch.float16)
+    tok = enc.encode_packed(image, eps=eps, noise=noise, scaling_factor=float(vc.scaling_factor),
+                            shift_factor=float(getattr(vc, "shift_factor", None) or 0.0), sigma=sigma, out_dtype=out_dtype)
+    if dtype not in sixteen:
+        tok = tok.to(dtype)
+    ids = pipe._prepare_latent_image_ids(n_img * rep, h // 2, w // 2, device, dtype)
+    return tok, ids
+
+
 def native_prepare_latents_multi(pipe, image, timesteps, batch_size, dtype, device, generator=None, schedulers=None):
     """`native_prepare_latents` for K timesteps of the same B images from ONE VAE encode (NativeVAEEncoder.encode_multi): returns
     (K*B, L, h, w) TIMESTEP-MAJOR — rows k*B:(k+1)*B are the B images noised for timesteps[k] (each entry what the single call takes: a
@@ -473,6 +564,10 @@ class SyntheticFluxPipe:
         self.scheduler = types.SimpleNamespace()
         self.image_processor = types.SimpleNamespace(preprocess=SyntheticPipe._preprocess.__get__(self))
         self.last_call = None                      # (sigma, packed latents, prompt embeds, ...) of the last call: test / debugging aid
+        # GDF_FLUX_NATIVE_VAE=1: the true-architecture 16-channel encoder (seeded random weights) in place of the average-pool stand-in
+        self.native_vae = None
+        if flux_native_vae_enabled():
+            self.native_vae = _fill(NativeVAEEncoder(VAE_CONFIGS["flux"], device=device), lambda m: m.init_synthetic(seed + 1))
 
     def _embeds(self, text, shape):
         seed = int.from_bytes(hashlib.sha256(text.encode()).digest()[:4], "little")
@@ -496,11 +591,14 @@ class SyntheticFluxPipe:
         prompts = prompt if isinstance(prompt, (list, tuple)) else [prompt] * B
         enc = torch.cat([self._embeds(p, (1, self.n_txt, self._cfg["joint_attention_dim"])) for p in prompts], 0)
         pooled = torch.cat([self._embeds("pool:" + p, (1, self._cfg["pooled_projection_dim"])) for p in prompts], 0)
-        # synthetic 16-channel 'VAE encode' (8x8 average pooling + fixed channel mix), then 2x2 packing -> (B, S, 64)
-        lat = torch.nn.functional.avg_pool2d(x, 8)
-        mix = torch.linspace(-1.0, 1.0, 48, device=dev).reshape(16, 3)
-        lat = torch.einsum("oc,bchw->bohw", mix, lat) * 2.0
-        Bc, Cc, H, W = lat.shape
+        native = self.native_vae is not None
+        Bc, Cc, H, W = B, 16, x.shape[2] // 8, x.shape[3] // 8
+        if not native:
+            # synthetic 16-channel 'VAE encode' (8x8 average pooling + fixed channel mix), then 2x2 packing -> (B, S, 64)
+            lat = torch.nn.functional.avg_pool2d(x, 8)
+            mix = torch.linspace(-1.0, 1.0, 48, device=dev).reshape(16, 3)
+            lat = torch.einsum("oc,bchw->bohw", mix, lat) * 2.0
+            Bc, Cc, H, W = lat.shape
         gh, gw = H // 2, W // 2
         pack = lambda z: z.view(Bc, Cc, gh, 2, gw, 2).permute(0, 2, 4, 1, 3, 5).reshape(Bc, gh * gw, Cc * 4)
         # img2img schedule (get_timesteps, :606-616): the last int(N * strength) steps remain; only the FIRST of them is run
@@ -511,9 +609,18 @@ class SyntheticFluxPipe:
         if N - t_start < 1:
             raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of "
                              f"pipeline steps is {N - t_start} which is < 1 and not appropriate for this pipeline.")
-        noise = torch.randn(lat.shape, generator=torch.Generator(device=dev).manual_seed(1234), device=dev)
         s0 = sigmas[t_start]
-        z = pack((1.0 - s0) * lat + s0 * noise)                      # FlowMatchEulerDiscreteScheduler.scale_noise
+        if native:
+            # encode + posterior sample + (z - shift) * scaling + scale_noise + packing in ONE libgdf call, written in the transformer's
+            # operand type; draws: eps, then noise (native_flux_prepare_latents), from the stand-in path's fixed seed
+            g = torch.Generator(device=dev).manual_seed(1234)
+            eps = torch.randn((Bc, Cc, H, W), generator=g, device=dev)
+            noise = torch.randn((Bc, Cc, H, W), generator=g, device=dev)
+            z = self.native_vae.encode_packed(x, eps=eps, noise=noise, scaling_factor=self.vae.config.scaling_factor,
+                                              shift_factor=self.vae.config.shift_factor, sigma=s0, out_dtype=self.transformer.io_dtype)
+        else:
+            noise = torch.randn(lat.shape, generator=torch.Generator(device=dev).manual_seed(1234), device=dev)
+            z = pack((1.0 - s0) * lat + s0 * noise)                  # FlowMatchEulerDiscreteScheduler.scale_noise
         img_ids = torch.zeros(gh, gw, 3, device=dev)
         img_ids[..., 1] = torch.arange(gh, device=dev)[:, None]; img_ids[..., 2] = torch.arange(gw, device=dev)[None, :]
         img_ids = img_ids.reshape(gh * gw, 3)
@@ -557,6 +664,23 @@ def _native_flux_from_diffusers(pipe, device):
     net.arm_range_check(sd)
     pipe.transformer = net
     pipe.unet = net
+    if flux_native_vae_enabled():
+        _native_flux_vae_from_diffusers(pipe, device)
+    return pipe
+
+
+def _native_flux_vae_from_diffusers(pipe, device):
+    """GDF_FLUX_NATIVE_VAE=1: pipe.native_vae = the 16-channel AutoencoderKL encoder half in libgdf.so with pipe.vae's weights (filled like the
+    UNet versions' VAE: _fill, i.e. rank 0 loads and broadcasts under a data-parallel launch); pipe.prepare_latents =
+    native_flux_prepare_latents, bound to a weak proxy for the reason given in _native_vae_from_diffusers."""
+    vc = pipe.vae.config
+    enc = NativeVAEEncoder(dict(in_channels=vc.in_channels, latent_channels=vc.latent_channels,
+                                block_out_channels=tuple(vc.block_out_channels), layers_per_block=vc.layers_per_block,
+                                use_quant_conv=int(getattr(vc, "use_quant_conv", True))), device=device)
+    _fill(enc, lambda m: m.load_vae_state_dict(pipe.vae.state_dict()))
+    pipe.native_vae = enc
+    import weakref
+    pipe.prepare_latents = types.MethodType(native_flux_prepare_latents, weakref.proxy(pipe))
     return pipe
 
 

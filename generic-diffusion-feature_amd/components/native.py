@@ -133,6 +133,8 @@ SIGNATURES.update({
     "gdf_vae_plan_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_char_p),
                                        C.POINTER(C.c_double), C.c_int]),
+    "gdf_vae_encode_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
 })
 
 # the decoder half of include/gdf_vae.h (`vae-out`)
@@ -1581,7 +1583,10 @@ class NativeFluxTransformer(_NativeModel):
 # VAE encoder + sampling + noise-add (include/gdf_vae.h): the step before the hot path
 # --------------------------------------------------------------------------------------------- #
 VAE_CONFIGS = {"sd": dict(in_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512), layers_per_block=2,
-                          use_quant_conv=1)}
+                          use_quant_conv=1),
+               # FLUX.1 VAE: the SD block layout, 16 latent channels, no quant_conv (and a shift_factor, a run-time scalar of encode_packed)
+               "flux": dict(in_channels=3, latent_channels=16, block_out_channels=(128, 256, 512, 512), layers_per_block=2,
+                            use_quant_conv=0)}
 
 
 class NativeVAEEncoder(_NativeModel):
@@ -1690,6 +1695,37 @@ class NativeVAEEncoder(_NativeModel):
         f16 = torch.float16
         # (staging buffers of their own names: eps / noise of encode have B rows, these K * B, and a plan serves both calls in turn)
         out, _, _ = plan.run(dev, [("image", image, f16), ("eps_multi", eps, f16), ("noise_multi", noise, f16)], out_shape, call)
+        return out
+
+    def encode_packed(self, image, eps=None, noise=None, scaling_factor=0.3611, shift_factor=0.1159, sigma=0.0, out_dtype=torch.float16):
+        """The Flux latent preparation in one call (gdf_vae_encode_packed, on the plan and workspace encode uses): image (B,3,H,W) in [-1,1];
+        eps / noise (B,L,H/f,W/f) or None.  Returns the 2x2-packed token rows (B, S, 4L), S = (H/2f)(W/2f), in `out_dtype` (fp16 or bf16):
+        (1 - sigma) * scaling_factor * ((mean + std * eps) - shift_factor) + sigma * noise at [b, gy*(W/2f)+gx, c*4 + dy*2 + dx] for latent
+        (b, c, 2gy+dy, 2gx+dx) — `_pack_latents(scheduler.scale_noise((z - shift) * scaling, t, noise))` of FluxImg2ImgPipeline."""
+        dev = self.device
+        B, _, H, W = image.shape
+        f = 1 << (len(self.cfg["block_out_channels"]) - 1)
+        L = self.cfg["latent_channels"]
+        h, w = H // f, W // f
+        if h % 2 or w % 2:
+            raise ValueError("encode_packed needs an even latent grid (2x2 packing)")
+        if out_dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError("encode_packed writes fp16 or bf16 tokens")
+        for t in (eps, noise):
+            if t is not None and tuple(t.shape) != (B, L, h, w):
+                raise ValueError("eps / noise must have the latent shape (B, L, H/f, W/f)")
+        plan = self._plan(B, H, W)
+        lib = self.lib
+        sc = (float(scaling_factor), float(shift_factor), 1.0 - float(sigma), float(sigma), int(out_dtype == torch.bfloat16))
+
+        def call(staged, hook_ptrs, out_ptr, ws_ptr, stream_ptr):
+            vp = lambda a: C.c_void_p(a.data_ptr() if a is not None else 0)
+            _check(lib.gdf_vae_encode_packed(plan.handle, vp(staged[0]), vp(staged[1]), vp(staged[2]), *sc, out_ptr, ws_ptr, stream_ptr),
+                   "vae_encode_packed")
+
+        f16 = torch.float16
+        out, _, _ = plan.run(dev, [("image", image, f16), ("eps", eps, f16), ("noise", noise, f16)], (B, (h // 2) * (w // 2), 4 * L), call,
+                             out_dtype=out_dtype)
         return out
 
 

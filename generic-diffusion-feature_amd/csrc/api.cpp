@@ -161,6 +161,12 @@ int gdf_vae_encode_multi(gdf_plan* p, const void* image, const void* eps, const 
   return vae_encode_multi(p->p, *p->p.model, image, eps, noise, scaling_factor, n_t, noise_a, noise_b, input_scale, latents_out, workspace,
                           (hipStream_t)stream);
 }
+int gdf_vae_encode_packed(gdf_plan* p, const void* image, const void* eps, const void* noise, float scaling_factor, float shift_factor,
+                          float noise_a, float noise_b, int out_bf16, void* tokens_out, void* workspace, void* stream) {
+  if (!p) { set_error("null plan"); return GDF_ERR_ARG; }
+  return vae_encode_packed(p->p, *p->p.model, image, eps, noise, scaling_factor, shift_factor, noise_a, noise_b, out_bf16, tokens_out, workspace,
+                           (hipStream_t)stream);
+}
 int gdf_vae_plan_profile(gdf_plan* p, const void* image, const void* eps, const void* noise, float scaling_factor, float noise_a,
                          float noise_b, float input_scale, void* latents_out, void* workspace, void* stream, float* ms,
                          const char** names, double* flops, int cap) {

@@ -347,7 +347,7 @@ hipError_t launch_softmax_rows(half_t* x, int ld, int R, int n, float scale, hip
 
 // quant_conv of one pixel's 2L moments (1x1: wq fp16 [2L][2L], bq fp32 or NULL = 0; wq == NULL: identity): m[0..L) = mean, m[L..2L) = logvar
 __device__ __forceinline__ void vae_moments(const float* h, size_t pixel, int L2, const half_t* wq, const float* bq, float* m) {
-  float hv[16];
+  float hv[32];
   for (int c = 0; c < L2; ++c) hv[c] = h[pixel * L2 + c];
   for (int o = 0; o < L2; ++o) {
     if (wq) {
@@ -362,13 +362,20 @@ __device__ __forceinline__ void vae_moments(const float* h, size_t pixel, int L2
 
 // One latent element of the VAE tail — the ONE place its arithmetic is written: vae_finish_kernel and vae_finish_multi_kernel both call it, so
 // the same operands give the same bits in either (tests/test_gpu_vae_multi.py compares them bit for bit)
+// (vae_finish_f32 is that value before its one rounding, on operands already in registers: the packed tail reads eps / noise as pairs and
+// rounds to bf16 as well)
+__device__ __forceinline__ float vae_finish_f32(float mean, float logvar, bool has_eps, float eps, bool has_noise, float noise, float scaling,
+                                                 float na, float nb, float in_scale) {
+  float z = mean;
+  if (has_eps) z += expf(0.5f * fminf(fmaxf(logvar, -30.0f), 20.0f)) * eps;
+  float lat = scaling * z;
+  if (has_noise) lat = na * lat + nb * noise;
+  return in_scale * lat;
+}
 __device__ __forceinline__ _Float16 vae_finish_value(float mean, float logvar, const half_t* eps, const half_t* noise, size_t oi,
                                                       float scaling, float na, float nb, float in_scale) {
-  float z = mean;
-  if (eps) z += expf(0.5f * fminf(fmaxf(logvar, -30.0f), 20.0f)) * (float)eps[oi];
-  float lat = scaling * z;
-  if (noise) lat = na * lat + nb * (float)noise[oi];
-  return (_Float16)(in_scale * lat);
+  return (_Float16)vae_finish_f32(mean, logvar, eps != nullptr, eps ? (float)eps[oi] : 0.f, noise != nullptr, noise ? (float)noise[oi] : 0.f,
+                                  scaling, na, nb, in_scale);
 }
 
 __global__ void vae_finish_kernel(const float* h, int HW, int L, const half_t* wq, const float* bq, const half_t* eps,
@@ -429,6 +436,102 @@ hipError_t launch_vae_finish_multi(const float* h, int B, int HW, int L, const h
   for (int k = 0; k < K; ++k) { ts.noise_a[k] = noise_a[k]; ts.noise_b[k] = noise_b[k]; ts.in_scale[k] = in_scale[k]; }
   hipLaunchKernelGGL(vae_finish_multi_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, h, HW, L, wq, bq, eps, noise,
                      scaling, K, ts, out, total, t_stride);
+  return hipGetLastError();
+}
+
+// The tail of the Flux latent preparation (FluxImg2ImgPipeline.prepare_latents: retrieve_latents(vae.encode(image)), (z - shift_factor) *
+// scaling_factor, scheduler.scale_noise, _pack_latents) in one pass over the moments:
+//     out[b][gy * (w/2) + gx][c * 4 + dy * 2 + dx] = na * scaling * ((mean - shift) + std * eps) + nb * noise     at latent (b, c, 2gy + dy, 2gx + dx)
+// i.e. vae_finish_value's arithmetic (vae_finish_f32) on (mean - shift) with in_scale = 1, written as the (B, (h/2)(w/2), 4L) token rows the MMDiT reads, fp16 or bf16 (BF).
+// One lane per token, consecutive lanes = consecutive tokens of a row: a lane reads its four pixels' moment rows (2L fp32 each, 16-byte loads),
+// per channel and dy ONE 4-byte eps / noise pair (the two dx; contiguous across the wave), builds the token's 4L values in registers and writes
+// them with 16-byte stores.  LT = L at compile time (4, 16: everything stays in registers) or 0 (any L <= 16); QC: quant_conv through
+// vae_moments (LT = 0 only).  vec = 0: the operands are not aligned for the wide accesses (or L is odd): element-wise loads and stores.
+template <bool BF, int LT, bool QC>
+__global__ __launch_bounds__(256) void vae_finish_packed_kernel(const float* h, int hh, int ww, int L, const half_t* wq, const float* bq,
+                                                                const half_t* eps, const half_t* noise, float scaling, float shift, float na,
+                                                                float nb, unsigned short* out, long total, int vec) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;      // (b, gy, gx)
+  if (i >= total) return;
+  const int Lr = LT ? LT : L, L2 = 2 * Lr;
+  constexpr int UF = LT ? 64 : 1;                                  // channel loops: unrolled completely for a compile-time L, left alone otherwise
+  const int gw = ww >> 1, gh = hh >> 1;
+  const long r = i / gw;
+  const int gx = (int)(i - r * gw);
+  const long b = r / gh;
+  const int gy = (int)(r - b * gh);
+  const size_t HW = (size_t)hh * ww;
+  unsigned short tok[64];
+#pragma unroll
+  for (int dy = 0; dy < 2; ++dy) {
+    const size_t pix = (size_t)(2 * gy + dy) * ww + 2 * gx;         // dx = 0; dx = 1 is the next pixel
+    float m[2][32];
+#pragma unroll
+    for (int dx = 0; dx < 2; ++dx) {
+      const size_t p = (size_t)b * HW + pix + dx;
+      if (QC) {
+        vae_moments(h, p, L2, wq, bq, m[dx]);
+      } else if (vec) {
+        const float4* hp = (const float4*)(h + p * L2);
+#pragma unroll UF
+        for (int j = 0; j < L2 / 4; ++j) { const float4 v = hp[j]; m[dx][4 * j] = v.x; m[dx][4 * j + 1] = v.y; m[dx][4 * j + 2] = v.z; m[dx][4 * j + 3] = v.w; }
+      } else {
+#pragma unroll UF
+        for (int c = 0; c < L2; ++c) m[dx][c] = h[p * L2 + c];
+      }
+    }
+#pragma unroll UF
+    for (int c = 0; c < Lr; ++c) {
+      const size_t e = ((size_t)b * Lr + c) * HW + pix;
+      float ev[2] = {0.f, 0.f}, nv[2] = {0.f, 0.f};
+      if (vec) {
+        if (eps) { const uint32_t u = *(const uint32_t*)(eps + e); ev[0] = (float)__builtin_bit_cast(half_t, (unsigned short)(u & 0xffffu)); ev[1] = (float)__builtin_bit_cast(half_t, (unsigned short)(u >> 16)); }
+        if (noise) { const uint32_t u = *(const uint32_t*)(noise + e); nv[0] = (float)__builtin_bit_cast(half_t, (unsigned short)(u & 0xffffu)); nv[1] = (float)__builtin_bit_cast(half_t, (unsigned short)(u >> 16)); }
+      } else {
+        if (eps) { ev[0] = (float)eps[e]; ev[1] = (float)eps[e + 1]; }
+        if (noise) { nv[0] = (float)noise[e]; nv[1] = (float)noise[e + 1]; }
+      }
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) {
+        const float v = vae_finish_f32(m[dx][c] - shift, m[dx][Lr + c], eps != nullptr, ev[dx], noise != nullptr, nv[dx], scaling, na, nb, 1.0f);
+        tok[c * 4 + dy * 2 + dx] = BF ? __builtin_bit_cast(unsigned short, (__bf16)v) : __builtin_bit_cast(unsigned short, (_Float16)v);
+      }
+    }
+  }
+  unsigned short* row = out + (size_t)i * 4 * Lr;
+  if (vec) {
+#pragma unroll UF
+    for (int j = 0; j < Lr / 2; ++j) {
+      uint4 q;
+      q.x = (uint32_t)tok[8 * j] | ((uint32_t)tok[8 * j + 1] << 16);
+      q.y = (uint32_t)tok[8 * j + 2] | ((uint32_t)tok[8 * j + 3] << 16);
+      q.z = (uint32_t)tok[8 * j + 4] | ((uint32_t)tok[8 * j + 5] << 16);
+      q.w = (uint32_t)tok[8 * j + 6] | ((uint32_t)tok[8 * j + 7] << 16);
+      *(uint4*)(row + 8 * j) = q;
+    }
+  } else {
+    for (int k = 0; k < 4 * Lr; ++k) row[k] = tok[k];
+  }
+}
+
+hipError_t launch_vae_finish_packed(const float* h, int B, int H, int W, int L, const half_t* wq, const float* bq, const half_t* eps,
+                                    const half_t* noise, float scaling, float shift, float noise_a, float noise_b, int out_bf16, void* out,
+                                    hipStream_t s) {
+  if (L < 1 || L > 16 || H < 2 || W < 2 || (H & 1) || (W & 1) || !out || !h) return hipErrorInvalidValue;   // refused before anything is written
+  const long total = (long)B * (H / 2) * (W / 2);
+  if (total <= 0) return hipSuccess;
+  const auto al = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+  // L even: a moment row is a multiple of 16 bytes and so is a token row; H * W is even, so every eps / noise pair starts on 4 bytes
+  const int vec = (L % 2 == 0) && al(h, 16) && al(out, 16) && al(eps, 4) && al(noise, 4);
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  unsigned short* o = (unsigned short*)out;
+#define GDF_VFP(BF, LT, QC) hipLaunchKernelGGL((vae_finish_packed_kernel<BF, LT, QC>), grid, block, 0, s, h, H, W, L, wq, bq, eps, noise, \
+                                               scaling, shift, noise_a, noise_b, o, total, vec)
+  if (wq) { if (out_bf16) GDF_VFP(true, 0, true); else GDF_VFP(false, 0, true); }
+  else if (L == 16) { if (out_bf16) GDF_VFP(true, 16, false); else GDF_VFP(false, 16, false); }
+  else if (L == 4) { if (out_bf16) GDF_VFP(true, 4, false); else GDF_VFP(false, 4, false); }
+  else { if (out_bf16) GDF_VFP(true, 0, false); else GDF_VFP(false, 0, false); }
+#undef GDF_VFP
   return hipGetLastError();
 }
 

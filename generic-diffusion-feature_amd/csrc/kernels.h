@@ -272,6 +272,13 @@ struct VaeTimesteps { float noise_a[GDF_MAX_TIMESTEPS], noise_b[GDF_MAX_TIMESTEP
 hipError_t launch_vae_finish_multi(const float* h, int B, int HW, int L, const half_t* wq, const float* bq, const half_t* eps,
                                    const half_t* noise, float scaling, int K, const float* noise_a, const float* noise_b,
                                    const float* in_scale, half_t* out, long t_stride, hipStream_t s);
+// The Flux latent-preparation tail (1 <= L <= 16, H and W even): the same moments, out = noise_a * scaling * ((mean - shift) + std * eps) +
+// noise_b * noise — vae_finish's value on (mean - shift) with in_scale = 1 — written 2x2-PACKED: (B, (H/2)(W/2), 4L) fp16 or bf16 (out_bf16), element
+// [b][gy * (W/2) + gx][c * 4 + dy * 2 + dx] = latent (b, c, 2gy + dy, 2gx + dx) (FluxImg2ImgPipeline._pack_latents).  eps / noise NCHW fp16 or NULL.
+// L > 16, odd H or W, a null h / out: hipErrorInvalidValue, nothing launched.
+hipError_t launch_vae_finish_packed(const float* h, int B, int H, int W, int L, const half_t* wq, const float* bq, const half_t* eps,
+                                    const half_t* noise, float scaling, float shift, float noise_a, float noise_b, int out_bf16, void* out,
+                                    hipStream_t s);
 // VAE decoder head: z = (c_sample * latents + c_eps * noise_pred) * inv_scaling; y = post_quant_conv(z) (wq == NULL: identity)
 // -> NHWC fp16 padded to 8 channels.  latents / noise_pred NCHW fp16 (B, L, H, W); noise_pred may be NULL (plain decode)
 hipError_t launch_vae_dec_prepare(const half_t* lat, const half_t* eps, int B, int HW, int L, float ca, float cb, float inv_sf,

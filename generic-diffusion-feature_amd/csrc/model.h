@@ -141,7 +141,8 @@ struct Ref { int buf = BUF_WS; size_t off = 0; };
 struct Bind {
   char* base[BUF_COUNT] = {nullptr};
   void* const* hooks = nullptr;
-  float f[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // run-time scalars (VAE: scaling_factor, noise_a, noise_b, input_scale)
+  float f[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // run-time scalars (VAE: scaling_factor, noise_a, noise_b, input_scale; gdf_vae_encode_packed adds
+                                              // f[4] = shift_factor and f[5] = 1 (fp16) / 2 (bf16), which selects the packed tail: part of the graph key)
   // VAE encode for several timesteps (gdf_vae_encode_multi): n > 0 makes the tail op fan out — row block k of BUF_TXT / BUF_CTX / BUF_NOISE
   // starts k * stride fp16 elements after block 0 and uses the k-th triple.  Part of the graph key, like f (no padding: compared bytewise)
   struct MultiT { long n = 0, stride = 0; float noise_a[GDF_MAX_TIMESTEPS] = {}, noise_b[GDF_MAX_TIMESTEPS] = {}, in_scale[GDF_MAX_TIMESTEPS] = {}; } mt;
@@ -242,6 +243,9 @@ int vae_encode(Plan& P, const Model& m, const void* image, const void* eps, cons
 // n_t timesteps of the same images on the same plan: eps / noise / out (n_t * B, L, h, w) timestep-major, host coefficient arrays
 int vae_encode_multi(Plan& P, const Model& m, const void* image, const void* eps, const void* noise, float scaling, int n_t,
                      const float* noise_a, const float* noise_b, const float* in_scale, void* out, void* ws, hipStream_t s);
+// the Flux latent preparation on the same plan: shift, flow-matching noise, (B, (h/2)(w/2), 4L) token rows in fp16 or bf16
+int vae_encode_packed(Plan& P, const Model& m, const void* image, const void* eps, const void* noise, float scaling, float shift, float noise_a,
+                      float noise_b, int out_bf16, void* out, void* ws, hipStream_t s);
 
 // ---- VAE decoder (`vae-out`, include/gdf_vae.h) ----
 Model* vae_decoder_create(const gdf_vae_desc& d);

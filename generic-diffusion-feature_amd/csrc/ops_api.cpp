@@ -397,6 +397,11 @@ int gdf_op_vae_finish_multi(const float* h, int B, int HW, int L, const void* wq
   return fin(launch_vae_finish_multi(h, B, HW, L, (const half_t*)wq, bq, (const half_t*)eps, (const half_t*)noise, scaling, n_t, noise_a,
                                      noise_b, in_scale, (half_t*)out, (long)B * L * HW, (hipStream_t)stream), "vae_finish_multi");
 }
+int gdf_op_vae_finish_packed(const float* h, int B, int H, int W, int L, const void* wq, const float* bq, const void* eps, const void* noise,
+                             float scaling, float shift, float noise_a, float noise_b, int out_bf16, void* out, void* stream) {
+  return fin(launch_vae_finish_packed(h, B, H, W, L, (const half_t*)wq, bq, (const half_t*)eps, (const half_t*)noise, scaling, shift, noise_a,
+                                      noise_b, out_bf16, out, (hipStream_t)stream), "vae_finish_packed");
+}
 int gdf_op_vae_dec_prepare(const void* latents, const void* noise_pred, int B, int HW, int L, float c_sample, float c_eps, float inv_scaling,
                            const void* wq, const float* bq, void* nhwc8, void* stream) {
   return fin(launch_vae_dec_prepare((const half_t*)latents, (const half_t*)noise_pred, B, HW, L, c_sample, c_eps, inv_scaling, (const half_t*)wq, bq,

@@ -217,6 +217,10 @@ struct VB : PlanBuilder {
       const bool uq = d.use_quant_conv != 0;
       const Ref qw = wt(v.quant.w), qb = wt(v.quant.b);
       op("vae_sample_noise", 0, [=](const Bind& b, hipStream_t s) {
+        if (b.f[5] != 0.f)                                                 // gdf_vae_encode_packed: shift, flow-matching noise, 2x2-packed token rows
+          return launch_vae_finish_packed((const float*)b.ws(mo), Bq, hh, ww, Lc, uq ? (const half_t*)b.p(qw) : nullptr,
+                                          uq ? (const float*)b.p(qb) : nullptr, (const half_t*)b.base[BUF_TXT], (const half_t*)b.base[BUF_CTX],
+                                          b.f[0], b.f[4], b.f[1], b.f[2], b.f[5] == 2.f, b.base[BUF_NOISE], s);
         if (b.mt.n > 0)                                                    // gdf_vae_encode_multi: one pass over the moments, n timesteps out
           return launch_vae_finish_multi((const float*)b.ws(mo), Bq, HW, Lc, uq ? (const half_t*)b.p(qw) : nullptr,
                                          uq ? (const float*)b.p(qb) : nullptr, (const half_t*)b.base[BUF_TXT], (const half_t*)b.base[BUF_CTX],
@@ -305,7 +309,7 @@ static bool gn_from_epilogue() {
 
 Model* vae_model_create(const gdf_vae_desc& d) {
   if (d.n_levels < 1 || d.n_levels > GDF_MAX_LEVELS || d.in_channels < 1 || d.in_channels > 8 || d.latent_channels < 1 ||
-      d.latent_channels > 8 || d.layers_per_block < 1) { set_error("bad vae desc"); return nullptr; }
+      d.latent_channels > 16 || d.layers_per_block < 1) { set_error("bad vae desc"); return nullptr; }   // (16: the Flux VAE; its tail is gdf_vae_encode_packed)
   for (int i = 0; i < d.n_levels; ++i)
     if (d.block_out_channels[i] % 64) { set_error("block_out_channels must be multiples of 64"); return nullptr; }
   Model* m = new Model();
@@ -356,6 +360,7 @@ int vae_encode(Plan& P, const Model& m, const void* image, const void* eps, cons
   if (m.n_set != (int)m.params.size()) { set_error("model weights incomplete"); return GDF_ERR_STATE; }
   if (!image || !out || !ws) { set_error("null input pointer"); return GDF_ERR_ARG; }
   const gdf_vae_desc& d = m.vae.d;
+  if (d.latent_channels > 8) { set_error("gdf_vae_encode writes up to 8 latent channels (NCHW); a 16-channel VAE goes through gdf_vae_encode_packed"); return GDF_ERR_UNSUPPORTED; }
   const size_t img_b = (size_t)d.in_channels * P.H * P.W * 2;                       // bytes per image
   const int f = 1 << (d.n_levels - 1);                                               // spatial reduction (8 for the SD VAEs)
   const size_t lat_b = (size_t)d.latent_channels * (P.H / f) * (P.W / f) * 2;        // bytes per latent
@@ -374,6 +379,32 @@ int vae_encode(Plan& P, const Model& m, const void* image, const void* eps, cons
   return GDF_OK;
 }
 
+// The packed tail (Bind::f[5]: 1 = fp16, 2 = bf16 token rows; f[4] = shift_factor).  A token row belongs to one image, so a sub-batch pass advances
+// the output by whole images: c0 * (h/2)(w/2) * 4L elements = c0 latents, the same byte count as the NCHW layout.
+int vae_encode_packed(Plan& P, const Model& m, const void* image, const void* eps, const void* noise, float scaling, float shift, float noise_a,
+                      float noise_b, int out_bf16, void* out, void* ws, hipStream_t s) {
+  if (m.kind != 2) { set_error("gdf_vae_encode_packed on a non-VAE model"); return GDF_ERR_STATE; }
+  if (m.n_set != (int)m.params.size()) { set_error("model weights incomplete"); return GDF_ERR_STATE; }
+  if (!image || !out || !ws) { set_error("null input pointer"); return GDF_ERR_ARG; }
+  const gdf_vae_desc& d = m.vae.d;
+  const int f = 1 << (d.n_levels - 1);
+  if (((P.H / f) & 1) || ((P.W / f) & 1)) { set_error("gdf_vae_encode_packed: the latent grid must be even in both directions (2x2 packing)"); return GDF_ERR_ARG; }
+  const size_t img_b = (size_t)d.in_channels * P.H * P.W * 2;
+  const size_t lat_b = (size_t)d.latent_channels * (P.H / f) * (P.W / f) * 2;
+  for (int c0 = 0; c0 < P.batch; c0 += P.chunk) {
+    Bind b;
+    b.base[BUF_WS] = (char*)ws; b.base[BUF_WT] = (char*)m.weights;
+    b.base[BUF_LAT] = (char*)image + (size_t)c0 * img_b;
+    b.base[BUF_TXT] = eps ? (char*)eps + (size_t)c0 * lat_b : nullptr;
+    b.base[BUF_CTX] = noise ? (char*)noise + (size_t)c0 * lat_b : nullptr;
+    b.base[BUF_NOISE] = (char*)out + (size_t)c0 * lat_b;
+    b.f[0] = scaling; b.f[1] = noise_a; b.f[2] = noise_b; b.f[3] = 1.0f; b.f[4] = shift; b.f[5] = out_bf16 ? 2.f : 1.f;
+    const int rc = plan_run(P, b, s, nullptr, nullptr, nullptr, 0);
+    if (rc != GDF_OK) return rc;
+  }
+  return GDF_OK;
+}
+
 // For images c0 .. c0 + chunk - 1 of a sub-batch pass the tail writes rows k * B + c0 + j: the eps / noise / out pointers advance by c0 latents
 // as in vae_encode, and the row blocks of two timesteps lie B latents apart whatever the chunk is.
 int vae_encode_multi(Plan& P, const Model& m, const void* image, const void* eps, const void* noise, float scaling, int n_t,
@@ -384,6 +415,7 @@ int vae_encode_multi(Plan& P, const Model& m, const void* image, const void* eps
   if (n_t < 1 || n_t > GDF_MAX_TIMESTEPS) { set_error("n_t must be 1.." + std::to_string(GDF_MAX_TIMESTEPS)); return GDF_ERR_ARG; }
   if (!noise_a || !noise_b || !in_scale) { set_error("null coefficient array"); return GDF_ERR_ARG; }
   const gdf_vae_desc& d = m.vae.d;
+  if (d.latent_channels > 8) { set_error("gdf_vae_encode_multi writes up to 8 latent channels (NCHW)"); return GDF_ERR_UNSUPPORTED; }
   const size_t img_b = (size_t)d.in_channels * P.H * P.W * 2;
   const int f = 1 << (d.n_levels - 1);
   const size_t lat_b = (size_t)d.latent_channels * (P.H / f) * (P.W / f) * 2;

@@ -251,6 +251,13 @@ int gdf_op_vae_finish(const float* h, int B, int HW, int L, const void* wq, cons
  * table, no copy).  Per element the result has the bits gdf_op_vae_finish gives for the same operands.  L <= 8. */
 int gdf_op_vae_finish_multi(const float* h, int B, int HW, int L, const void* wq, const float* bq, const void* eps, const void* noise,
                             float scaling, int n_t, const float* noise_a, const float* noise_b, const float* in_scale, void* out, void* stream);
+/* The Flux latent-preparation tail, 1 <= L <= 16, H and W even: the same moments (h fp32 [B * H * W][2L]; quant_conv as above, NULL for the Flux
+ * VAE), out = noise_a * scaling * ((mean - shift) + std * eps) + noise_b * noise — gdf_op_vae_finish's value on (mean - shift) with in_scale = 1,
+ * so at shift = 0 the same bits — computed in fp32, rounded once to fp16 or bf16 (out_bf16) and written as 2x2-packed token rows
+ * (B, (H/2) * (W/2), 4L): element [b][gy * (W/2) + gx][c * 4 + dy * 2 + dx] is latent (b, c, 2gy + dy, 2gx + dx), the layout of
+ * FluxImg2ImgPipeline._pack_latents.  eps, noise NCHW fp16 (B, L, H, W) or NULL.  L > 16, odd H or W, a null out: an error, nothing written. */
+int gdf_op_vae_finish_packed(const float* h, int B, int H, int W, int L, const void* wq, const float* bq, const void* eps, const void* noise,
+                             float scaling, float shift, float noise_a, float noise_b, int out_bf16, void* out, void* stream);
 /* VAE decoder head: z = (c_sample * latents + c_eps * noise_pred) * inv_scaling (noise_pred == NULL: no second term), y = post_quant_conv(z)
  * (1x1: wq fp16 [L][L], bq fp32 [L] or NULL = 0; wq == NULL: identity) -> NHWC pixels of 8 fp16 channels, channels from L up zero.
  * latents, noise_pred NCHW fp16 (B, L, HW).  L <= 8. */

@@ -59,6 +59,19 @@ int gdf_vae_encode_multi(gdf_plan* p, const void* image, const void* eps, const 
                          const float* noise_a, const float* noise_b, const float* input_scale, void* latents_out, void* workspace,
                          void* stream);
 
+/* ---- Flux: the 16-channel VAE (latent_channels = 16, use_quant_conv = 0, the SD block layout) and what FluxImg2ImgPipeline.prepare_latents does
+ * behind it — `(retrieve_latents(vae.encode(image)) - shift_factor) * scaling_factor`, `scheduler.scale_noise`, `_pack_latents` — in one call on
+ * the SAME plan as gdf_vae_encode (only the last kernel differs):
+ *     z = mean + exp(0.5 * clamp(logvar, -30, 20)) * eps                                   (eps == NULL: posterior mode)
+ *     x = noise_a * scaling_factor * (z - shift_factor) + noise_b * noise                  (noise == NULL: scaling_factor * (z - shift_factor))
+ *   FlowMatchEulerDiscrete.scale_noise at sigma: noise_a = 1 - sigma, noise_b = sigma
+ * computed in fp32, rounded once, and written as the token rows the MMDiT reads: tokens_out (B, (h/2) * (w/2), 4L), fp16 or bf16 (out_bf16 != 0),
+ * element [b][gy * (w/2) + gx][c * 4 + dy * 2 + dx] = x(b, c, 2gy + dy, 2gx + dx), h = H/f, w = W/f both even.  image, eps, noise as for
+ * gdf_vae_encode (fp16 NCHW).  A batch the plan runs in sub-batches advances tokens_out by whole images.  latent_channels <= 16 here;
+ * gdf_vae_encode / gdf_vae_encode_multi and the decoder keep their limit of 8. */
+int gdf_vae_encode_packed(gdf_plan* p, const void* image, const void* eps, const void* noise, float scaling_factor, float shift_factor,
+                          float noise_a, float noise_b, int out_bf16, void* tokens_out, void* workspace, void* stream);
+
 /* Per-op timing of one sub-batch pass (diagnostics; synchronises). Same contract as gdf_plan_profile. */
 int gdf_vae_plan_profile(gdf_plan* p, const void* image, const void* eps, const void* noise, float scaling_factor,
                          float noise_a, float noise_b, float input_scale, void* latents_out, void* workspace, void* stream,
