@@ -173,7 +173,7 @@ SIGNATURES.update({
 })
 
 # the kernel-level entries of include/gdf_ops.h that the package itself calls (SIGNATURES stays the model-level headers' table): the device
-# Canny (csrc/canny.hip)
+# Canny (csrc/canny.hip) and the device image preprocessing (csrc/preproc.hip)
 GDF_CANNY_U8_HWC3, GDF_CANNY_U8_HW, GDF_CANNY_F32_NCHW, GDF_CANNY_F16_NCHW = 0, 1, 2, 3
 GDF_CANNY_DST_U8, GDF_CANNY_DST_F16_NCHW3 = 0, 1
 OP_SIGNATURES = {
@@ -181,6 +181,10 @@ OP_SIGNATURES = {
     "gdf_op_canny_classify": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gdf_op_canny_link": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gdf_op_canny": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    # the device PIL-to-tensor step (csrc/preproc.hip; components/preproc.py calls it)
+    "gdf_op_pil_coeffs": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
+    "gdf_op_pil_resize_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "gdf_op_pil_resize_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -374,6 +374,18 @@ size_t canny_workspace_bytes(int B, int H, int W);
 uint8_t* canny_workspace_cls(void* workspace, int B, int H, int W);     // the class map of the fused entry, behind the linking stage's part
 
 // ------------------------------------------------------------------------------------------------
+// PIL-to-tensor preprocessing: Pillow's 8-bit bicubic resize, convert("RGB"), normalisation (csrc/preproc.hip)
+// ------------------------------------------------------------------------------------------------
+// One axis' table for `in` source and `out` target samples: bounds int32 [out][2] = (xmin, xmax), kk int32 [out][pil_ksize(in, out)]
+int pil_ksize(int in, int out);
+hipError_t launch_pil_coeffs(int in, int out, int* bounds, int* kk, hipStream_t s);
+// src uint8 [src_h][src_w][C], C 1 or 3, any alignment -> dst_u8 uint8 [out_h][out_w][3] and / or dst_f32 fp32 [3][out_h][out_w] (either may be
+// null); workspace pil_resize_workspace_bytes(), 16-byte aligned.  src_h out_w C, 3 out_h out_w < 2^31; in <= 32 out per axis.
+hipError_t launch_pil_resize_u8(const uint8_t* src, int src_h, int src_w, int C, int out_h, int out_w, uint8_t* dst_u8, float* dst_f32,
+                                void* workspace, hipStream_t s);
+size_t pil_resize_workspace_bytes(int src_h, int src_w, int channels, int out_h, int out_w);
+
+// ------------------------------------------------------------------------------------------------
 // weight re-layout (model load time)
 // ------------------------------------------------------------------------------------------------
 // `src_f32` is the source dtype code of gdf_model_set_param: 0 fp16, 1 fp32, 2 bf16

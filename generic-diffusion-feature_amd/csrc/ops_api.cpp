@@ -537,6 +537,50 @@ int gdf_op_canny(const void* src, int src_kind, int B, int H, int W, int low, in
   return fin(launch_canny_link(cls, B, H, W, dst, dst_kind, workspace, (hipStream_t)stream), "canny_link");
 }
 
+// shared argument check of the gdf_op_pil_* entries for one axis pair: sizes, then the largest ratio the kernels' tables are sized for
+static int pil_axis_check(const char* what, int in, int out) {
+  if (in < 1 || out < 1) { set_error(std::string(what) + ": sizes >= 1"); return GDF_ERR_ARG; }
+  if ((long long)in > 32ll * out) {
+    set_error(std::string(what) + ": " + std::to_string(in) + " -> " + std::to_string(out) + " samples: in / out > 32 (ksize > 129) is not built; "
+              "reduce the source on the host first");
+    return GDF_ERR_UNSUPPORTED;
+  }
+  return GDF_OK;
+}
+int gdf_op_pil_coeffs(int in, int out, void* bounds, void* kk, int* ksize, void* stream) {
+  if (!bounds || !kk || !ksize) { set_error("gdf_op_pil_coeffs: null pointer"); return GDF_ERR_ARG; }
+  if (((uintptr_t)bounds | (uintptr_t)kk) & 3) { set_error("gdf_op_pil_coeffs: bounds and kk must be 4-byte aligned"); return GDF_ERR_ARG; }
+  if (int rc = pil_axis_check("gdf_op_pil_coeffs", in, out)) return rc;
+  *ksize = pil_ksize(in, out);
+  return fin(launch_pil_coeffs(in, out, (int*)bounds, (int*)kk, (hipStream_t)stream), "pil_coeffs");
+}
+static int pil_resize_check(const char* what, int src_h, int src_w, int channels, int out_h, int out_w) {
+  if (channels != 1 && channels != 3) { set_error(std::string(what) + ": channels is 1 (mode L) or 3 (mode RGB)"); return GDF_ERR_ARG; }
+  if (int rc = pil_axis_check(what, src_w, out_w)) return rc;
+  if (int rc = pil_axis_check(what, src_h, out_h)) return rc;
+  const size_t lim = 1ull << 31;
+  if ((size_t)src_h * src_w * channels >= lim || (size_t)src_h * out_w * channels >= lim || (size_t)out_h * out_w * 3 >= lim) {
+    set_error(std::string(what) + ": 2^31 bytes or more in the source, the intermediate or the output (32-bit lane indices)");
+    return GDF_ERR_UNSUPPORTED;
+  }
+  return GDF_OK;
+}
+size_t gdf_op_pil_resize_workspace_bytes(int src_h, int src_w, int channels, int out_h, int out_w) {
+  if (pil_resize_check("gdf_op_pil_resize_workspace_bytes", src_h, src_w, channels, out_h, out_w)) return 0;
+  return pil_resize_workspace_bytes(src_h, src_w, channels, out_h, out_w);
+}
+int gdf_op_pil_resize_u8(const void* src, int src_h, int src_w, int channels, int out_h, int out_w, void* dst_u8_hwc3, void* dst_f32_chw,
+                         void* workspace, void* stream) {
+  auto bad = [](const char* msg) { set_error(std::string("gdf_op_pil_resize_u8: ") + msg); return GDF_ERR_ARG; };
+  if (!src || !workspace) return bad("null pointer");
+  if (!dst_u8_hwc3 && !dst_f32_chw) return bad("null pointer: one of dst_u8_hwc3, dst_f32_chw is needed");
+  if ((uintptr_t)dst_f32_chw & 3) return bad("dst_f32_chw must be 4-byte aligned");
+  if ((uintptr_t)workspace & 15) return bad("workspace must be 16-byte aligned");
+  if (int rc = pil_resize_check("gdf_op_pil_resize_u8", src_h, src_w, channels, out_h, out_w)) return rc;
+  return fin(launch_pil_resize_u8((const uint8_t*)src, src_h, src_w, channels, out_h, out_w, (uint8_t*)dst_u8_hwc3, (float*)dst_f32_chw, workspace,
+                                  (hipStream_t)stream), "pil_resize_u8");
+}
+
 // element type of the 16-bit operands of the MMDiT entry points below, per calling thread (GDF_F16 default)
 static thread_local int g_e16_bf = 0;
 int gdf_op_set_e16(int dtype) {

@@ -12,7 +12,8 @@ layers keep the features of the UNet calls named by `set_background_extraction` 
 device-resident run (NativeUNet.sample), and `control=` / `use_control`: ControlNet conditioning of the extraction forward with the
 ControlNet itself a native model (components/control.py, NativeControlNet) and the Canny preprocessor in front of it a device kernel
 (csrc/canny.hip), and `t=[t1, ..., tK]`: K timesteps of the same images from one VAE encode and one UNet forward of K*B rows
-(_extract_multi, split_timesteps).  `denoising_from` is not.
+(_extract_multi, split_timesteps), and `device_preprocess=`: the PIL-to-tensor step in front of all of it as device kernels
+(components/preproc.py, csrc/preproc.hip).  `denoising_from` is not.
 """
 import copy
 import os
@@ -69,8 +70,14 @@ class FeatureExtractor(nn.Module):
                  early_exit=False, # native extension, OPT-IN: stop the denoiser forward after the last requested layer (the reference always runs the
                                    # whole forward and discards `noise_pred`; the returned features are bit-identical either way).  Ignored when
                                    # 'vae-out' (which needs the model output) is requested
+                 device_preprocess=None,  # native extension, OPT-IN (UNet and PixArt versions): the PIL-to-tensor step of image_type='image' on the
+                                   # device — the images' bytes are uploaded as uint8 and Pillow's bicubic resize, convert("RGB") and the normalisation run
+                                   # as kernels (components/preproc.py, csrc/preproc.hip), bit for bit what preprocess_image gives.  None reads
+                                   # GDF_DEVICE_PREPROCESS (default off); True needs a HIP device
                  ):
         super().__init__()
+        from components.preproc import resolve_flag
+        self.device_preprocess = resolve_flag(device_preprocess, device)                  # (True on a device that is not a HIP one raises, before anything loads)
         if control and (version == 'flux' or version.startswith('pixart')):
             raise NotImplementedError("control= exists for the UNet versions ('1-5', '2-1', 'xl', 'pgv2') only: the native ControlNet is the "
                                       "encoder half of a UNet (include/gdf_control.h)")
@@ -152,6 +159,19 @@ class FeatureExtractor(nn.Module):
         if not is_tensor:
             return self.pipe.image_processor.preprocess(self._preprocess_basic(x))
         return self.pipe.image_processor.preprocess([x[i] for i in range(x.shape[0])])
+
+    def preprocess_images_device(self, images):
+        """torch.concat([preprocess_image(i) for i in images]) made on the device: (B, 3, img_size, img_size) fp32 there, the same bits
+        (components/preproc.py device_preprocess; modes other than RGB / L take preprocess_image itself, image by image)"""
+        from components.preproc import device_preprocess
+        return device_preprocess(images, self.img_size, self.device, host_fn=self.preprocess_image)
+
+    def _preprocess_images(self, images):
+        """the batch of image_type='image' (reference :358-364): on the device when the extractor was built with device_preprocess, else on the
+        host's thread pool"""
+        if getattr(self, 'device_preprocess', False):
+            return self.preprocess_images_device(images)
+        return torch.concat(_map_threads(self.preprocess_image, list(images)), dim=0)
 
     def restore_from_tensor_to_image(self, x):
         """(B, 3, h, w) in [-1, 1] -> list of RGB PIL images (reference :143-144, VaeImageProcessor.postprocess with do_denormalize): to fp32,
@@ -297,7 +317,7 @@ class FeatureExtractor(nn.Module):
             latents = image.to(device)
         else:
             if image_type == 'image':                                                    # :358-364
-                image = torch.concat(_map_threads(self.preprocess_image, list(image)), dim=0)
+                image = self._preprocess_images(list(image))
             elif tuple(image.shape[-2:]) != (self.img_size, self.img_size):
                 if derive and control_pipe.needs_source():
                     # the reference, literally (:259-263, :433): restore to PIL, _preprocess_basic (PIL's resize, not the bilinear one below), and
@@ -433,7 +453,7 @@ class FeatureExtractor(nn.Module):
             added_cond_kwargs = {"text_embeds": pooled.to(device), "time_ids": cache[key]}
 
         if image_type == 'image':
-            image = torch.concat(_map_threads(self.preprocess_image, list(image)), dim=0)
+            image = self._preprocess_images(list(image))
         elif tuple(image.shape[-2:]) != (self.img_size, self.img_size):
             image = F.interpolate(image, (self.img_size, self.img_size), mode='bilinear')
         # (a, b) of timestep k from the scheduler copy that picked it, as the single path's prepare_latents asks ITS copy: get_timesteps left

@@ -370,6 +370,27 @@ int gdf_op_canny_classify(const void* src, int src_kind, int B, int H, int W, in
 int gdf_op_canny_link(const void* cls, int B, int H, int W, void* dst, int dst_kind, void* workspace, void* stream);
 int gdf_op_canny(const void* src, int src_kind, int B, int H, int W, int low, int high, void* dst, int dst_kind, void* workspace, void* stream);
 
+/* ---- PIL-to-tensor preprocessing on the device (csrc/preproc.hip): preprocess_image of one PIL image,
+ * pipe.image_processor.preprocess(img.resize((S, S)).convert("RGB")), i.e. Pillow's ImagingResample (8 bits per channel, BICUBIC, whole-image box)
+ * restated in its own fixed-point arithmetic, equal to Pillow byte for byte.  Stream-ordered, caller-owned buffers, no device -> host
+ * read and no host synchronisation; every argument is checked before the first launch.
+ *   gdf_op_pil_coeffs   one axis' table for `in` source and `out` target samples, made on the device in IEEE double without fused multiply-add:
+ *                       bounds int32 [out][2] = (xmin, xmax), kk int32 [out][*ksize] (2^22 fixed point, entries from xmax up zero); *ksize (host) =
+ *                       2 ceil(2 max(in / out, 1)) + 1.  One launch.
+ *   gdf_op_pil_resize_u8  src uint8 [src_h][src_w][channels], channels 1 (mode L) or 3 (mode RGB), ANY byte alignment ->
+ *                       dst_u8_hwc3  uint8 [out_h][out_w][3] = np.array(Image.fromarray(src).resize((out_w, out_h)).convert("RGB")), and / or
+ *                       dst_f32_chw  fp32 [3][out_h][out_w] = (fp32(u) / 255) * 2 - 1 of those bytes: one row of the (B, 3, S, S) batch
+ *                       (either may be NULL, not both).  Horizontal pass first into a uint8 intermediate, then vertical; a pass whose axis already
+ *                       has the target size is skipped, with both skipped the bytes pass through.  At most four launches.
+ *   workspace           gdf_op_pil_resize_workspace_bytes(...) bytes (0 for arguments gdf_op_pil_resize_u8 refuses), 16-byte aligned: the two
+ *                       tables and the intermediate; nothing is kept in it between calls
+ * Sizes >= 1 (1 x 1 is legal).  in / out > 32 on an axis (ksize > 129) and 2^31 bytes or more in a buffer are GDF_ERR_UNSUPPORTED; every other
+ * refused argument is GDF_ERR_ARG. */
+int gdf_op_pil_coeffs(int in, int out, void* bounds, void* kk, int* ksize, void* stream);
+size_t gdf_op_pil_resize_workspace_bytes(int src_h, int src_w, int channels, int out_h, int out_w);
+int gdf_op_pil_resize_u8(const void* src, int src_h, int src_w, int channels, int out_h, int out_w, void* dst_u8_hwc3, void* dst_f32_chw,
+                         void* workspace, void* stream);
+
 /* ---- MMDiT (Flux) kernels (reference files cited in csrc/dit.hip, gdf_flux.h) ---- */
 
 /* Element type of the 16-bit operands ("e16": A, W, out16, q/k/v/o, y) of the MMDiT entry points below, per calling thread:
