@@ -6,6 +6,7 @@ extract_feature.py (/root/reference/extract_feature.py:18-43 flags, :113-148 out
   --sample_name_first <output_dir>/<name>/<layer_id>.npy
   --aggregate_output  <output_dir>/<name>.npy                       all layers nearest-resized to the largest H,W and
                                                                     concatenated over channels
+    --aggregate_mode bilinear, --aggregate_size N [M]               the same file in the evaluators' form: bilinear, to N x N (N x M)
   --t T1 T2 ...       <output_dir>/t<T>/<one of the layouts above>  one tree per timestep (a single --t T: no t<T>/ level)
   <name> = original file stem (--use_original_filename; parent-dir/stem with --nested_input_dir) or <split><index>.
 
@@ -59,6 +60,13 @@ def parse_args(argv=None):
     p.add_argument('--prompt_file', type=str, default='prompt.txt')
     p.add_argument('--output_dir', type=str, default='./output/')
     p.add_argument('--aggregate_output', action='store_true')
+    p.add_argument('--aggregate_mode', type=str, default=None, choices=('nearest', 'bilinear'),
+                   help="native extension, with --aggregate_output: how the layers are resized.  'nearest' (default) = the reference CLI's files; "
+                        "'bilinear' = F.interpolate(v, size, mode='bilinear'), what the reference's correspondence and segmentation evaluators "
+                        "compute from the per-layer features")
+    p.add_argument('--aggregate_size', type=int, nargs='+', default=None, metavar='N',
+                   help='native extension, with --aggregate_output: the grid the layers are resized to, N (N x N) or N M (N rows, M columns).  '
+                        'Default: the largest layer grid')
     p.add_argument('--use_original_filename', action='store_true')
     p.add_argument('--split', type=str, default='train')
     p.add_argument('--sample_name_first', action='store_true')
@@ -82,6 +90,13 @@ def parse_args(argv=None):
                    help='native extension (not in the reference CLI): data-parallel over N GPUs of this node.  Started as a plain process '
                         '(`python3 extract_feature.py --gpus 8 ...`) the script starts its N ranks itself; under torchrun it must equal WORLD_SIZE')
     args = p.parse_args(argv)
+    if not args.aggregate_output and (args.aggregate_mode is not None or args.aggregate_size is not None):
+        p.error("--aggregate_mode / --aggregate_size are only meaningful with --aggregate_output")
+    if args.aggregate_size is not None:
+        if len(args.aggregate_size) > 2 or min(args.aggregate_size) < 1:
+            p.error("--aggregate_size takes one or two positive integers: N or N M")
+        args.aggregate_size = args.aggregate_size[0] if len(args.aggregate_size) == 1 else tuple(args.aggregate_size)
+    args.aggregate_mode = args.aggregate_mode or 'nearest'
     if args.t is not None:
         if len(args.t) == 1:
             args.t = args.t[0]                      # one value: an int, the single-timestep path and the output tree without t<T>/ directories
@@ -141,8 +156,12 @@ class HostWriter:
         originals = [v for v in feats.values() if torch.is_tensor(v)]      # what the extractor handed out (aggregation rebinds `feats`)
         with ctx:
             if self.args.aggregate_output:                      # reference :113-125; device tensors: resize_concat_kernel
-                from components.postproc import resize_concat
-                feats = {None: resize_concat(list(feats.values()))}
+                from components.postproc import aggregate, resize_concat
+                mode, size = getattr(self.args, 'aggregate_mode', 'nearest'), getattr(self.args, 'aggregate_size', None)
+                if mode == 'nearest' and size is None:          # the reference CLI's files
+                    feats = {None: resize_concat(list(feats.values()))}
+                else:                                           # the evaluators' form; device tensors: aggregate_kernel
+                    feats = {None: aggregate(list(feats.values()), size, mode)}
             for k, v in feats.items():
                 v = v.detach()
                 if v.is_cuda:

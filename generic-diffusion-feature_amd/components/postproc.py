@@ -2,6 +2,8 @@
 the hot path:
 
   resize_concat      extract_feature.py:113-125   `--aggregate_output`: nearest-resize every layer to the largest H, W, concat
+  aggregate          correspondence/aggregation_network.py:62-66, scarce_segmentation/task-pixel.py:50-55   the evaluators' form of it:
+                     F.interpolate(v, size, mode='bilinear') of every layer + torch.cat(dim=1), one launch per 16 layers
   avg_pool           components/feature_extractor.py:51-53   `feature_resize` (adaptive_avg_pool2d to (H/r, W/r))
   aggregate_maps     components/attention.py:238-244, 141-161 + diffusion_feature.py:492-500   aggregated `attn` feature
 
@@ -23,6 +25,16 @@ _SIG = {
                                   C.c_void_p]),
     "gdf_op_maps_mean": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
+
+
+class AggSrc(C.Structure):
+    """gdf_agg_src (include/gdf_ops.h)"""
+    _fields_ = [("ptr", C.c_void_p), ("f32", C.c_int), ("sb", C.c_long), ("sc", C.c_long), ("sy", C.c_long), ("sx", C.c_long),
+                ("C", C.c_int), ("H", C.c_int), ("W", C.c_int), ("coff", C.c_int)]
+
+
+_SIG["gdf_op_aggregate"] = (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p])
+AGG_MAX = 16                                             # sources of one gdf_op_aggregate launch
 _lib = None
 
 
@@ -62,6 +74,45 @@ def resize_concat(feats, size=None):
             native._check(_L().gdf_op_resize_concat(C.c_void_p(v.data_ptr()), int(v.dtype == torch.float32), sb, sc, sy, sx, b, c, h, w,
                                                     C.c_void_p(out.data_ptr()), ctot, off, S, _stream(dev)), "resize_concat")
             off += c
+    return out
+
+
+def aggregate(feats, size=None, mode='bilinear', dtype=torch.float16):
+    """[(B, C_l, H_l, W_l) tensors, any strides] -> (B, sum C_l, OH, OW) `dtype` (fp16 or fp32):
+    torch.cat([F.interpolate(v, size, mode=mode) for v in feats], 1), mode 'bilinear' (align_corners=False) or 'nearest'.
+    size: an int, (OH, OW), or None = the largest W (as resize_concat).  Device tensors: aggregate_kernel, one launch per 16 tensors."""
+    feats = list(feats)
+    if mode not in ('nearest', 'bilinear'):
+        raise ValueError(f"mode is 'nearest' or 'bilinear', not {mode!r}")
+    if dtype not in (torch.float16, torch.float32):
+        raise ValueError(f"dtype is torch.float16 or torch.float32, not {dtype}")
+    if not feats or any(v.dim() != 4 for v in feats):
+        raise ValueError("feats is a non-empty list of 4-D tensors")
+    if size is None:
+        size = max(v.shape[-1] for v in feats)
+    OH, OW = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if not feats[0].is_cuda:
+        return torch.cat([F.interpolate(v.float(), (OH, OW), mode=mode) for v in feats], 1).to(dtype)
+    dev = feats[0].device
+    B = feats[0].shape[0]
+    if any(v.shape[0] != B or v.device != dev for v in feats):
+        raise ValueError("every tensor has the same batch size and device")
+    feats = [v if v.dtype in (torch.float16, torch.float32) else v.float() for v in feats]
+    ctot = sum(v.shape[1] for v in feats)
+    with torch.cuda.device(dev):
+        out = torch.empty(B, ctot, OH, OW, dtype=dtype, device=dev)
+        off = 0
+        for i in range(0, len(feats), AGG_MAX):
+            part = feats[i:i + AGG_MAX]
+            srcs = (AggSrc * len(part))()
+            for s, v in zip(srcs, part):
+                s.ptr, s.f32 = v.data_ptr(), int(v.dtype == torch.float32)
+                s.sb, s.sc, s.sy, s.sx = v.stride()
+                _, s.C, s.H, s.W = v.shape
+                s.coff = off
+                off += v.shape[1]
+            native._check(_L().gdf_op_aggregate(srcs, len(part), B, C.c_void_p(out.data_ptr()), int(dtype == torch.float32), ctot, OH, OW,
+                                                int(mode == 'bilinear'), _stream(dev)), "aggregate")
     return out
 
 

@@ -329,6 +329,12 @@ hipError_t launch_small_linear(const float* x, int ldx, int M, int K, const half
 // [coff, coff + C) of out (B, Ctot, S, S) fp16 contiguous
 hipError_t launch_resize_concat(const half_t* s16, const float* s32, long sb, long sc, long sy, long sx, int B, int C, int H, int W,
                                 half_t* out, int Ctot, int coff, int S, hipStream_t s);
+// F.interpolate(v, (OH, OW), mode='bilinear') (align_corners = false, no antialias) of n <= AGG_MAX layers + torch.cat(dim=1) in ONE launch:
+// source l is a logical (B, C, H, W) tensor, fp16 or fp32, element strides sb/sc/sy/sx, and lands in channels [coff, coff + C) of
+// out (B, Ctot, OH, OW) contiguous, fp16 or fp32.  fp32 coordinates and blend as ATen's upsample_bilinear2d, one rounding to the output type.
+enum { AGG_MAX = 16 };
+struct AggSrc { const void* ptr; int f32; long sb, sc, sy, sx; int C, H, W, coff; };
+hipError_t launch_aggregate(const AggSrc* srcs, int n, int B, void* out, int out_f32, int Ctot, int OH, int OW, hipStream_t s);
 // adaptive_avg_pool2d to (H/r, W/r) of a channels-last hook (B,C,H,W; strides sb, 1, sy, sx) -> (B, H/r, W/r, C) fp16: the r x r mean
 // where r divides H and W, ATen's longer windows [floor(o H / OH), ceil((o + 1) H / OH)) otherwise
 hipError_t launch_avg_pool(const half_t* src, long sb, long sy, long sx, int B, int C, int H, int W, int r, half_t* out, hipStream_t s);

@@ -453,6 +453,34 @@ int gdf_op_resize_concat(const void* src, int src_f32, long sb, long sc, long sy
   return fin(launch_resize_concat(src_f32 ? nullptr : (const half_t*)src, src_f32 ? (const float*)src : nullptr, sb, sc, sy, sx, B, C, H, W,
                                   (half_t*)out, Ctot, coff, S, (hipStream_t)stream), "resize_concat");
 }
+int gdf_op_aggregate(const gdf_agg_src* srcs, int n, int B, void* out, int out_f32, int Ctot, int OH, int OW, int mode, void* stream) {
+  auto bad = [](const char* msg) { set_error(std::string("gdf_op_aggregate: ") + msg); return GDF_ERR_ARG; };
+  if (n < 1 || n > AGG_MAX) return bad("1 <= n <= 16 sources");
+  if (!srcs || !out) return bad("null pointer");
+  if (mode != 0 && mode != 1) return bad("mode is 0 (nearest) or 1 (bilinear)");
+  if (B < 0 || OH < 1 || OW < 1) return bad("B >= 0, OH and OW >= 1");
+  if (mode == 0 && (out_f32 || OH != OW)) return bad("nearest writes fp16 and a square grid (gdf_op_resize_concat's kernel)");
+  size_t blocks = 0;
+  AggSrc a[AGG_MAX];
+  for (int k = 0; k < n; ++k) {
+    const gdf_agg_src& e = srcs[k];
+    if (!e.ptr) return bad("null source pointer");
+    if (e.C < 1 || e.H < 1 || e.W < 1) return bad("C, H and W >= 1");
+    if (e.coff < 0 || (long)e.coff + e.C > Ctot) return bad("coff < 0 or coff + C > Ctot");
+    blocks += (size_t)B * OH * ((e.C + 63) / 64);
+    a[k] = AggSrc{e.ptr, e.f32, e.sb, e.sc, e.sy, e.sx, e.C, e.H, e.W, e.coff};
+  }
+  if (blocks >= (1ull << 31)) { set_error("gdf_op_aggregate: 2^31 workgroups or more; split the batch"); return GDF_ERR_UNSUPPORTED; }
+  if (B == 0) return GDF_OK;
+  if (mode == 1) return fin(launch_aggregate(a, n, B, out, out_f32, Ctot, OH, OW, (hipStream_t)stream), "gdf_op_aggregate");
+  for (int k = 0; k < n; ++k) {
+    const AggSrc& e = a[k];
+    const hipError_t rc = launch_resize_concat(e.f32 ? nullptr : (const half_t*)e.ptr, e.f32 ? (const float*)e.ptr : nullptr, e.sb, e.sc, e.sy, e.sx,
+                                               B, e.C, e.H, e.W, (half_t*)out, Ctot, e.coff, OH, (hipStream_t)stream);
+    if (rc != hipSuccess) return fin(rc, "gdf_op_aggregate");
+  }
+  return GDF_OK;
+}
 int gdf_op_avg_pool(const void* src, long sb, long sy, long sx, int B, int C, int H, int W, int r, void* out, void* stream) {
   return fin(launch_avg_pool((const half_t*)src, sb, sy, sx, B, C, H, W, r, (half_t*)out, (hipStream_t)stream), "avg_pool");
 }

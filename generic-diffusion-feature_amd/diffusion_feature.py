@@ -611,6 +611,18 @@ class FeatureExtractor(nn.Module):
             return x, image
         return x
 
+    def aggregate(self, feats=None, size=128, mode='bilinear', dtype=torch.float16):
+        """The evaluators' first step on a feature dict (reference correspondence/aggregation_network.py:62-66, scarce_segmentation/
+        task-pixel.py:50-55): torch.cat([F.interpolate(f, size, mode=mode) for f in feats.values()], 1) -> (B, sum C, OH, OW) `dtype`.
+        feats defaults to the dict of the last extract(); the values are taken in dict order (hook execution order, `attn` last).
+        Device tensors: one aggregate_kernel launch per 16 layers (components/postproc.py aggregate)."""
+        from components.postproc import aggregate
+        if feats is None:
+            feats = self.feature_store.stored_feats
+        if not feats:
+            raise ValueError("aggregate: no features (call extract() first or pass feats=)")
+        return aggregate(list(feats.values()) if isinstance(feats, dict) else list(feats), size, mode, dtype)
+
     def set_background_extraction(self, idxs):
         self.feature_store.store_idx = idxs
 

@@ -304,6 +304,20 @@ int gdf_op_sincos_pos_embed(float* out, int C, int gh, int gw, int base_size, fl
  * [coff, coff + C) of out (B, Ctot, S, S) fp16 contiguous; one call per layer performs F.interpolate + torch.cat(dim=1). */
 int gdf_op_resize_concat(const void* src, int src_f32, long sb, long sc, long sy, long sx, int B, int C, int H, int W, void* out,
                          int Ctot, int coff, int S, void* stream);
+/* The evaluators' form of the same stage (correspondence/aggregation_network.py:62-66, scarce_segmentation/task-pixel.py:50-55):
+ * torch.cat([F.interpolate(v, (OH, OW), mode='bilinear') for v in feats], 1) — ONE launch of aggregate_kernel over n <= 16 sources.
+ *   srcs   source l is a logical (B, C, H, W) tensor, fp16 (f32 = 0) or fp32, with element strides sb/sc/sy/sx (hooks: channels-last, sc = 1;
+ *          `attn`: NCHW), read only; it lands in channels [coff, coff + C) of out.  Callers with more sources make several calls.
+ *   out    (B, Ctot, OH, OW) contiguous, fp16 (out_f32 = 0) or fp32; channels no source names are not written
+ *   mode   1 bilinear: align_corners = False, no antialias, as ATen's upsample_bilinear2d: in fp32, scale = (float)in / out,
+ *          src = max(0, scale * (dst + 0.5f) - 0.5f), i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1; the four taps are
+ *          combined in fp32 and rounded once.  Where H == OH and W == OW the result is the source value cast to the output type.
+ *          0 nearest: the bits of gdf_op_resize_concat, one launch of its kernel per source; fp16 output and OH == OW only.
+ * Stream-ordered, no workspace, nothing read back.  n < 1 or > 16, a null pointer, C, H, W, OH or OW below 1, B < 0, coff < 0 or
+ * coff + C > Ctot, an unknown mode, or nearest with out_f32 or OH != OW: GDF_ERR_ARG before any launch.  B == 0 is a successful no-op. */
+typedef struct gdf_agg_src { const void* ptr; int f32; long sb, sc, sy, sx; int C, H, W, coff; } gdf_agg_src;
+int gdf_op_aggregate(const gdf_agg_src* srcs, int n, int B, void* out, int out_f32, int Ctot, int OH, int OW,
+                     int mode /* 0 nearest, 1 bilinear */, void* stream);
 /* `feature_resize` (components/feature_extractor.py:51-53): adaptive_avg_pool2d to (OH, OW) = (H / r, W / r) (integer division) of a
  * channels-last hook (strides sb, 1, sy, sx; C % 8 == 0) -> (B, OH, OW, C) fp16, fp32 accumulation.  Output row o averages source rows
  * [floor(o H / OH), ceil((o + 1) H / OH)), columns likewise: the r x r window where r divides the size, otherwise longer windows that may
