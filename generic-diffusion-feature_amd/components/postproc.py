@@ -4,6 +4,8 @@ the hot path:
   resize_concat      extract_feature.py:113-125   `--aggregate_output`: nearest-resize every layer to the largest H, W, concat
   aggregate          correspondence/aggregation_network.py:62-66, scarce_segmentation/task-pixel.py:50-55   the evaluators' form of it:
                      F.interpolate(v, size, mode='bilinear') of every layer + torch.cat(dim=1), one launch per 16 layers
+  nn_match / find_nn_source_correspondences   correspondence/correspondence/correspondence_utils.py:113-138   the evaluators' second step:
+                     nearest neighbours of N source points among the load-size target pixels, without either load-size map (csrc/corres.hip)
   avg_pool           components/feature_extractor.py:51-53   `feature_resize` (adaptive_avg_pool2d to (H/r, W/r))
   aggregate_maps     components/attention.py:238-244, 141-161 + diffusion_feature.py:492-500   aggregated `attn` feature
 
@@ -13,6 +15,7 @@ out `.cpu()` copies, feature_extractor.py:65-66) are plain data already off the 
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -35,6 +38,9 @@ class AggSrc(C.Structure):
 
 _SIG["gdf_op_aggregate"] = (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p])
 AGG_MAX = 16                                             # sources of one gdf_op_aggregate launch
+_SIG["gdf_op_nn_match_workspace"] = (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int])
+_SIG["gdf_op_nn_match"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_size_t, C.c_void_p])
 _lib = None
 
 
@@ -114,6 +120,77 @@ def aggregate(feats, size=None, mode='bilinear', dtype=torch.float16):
             native._check(_L().gdf_op_aggregate(srcs, len(part), B, C.c_void_p(out.data_ptr()), int(dtype == torch.float32), ctot, OH, OW,
                                                 int(mode == 'bilinear'), _stream(dev)), "aggregate")
     return out
+
+
+def _agg_src(v):
+    s = AggSrc()
+    s.ptr, s.f32 = v.data_ptr(), int(v.dtype == torch.float32)
+    s.sb, s.sc, s.sy, s.sx = v.stride()
+    _, s.C, s.H, s.W = v.shape
+    return s
+
+
+def nn_match(feats1, feats2, source_points, load_size=(512, 512)):
+    """feats1 (B, C, h1, w1), feats2 (B, C, h2, w2), fp16 or fp32 with any strides; source_points (B, N, 2) or, for B = 1, (N, 2): (y, x) in
+    load-size coordinates -> (points2 int64 (B, N, 2) (y, x), scores fp32 (B, N)).
+    The reference's find_nn_source_correspondences for a load size (LH, LW): both maps F.interpolate'd to it (bilinear), the source pixels
+    idx = LW * round(clip(y, 0, LH - 1)) + round(clip(x, 0, LW - 1)) (np.round: half to even) gathered, both sides L2-normalised, argmax of q @ k^T
+    (lowest index of the maximum) and the cosine there.  Device tensors: gdf_op_nn_match, which builds neither load-size map; host tensors: that
+    torch chain in fp32."""
+    LH, LW = (int(load_size), int(load_size)) if isinstance(load_size, int) else (int(load_size[0]), int(load_size[1]))
+    if feats1.dim() != 4 or feats2.dim() != 4 or feats1.shape[0] != feats2.shape[0] or feats1.shape[1] != feats2.shape[1]:
+        raise ValueError("feats1 and feats2 are (B, C, h, w) tensors with the same B and C")
+    if LH < 1 or LW < 1:
+        raise ValueError("load_size >= 1")
+    B = feats1.shape[0]
+    pts = torch.as_tensor(source_points)
+    if pts.dim() == 2 and B == 1:
+        pts = pts[None]
+    if pts.dim() != 3 or pts.shape[0] != B or pts.shape[2] != 2 or pts.shape[1] < 1:
+        raise ValueError("source_points is (B, N, 2), or (N, 2) for B = 1, with N >= 1")
+    N = pts.shape[1]
+    if not feats2.is_cuda:
+        f1 = F.interpolate(feats1.float(), (LH, LW), mode="bilinear")
+        f2 = F.interpolate(feats2.float(), (LH, LW), mode="bilinear")
+        p = pts.detach().cpu().double().numpy()
+        idx = torch.from_numpy((LW * np.round(np.clip(p[..., 0], 0, LH - 1)) + np.round(np.clip(p[..., 1], 0, LW - 1))).astype(np.int64))
+        f1 = f1.flatten(2).permute(0, 2, 1)
+        f2 = f2.flatten(2).permute(0, 2, 1)
+        q = torch.gather(f1, 1, idx[..., None].expand(B, N, f1.shape[2]))
+        q = q / torch.linalg.norm(q, dim=-1)[:, :, None]
+        f2 = f2 / torch.linalg.norm(f2, dim=-1)[:, :, None]
+        score, best = torch.matmul(q, f2.permute(0, 2, 1)).max(dim=-1)
+        return torch.stack([best // LW, best % LW], dim=-1), score
+    dev = feats2.device
+    if feats1.device != dev:
+        raise ValueError("feats1 and feats2 are on the same device")
+    feats1, feats2 = (v if v.dtype in (torch.float16, torch.float32) else v.float() for v in (feats1, feats2))
+    with torch.cuda.device(dev):
+        pts = pts.to(device=dev, dtype=torch.float32).contiguous()
+        out = torch.empty(B, N, 2, dtype=torch.int64, device=dev)
+        score = torch.empty(B, N, dtype=torch.float32, device=dev)
+        if B == 0:
+            return out, score
+        L = _L()
+        nbytes = L.gdf_op_nn_match_workspace(B, N, feats2.shape[1], feats2.shape[2], feats2.shape[3])
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        s1, s2 = _agg_src(feats1), _agg_src(feats2)
+        native._check(L.gdf_op_nn_match(C.addressof(s1), C.addressof(s2), B, C.c_void_p(pts.data_ptr()), N, LH, LW, C.c_void_p(out.data_ptr()),
+                                        C.c_void_p(score.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes, _stream(dev)), "nn_match")
+    return out, score
+
+
+def find_nn_source_correspondences(img1_feats, img2_feats, source_points, output_size, load_size):
+    """The reference's function (correspondence/correspondence/correspondence_utils.py:113-138), same signature and return value:
+    source_points a numpy (N, 2) array of (y, x) in load-size coordinates -> (points1 = torch.from_numpy(source_points), points2 (N, 2) int64
+    (y, x) of batch element 0).  output_size is unused, as in the reference.  The points are clipped and rounded on the host in their own
+    precision (np.round), so a float64 annotation rounds as the reference rounds it."""
+    LH, LW = (int(load_size), int(load_size)) if isinstance(load_size, int) else (int(load_size[0]), int(load_size[1]))
+    p = np.asarray(source_points)
+    idx = np.stack([np.round(np.clip(p[:, 0], 0, LH - 1)), np.round(np.clip(p[:, 1], 0, LW - 1))], -1).astype(np.float32)
+    B = img1_feats.shape[0]
+    points2, _ = nn_match(img1_feats, img2_feats, torch.from_numpy(idx)[None].expand(B, -1, -1), (LH, LW))
+    return torch.from_numpy(source_points), points2[0]
 
 
 def avg_pool(feat, r):

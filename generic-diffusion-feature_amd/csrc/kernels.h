@@ -335,6 +335,13 @@ hipError_t launch_resize_concat(const half_t* s16, const float* s32, long sb, lo
 enum { AGG_MAX = 16 };
 struct AggSrc { const void* ptr; int f32; long sb, sc, sy, sx; int C, H, W, coff; };
 hipError_t launch_aggregate(const AggSrc* srcs, int n, int B, void* out, int out_f32, int Ctot, int OH, int OW, hipStream_t s);
+// find_nn_source_correspondences (corres.hip): for N source points of f1, the pixel of f2 upsampled (bilinear) to (LH, LW) whose vector has the highest
+// cosine similarity, without either upsampled map: out_yx (B, N, 2) int64 (y, x), out_score (B, N) fp32.  f1 / f2 are logical (B, C, H, W) tensors
+// (coff unused); points (B, N, 2) fp32 on the device; queries go in chunks of NN_MAXQ; workspace of nn_match_workspace bytes, 16-byte aligned.
+enum { NN_MAXQ = 24, NN_FINE_BLOCKS = 1024 };
+size_t nn_match_workspace(int B, int N, int C, int h2, int w2);
+hipError_t launch_nn_match(const AggSrc& f1, const AggSrc& f2, int B, const float* points, int N, int LH, int LW, long long* out_yx,
+                           float* out_score, void* workspace, hipStream_t s);
 // adaptive_avg_pool2d to (H/r, W/r) of a channels-last hook (B,C,H,W; strides sb, 1, sy, sx) -> (B, H/r, W/r, C) fp16: the r x r mean
 // where r divides H and W, ATen's longer windows [floor(o H / OH), ceil((o + 1) H / OH)) otherwise
 hipError_t launch_avg_pool(const half_t* src, long sb, long sy, long sx, int B, int C, int H, int W, int r, half_t* out, hipStream_t s);

@@ -481,6 +481,28 @@ int gdf_op_aggregate(const gdf_agg_src* srcs, int n, int B, void* out, int out_f
   }
   return GDF_OK;
 }
+size_t gdf_op_nn_match_workspace(int B, int N, int C, int h2, int w2) {
+  return nn_match_workspace(std::max(B, 1), std::max(N, 1), std::max(C, 1), std::max(h2, 1), std::max(w2, 1));
+}
+int gdf_op_nn_match(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const float* points, int N, int LH, int LW, long long* out_yx,
+                    float* out_score, void* workspace, size_t workspace_bytes, void* stream) {
+  auto bad = [](const char* msg) { set_error(std::string("gdf_op_nn_match: ") + msg); return GDF_ERR_ARG; };
+  auto big = [](const char* msg) { set_error(std::string("gdf_op_nn_match: ") + msg); return GDF_ERR_UNSUPPORTED; };
+  if (!f1 || !f2 || !points || !out_yx || !out_score || !workspace) return bad("null pointer");
+  if (!f1->ptr || !f2->ptr) return bad("null feature pointer");
+  if (B < 0 || N < 1 || LH < 1 || LW < 1) return bad("B >= 0, N, LH and LW >= 1");
+  if (f1->C < 1 || f1->H < 1 || f1->W < 1 || f2->C < 1 || f2->H < 1 || f2->W < 1) return bad("C, H and W >= 1");
+  if (f1->C != f2->C) return bad("the two maps differ in C");
+  if ((uintptr_t)workspace & 15) return bad("the workspace must be 16-byte aligned");
+  if (B > 65535) return big("B > 65535; split the batch");
+  if ((long long)LH * LW >= (1ll << 30)) return big("LH * LW >= 2^30 pixels (32-bit flat indices)");
+  if ((long long)std::max(B, 1) * f2->H * f2->W >= (1ll << 31)) return big("B * h2 * w2 >= 2^31; split the batch");
+  if (workspace_bytes < gdf_op_nn_match_workspace(B, N, f2->C, f2->H, f2->W)) return bad("workspace smaller than gdf_op_nn_match_workspace says");
+  if (B == 0) return GDF_OK;
+  const AggSrc a{f1->ptr, f1->f32, f1->sb, f1->sc, f1->sy, f1->sx, f1->C, f1->H, f1->W, 0};
+  const AggSrc b{f2->ptr, f2->f32, f2->sb, f2->sc, f2->sy, f2->sx, f2->C, f2->H, f2->W, 0};
+  return fin(launch_nn_match(a, b, B, points, N, LH, LW, out_yx, out_score, workspace, (hipStream_t)stream), "gdf_op_nn_match");
+}
 int gdf_op_avg_pool(const void* src, long sb, long sy, long sx, int B, int C, int H, int W, int r, void* out, void* stream) {
   return fin(launch_avg_pool((const half_t*)src, sb, sy, sx, B, C, H, W, r, (half_t*)out, (hipStream_t)stream), "avg_pool");
 }

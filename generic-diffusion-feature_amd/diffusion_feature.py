@@ -623,6 +623,13 @@ class FeatureExtractor(nn.Module):
             raise ValueError("aggregate: no features (call extract() first or pass feats=)")
         return aggregate(list(feats.values()) if isinstance(feats, dict) else list(feats), size, mode, dtype)
 
+    def correspond(self, feats1, feats2, source_points, load_size=(512, 512)):
+        """The evaluators' second step (reference correspondence/correspondence/correspondence_utils.py:113-138) on two aggregated maps, e.g. two
+        results of aggregate(): the nearest neighbour of every source point among the load-size target pixels -> (points2 int64 (B, N, 2) (y, x),
+        cosine scores fp32 (B, N)).  Device tensors: gdf_op_nn_match, neither load-size map is built (components/postproc.py nn_match)."""
+        from components.postproc import nn_match
+        return nn_match(feats1, feats2, source_points, load_size)
+
     def set_background_extraction(self, idxs):
         self.feature_store.store_idx = idxs
 

@@ -318,6 +318,31 @@ int gdf_op_resize_concat(const void* src, int src_f32, long sb, long sc, long sy
 typedef struct gdf_agg_src { const void* ptr; int f32; long sb, sc, sy, sx; int C, H, W, coff; } gdf_agg_src;
 int gdf_op_aggregate(const gdf_agg_src* srcs, int n, int B, void* out, int out_f32, int Ctot, int OH, int OW,
                      int mode /* 0 nearest, 1 bilinear */, void* stream);
+/* The evaluators' second step on two aggregated maps (correspondence/correspondence/correspondence_utils.py:113-138,
+ * find_nn_source_correspondences, called per image pair from correspondence/task-corres.py:110): both maps F.interpolate'd to the load size
+ * (LH, LW) (bilinear), the N source points gathered from the first, both sides L2-normalised, sims = q @ k^T, argmax over the LH * LW target
+ * pixels — computed WITHOUT either load-size map (csrc/corres.hip): one pass over the coarse target yields <q_n, T> and five
+ * neighbour products per coarse pixel; a pass over the fine grid blends them, divides by the Gram-form norm and reduces.
+ *   f1, f2     logical (B, C, H, W) tensors, fp16 (f32 = 0) or fp32 independently, with element strides sb/sc/sy/sx, read only; the two C must
+ *              agree, the grids need not; `coff` is ignored.  A target with sx == 1 (NCHW, what gdf_op_aggregate writes) is read with lanes along
+ *              x; one with sc == 1, C a multiple of 8 (fp32: 4) and 16-byte aligned pixels (a channels-last hook) with 16-byte loads along C;
+ *              any other strides are correct, not fast.
+ *   points     device, (B, N, 2) fp32, (y, x) in load-size coordinates.  Source index: y = round_half_even(clip(y, 0, LH - 1)), x likewise with
+ *              LW (points_to_idxs, np.round); the query is the bilinear sample of f1 there — its four taps — normalised in fp32.
+ *   upsampling ATen's upsample_bilinear2d, align_corners = False, with the fp32 coordinate arithmetic of gdf_op_aggregate mode 1 above; where the
+ *              second tap clamps onto the first (i1 == i0) its weight is taken as 0.
+ *   score      s[n, p] = <q_n, v_p> / ||v_p|| in fp32 throughout.  out_yx (B, N, 2) int64 = (p* / LW, p* % LW) of the LOWEST flat index p* of
+ *              maximal computed score (argmax's rule), out_score (B, N) fp32 the score there.
+ *   zero norms a target pixel whose computed norm is not positive never wins; a query of norm 0 (or one no pixel answers) returns index 0 and a
+ *              NaN score — the reference propagates NaN here.
+ *   workspace  gdf_op_nn_match_workspace(B, N, C, h2, w2) bytes (h2, w2: the grid of f2), 16-byte aligned, caller-owned, contents undefined
+ *              before and after.  Any N: queries are processed 24 at a time.
+ * Stream-ordered, nothing read back, no allocation; the same inputs give the same bits on any stream.  A null pointer, C, H, W, LH, LW or N
+ * below 1, differing C, B < 0, a misaligned or too small workspace: GDF_ERR_ARG before any launch.  B > 65535, LH * LW >= 2^30 or
+ * B * h2 * w2 >= 2^31: GDF_ERR_UNSUPPORTED.  B == 0 is a successful no-op. */
+size_t gdf_op_nn_match_workspace(int B, int N, int C, int h2, int w2);
+int gdf_op_nn_match(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const float* points /* device, (B, N, 2) */, int N, int LH, int LW,
+                    long long* out_yx /* (B, N, 2) */, float* out_score /* (B, N) */, void* workspace, size_t workspace_bytes, void* stream);
 /* `feature_resize` (components/feature_extractor.py:51-53): adaptive_avg_pool2d to (OH, OW) = (H / r, W / r) (integer division) of a
  * channels-last hook (strides sb, 1, sy, sx; C % 8 == 0) -> (B, OH, OW, C) fp16, fp32 accumulation.  Output row o averages source rows
  * [floor(o H / OH), ceil((o + 1) H / OH)), columns likewise: the r x r window where r divides the size, otherwise longer windows that may
