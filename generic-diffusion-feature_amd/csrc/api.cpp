@@ -8,19 +8,47 @@ using namespace gdf;
 struct gdf_model { Model* m; };
 struct gdf_plan { Plan p; gdf_model* owner; };
 
+// Every *_create: check the arguments, need a device, create, wrap.  `create()` returns the Model, or nullptr with the error set.
+template <typename Create>
+static int create_model(bool args_ok, gdf_model** out, Create create, bool need_device = true) {
+  if (!args_ok) { set_error("null argument"); return GDF_ERR_ARG; }
+  int ndev = 0;
+  if (need_device && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) { set_error("no HIP device: libgdf has no CPU fallback"); return GDF_ERR_HIP; }
+  Model* m = create();
+  if (!m) return GDF_ERR_ARG;
+  *out = new gdf_model{m};
+  return GDF_OK;
+}
+
+// Every *_plan_create, behind its argument checks: default options, new plan, build, delete on failure.  `build(plan, options)` returns the status.
+template <typename Build>
+static int create_plan(gdf_model* m, const gdf_plan_opts* opts, gdf_plan** out, Build build) {
+  gdf_plan_opts o{};
+  o.stream_fp32 = 1;
+  if (opts) o = *opts;
+  gdf_plan* p = new gdf_plan();
+  p->owner = m;
+  p->p.model = m->m;
+  const int rc = build(p->p, o);
+  if (rc != GDF_OK) { delete p; return rc; }
+  *out = p;
+  return GDF_OK;
+}
+
+// Every *_plan_profile: -1 on bad arguments or a failed forward (`run()`), else the number of ops of the plan
+template <typename Run>
+static int profile_plan(const gdf_plan* p, const float* ms, Run run) {
+  if (!p || !ms) { set_error("null argument"); return -1; }
+  return run() != GDF_OK ? -1 : (int)p->p.ops.size();
+}
+
 extern "C" {
 
 const char* gdf_last_error(void) { return last_error(); }
 int gdf_abi_version(void) { return 1; }
 
 int gdf_model_create(const gdf_arch_desc* arch, gdf_model** out) {
-  if (!arch || !out) { set_error("null argument"); return GDF_ERR_ARG; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device: libgdf has no CPU fallback"); return GDF_ERR_HIP; }
-  Model* m = model_create(*arch);
-  if (!m) return GDF_ERR_ARG;
-  *out = new gdf_model{m};
-  return GDF_OK;
+  return create_model(arch && out, out, [&] { return model_create(*arch); });
 }
 void gdf_model_destroy(gdf_model* m) { if (m) { model_destroy(m->m); delete m; } }
 int gdf_model_param_count(const gdf_model* m) { return m ? (int)m->m->params.size() : 0; }
@@ -60,16 +88,7 @@ int gdf_plan_create(gdf_model* m, int batch, int lat_h, int lat_w, int n_ctx, co
   if (!m || !out || (n_hooks > 0 && !hook_ids)) { set_error("null argument"); return GDF_ERR_ARG; }
   if (m->m->kind != 0) { set_error("gdf_plan_create on a Flux model: use gdf_flux_plan_create"); return GDF_ERR_ARG; }
   if (m->m->controlnet) { set_error("gdf_plan_create on a ControlNet model: use gdf_controlnet_plan_create"); return GDF_ERR_ARG; }
-  gdf_plan_opts o{};
-  o.stream_fp32 = 1;
-  if (opts) o = *opts;
-  gdf_plan* p = new gdf_plan();
-  p->owner = m;
-  p->p.model = m->m;
-  const int rc = plan_build(*m->m, p->p, batch, lat_h, lat_w, n_ctx, hook_ids, n_hooks, o, false);
-  if (rc != GDF_OK) { delete p; return rc; }
-  *out = p;
-  return GDF_OK;
+  return create_plan(m, opts, out, [&](Plan& P, gdf_plan_opts& o) { return plan_build(*m->m, P, batch, lat_h, lat_w, n_ctx, hook_ids, n_hooks, o, false); });
 }
 void gdf_plan_destroy(gdf_plan* p) { delete p; }
 size_t gdf_plan_workspace_bytes(const gdf_plan* p) { return p ? p->p.ws_bytes : 0; }
@@ -90,27 +109,12 @@ int gdf_plan_hook_copied(const gdf_plan* p, int i) {
 
 // ---- PixArt DiT front end (include/gdf_pixart.h) ----
 int gdf_pixart_model_create(const gdf_pixart_desc* desc, gdf_model** out) {
-  if (!desc || !out) { set_error("null argument"); return GDF_ERR_ARG; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device: libgdf has no CPU fallback"); return GDF_ERR_HIP; }
-  Model* m = pixart_model_create(*desc);
-  if (!m) return GDF_ERR_ARG;
-  *out = new gdf_model{m};
-  return GDF_OK;
+  return create_model(desc && out, out, [&] { return pixart_model_create(*desc); });
 }
 int gdf_pixart_plan_create(gdf_model* m, int batch, int lat_h, int lat_w, int n_txt, const char* const* hook_ids, int n_hooks,
                            const gdf_plan_opts* opts, gdf_plan** out) {
   if (!m || !out || (n_hooks > 0 && !hook_ids)) { set_error("null argument"); return GDF_ERR_ARG; }
-  gdf_plan_opts o{};
-  o.stream_fp32 = 1;
-  if (opts) o = *opts;
-  gdf_plan* p = new gdf_plan();
-  p->owner = m;
-  p->p.model = m->m;
-  const int rc = pixart_plan_build(*m->m, p->p, batch, lat_h, lat_w, n_txt, hook_ids, n_hooks, o, false);
-  if (rc != GDF_OK) { delete p; return rc; }
-  *out = p;
-  return GDF_OK;
+  return create_plan(m, opts, out, [&](Plan& P, gdf_plan_opts& o) { return pixart_plan_build(*m->m, P, batch, lat_h, lat_w, n_txt, hook_ids, n_hooks, o, false); });
 }
 int gdf_pixart_forward(gdf_plan* p, const void* latents, const float* timestep, const void* encoder_hidden_states,
                        const int* text_lens, void* const* hook_out, void* out, void* workspace, void* stream) {
@@ -121,32 +125,19 @@ int gdf_pixart_forward(gdf_plan* p, const void* latents, const float* timestep, 
 int gdf_pixart_plan_profile(gdf_plan* p, const void* latents, const float* timestep, const void* encoder_hidden_states,
                             const int* text_lens, void* const* hook_out, void* out, void* workspace, void* stream, float* ms,
                             const char** names, double* flops, int cap) {
-  if (!p || !ms) { set_error("null argument"); return -1; }
-  const int rc = pixart_forward(p->p, *p->p.model, latents, timestep, encoder_hidden_states, text_lens, hook_out, out, workspace,
-                                (hipStream_t)stream, ms, names, flops, cap);
-  if (rc != GDF_OK) return -1;
-  return (int)p->p.ops.size();
+  return profile_plan(p, ms, [&] {
+    return pixart_forward(p->p, *p->p.model, latents, timestep, encoder_hidden_states, text_lens, hook_out, out, workspace, (hipStream_t)stream,
+                          ms, names, flops, cap);
+  });
 }
 
 // ---- VAE encoder front end (include/gdf_vae.h) ----
 int gdf_vae_model_create(const gdf_vae_desc* desc, gdf_model** out) {
-  if (!desc || !out) { set_error("null argument"); return GDF_ERR_ARG; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device: libgdf has no CPU fallback"); return GDF_ERR_HIP; }
-  Model* m = vae_model_create(*desc);
-  if (!m) return GDF_ERR_ARG;
-  *out = new gdf_model{m};
-  return GDF_OK;
+  return create_model(desc && out, out, [&] { return vae_model_create(*desc); });
 }
 int gdf_vae_plan_create(gdf_model* m, int batch, int img_h, int img_w, gdf_plan** out) {
   if (!m || !out) { set_error("null argument"); return GDF_ERR_ARG; }
-  gdf_plan* p = new gdf_plan();
-  p->owner = m;
-  p->p.model = m->m;
-  const int rc = vae_plan_build(*m->m, p->p, batch, img_h, img_w, false);
-  if (rc != GDF_OK) { delete p; return rc; }
-  *out = p;
-  return GDF_OK;
+  return create_plan(m, nullptr, out, [&](Plan& P, gdf_plan_opts&) { return vae_plan_build(*m->m, P, batch, img_h, img_w, false); });   // (sets its own options)
 }
 int gdf_vae_encode(gdf_plan* p, const void* image, const void* eps, const void* noise, float scaling_factor, float noise_a,
                    float noise_b, float input_scale, void* latents_out, void* workspace, void* stream) {
@@ -170,32 +161,19 @@ int gdf_vae_encode_packed(gdf_plan* p, const void* image, const void* eps, const
 int gdf_vae_plan_profile(gdf_plan* p, const void* image, const void* eps, const void* noise, float scaling_factor, float noise_a,
                          float noise_b, float input_scale, void* latents_out, void* workspace, void* stream, float* ms,
                          const char** names, double* flops, int cap) {
-  if (!p || !ms) { set_error("null argument"); return -1; }
-  const int rc = vae_encode(p->p, *p->p.model, image, eps, noise, scaling_factor, noise_a, noise_b, input_scale, latents_out,
-                            workspace, (hipStream_t)stream, ms, names, flops, cap);
-  if (rc != GDF_OK) return -1;
-  return (int)p->p.ops.size();
+  return profile_plan(p, ms, [&] {
+    return vae_encode(p->p, *p->p.model, image, eps, noise, scaling_factor, noise_a, noise_b, input_scale, latents_out, workspace,
+                      (hipStream_t)stream, ms, names, flops, cap);
+  });
 }
 
 // ---- VAE decoder: the optional `vae-out` feature (include/gdf_vae.h) ----
 int gdf_vae_decoder_create(const gdf_vae_desc* desc, gdf_model** out) {
-  if (!desc || !out) { set_error("null argument"); return GDF_ERR_ARG; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device: libgdf has no CPU fallback"); return GDF_ERR_HIP; }
-  Model* m = vae_decoder_create(*desc);
-  if (!m) return GDF_ERR_ARG;
-  *out = new gdf_model{m};
-  return GDF_OK;
+  return create_model(desc && out, out, [&] { return vae_decoder_create(*desc); });
 }
 int gdf_vae_decode_plan_create(gdf_model* m, int batch, int lat_h, int lat_w, gdf_plan** out) {
   if (!m || !out) { set_error("null argument"); return GDF_ERR_ARG; }
-  gdf_plan* p = new gdf_plan();
-  p->owner = m;
-  p->p.model = m->m;
-  const int rc = vae_dec_plan_build(*m->m, p->p, batch, lat_h, lat_w, false);
-  if (rc != GDF_OK) { delete p; return rc; }
-  *out = p;
-  return GDF_OK;
+  return create_plan(m, nullptr, out, [&](Plan& P, gdf_plan_opts&) { return vae_dec_plan_build(*m->m, P, batch, lat_h, lat_w, false); });
 }
 int gdf_vae_decode(gdf_plan* p, const void* latents, const void* noise_pred, float step_c_sample, float step_c_eps, float inv_scaling,
                    void* image_out, void* workspace, void* stream) {
@@ -206,36 +184,20 @@ int gdf_vae_decode(gdf_plan* p, const void* latents, const void* noise_pred, flo
 int gdf_vae_decode_plan_profile(gdf_plan* p, const void* latents, const void* noise_pred, float step_c_sample, float step_c_eps,
                                 float inv_scaling, void* image_out, void* workspace, void* stream, float* ms, const char** names,
                                 double* flops, int cap) {
-  if (!p || !ms) { set_error("null argument"); return -1; }
-  const int rc = vae_decode(p->p, *p->p.model, latents, noise_pred, step_c_sample, step_c_eps, inv_scaling, image_out, workspace,
-                            (hipStream_t)stream, ms, names, flops, cap);
-  if (rc != GDF_OK) return -1;
-  return (int)p->p.ops.size();
+  return profile_plan(p, ms, [&] {
+    return vae_decode(p->p, *p->p.model, latents, noise_pred, step_c_sample, step_c_eps, inv_scaling, image_out, workspace, (hipStream_t)stream,
+                      ms, names, flops, cap);
+  });
 }
 
 // ---- MMDiT / Flux front end (include/gdf_flux.h) ----
 int gdf_flux_model_create(const gdf_flux_desc* desc, gdf_model** out) {
-  if (!desc || !out) { set_error("null argument"); return GDF_ERR_ARG; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device: libgdf has no CPU fallback"); return GDF_ERR_HIP; }
-  Model* m = flux_model_create(*desc);
-  if (!m) return GDF_ERR_ARG;
-  *out = new gdf_model{m};
-  return GDF_OK;
+  return create_model(desc && out, out, [&] { return flux_model_create(*desc); });
 }
 int gdf_flux_plan_create(gdf_model* m, int batch, int img_h, int img_w, int n_txt, const char* const* hook_ids, int n_hooks,
                          const gdf_plan_opts* opts, gdf_plan** out) {
   if (!m || !out || (n_hooks > 0 && !hook_ids)) { set_error("null argument"); return GDF_ERR_ARG; }
-  gdf_plan_opts o{};
-  o.stream_fp32 = 1;
-  if (opts) o = *opts;
-  gdf_plan* p = new gdf_plan();
-  p->owner = m;
-  p->p.model = m->m;
-  const int rc = flux_plan_build(*m->m, p->p, batch, img_h, img_w, n_txt, hook_ids, n_hooks, o, false);
-  if (rc != GDF_OK) { delete p; return rc; }
-  *out = p;
-  return GDF_OK;
+  return create_plan(m, opts, out, [&](Plan& P, gdf_plan_opts& o) { return flux_plan_build(*m->m, P, batch, img_h, img_w, n_txt, hook_ids, n_hooks, o, false); });
 }
 int gdf_flux_forward(gdf_plan* p, const void* hidden_states, const void* encoder_hidden_states, const void* pooled_projections,
                      const float* timestep, const float* guidance, const float* img_ids, const float* txt_ids,
@@ -248,11 +210,10 @@ int gdf_flux_plan_profile(gdf_plan* p, const void* hidden_states, const void* en
                           const void* pooled_projections, const float* timestep, const float* guidance, const float* img_ids,
                           const float* txt_ids, void* const* hook_out, void* out, void* workspace, void* stream, float* ms,
                           const char** names, double* flops, int cap) {
-  if (!p || !ms) { set_error("null argument"); return -1; }
-  const int rc = flux_forward(p->p, *p->p.model, hidden_states, encoder_hidden_states, pooled_projections, timestep, guidance,
-                              img_ids, txt_ids, hook_out, out, workspace, (hipStream_t)stream, ms, names, flops, cap);
-  if (rc != GDF_OK) return -1;
-  return (int)p->p.ops.size();
+  return profile_plan(p, ms, [&] {
+    return flux_forward(p->p, *p->p.model, hidden_states, encoder_hidden_states, pooled_projections, timestep, guidance, img_ids, txt_ids,
+                        hook_out, out, workspace, (hipStream_t)stream, ms, names, flops, cap);
+  });
 }
 
 int gdf_forward(gdf_plan* p, const void* latents, const float* timesteps, const void* ctx, const void* add_text_embeds,
@@ -272,36 +233,20 @@ int gdf_forward_res(gdf_plan* p, const void* latents, const float* timesteps, co
 
 // ---- ControlNet model (include/gdf_control.h) ----
 int gdf_controlnet_create(const gdf_arch_desc* arch, const int cond_channels[4], int conditioning_channels, gdf_model** out) {
-  if (!arch || !cond_channels || !out) { set_error("null argument"); return GDF_ERR_ARG; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device: libgdf has no CPU fallback"); return GDF_ERR_HIP; }
-  Model* m = controlnet_create(*arch, cond_channels, conditioning_channels);
-  if (!m) return GDF_ERR_ARG;
-  *out = new gdf_model{m};
-  return GDF_OK;
+  return create_model(arch && cond_channels && out, out, [&] { return controlnet_create(*arch, cond_channels, conditioning_channels); });
 }
 int gdf_controlnet_layout(const gdf_arch_desc* arch, const int cond_channels[4], int conditioning_channels, gdf_model** out) {
-  if (!arch || !cond_channels || !out) { set_error("null argument"); return GDF_ERR_ARG; }
-  Model* m = controlnet_create(*arch, cond_channels, conditioning_channels, /*layout_only=*/true);
-  if (!m) return GDF_ERR_ARG;
-  *out = new gdf_model{m};
-  return GDF_OK;
+  return create_model(arch && cond_channels && out, out, [&] { return controlnet_create(*arch, cond_channels, conditioning_channels, /*layout_only=*/true); },
+                      /*need_device=*/false);      // the parameter table alone: no device is touched
 }
 int gdf_controlnet_plan_create(gdf_model* m, int batch, int lat_h, int lat_w, int n_ctx, const gdf_plan_opts* opts, gdf_plan** out) {
   if (!m || !out) { set_error("null argument"); return GDF_ERR_ARG; }
   if (m->m->kind != 0 || !m->m->controlnet) { set_error("gdf_controlnet_plan_create needs a model of gdf_controlnet_create"); return GDF_ERR_ARG; }
   if (!m->m->weights) { set_error("this model is a parameter table without weights (gdf_controlnet_layout)"); return GDF_ERR_STATE; }
-  gdf_plan_opts o{};
-  o.stream_fp32 = 1;
-  if (opts) o = *opts;
-  o.early_exit = 0; o.reserved[3] = 0;        // no hooks to stop behind, and the block is written, not read
-  gdf_plan* p = new gdf_plan();
-  p->owner = m;
-  p->p.model = m->m;
-  const int rc = plan_build(*m->m, p->p, batch, lat_h, lat_w, n_ctx, nullptr, 0, o, false);
-  if (rc != GDF_OK) { delete p; return rc; }
-  *out = p;
-  return GDF_OK;
+  return create_plan(m, opts, out, [&](Plan& P, gdf_plan_opts& o) {
+    o.early_exit = 0; o.reserved[3] = 0;        // no hooks to stop behind, and the block is written, not read
+    return plan_build(*m->m, P, batch, lat_h, lat_w, n_ctx, nullptr, 0, o, false);
+  });
 }
 int gdf_controlnet_forward(gdf_plan* p, const void* latents, const float* timesteps, const void* ctx, const void* add_text_embeds,
                            const float* add_time_ids, const void* cond_image, int cond_dtype, void* residual_block_out, void* workspace,
@@ -360,11 +305,10 @@ int gdf_sample(gdf_plan* plain, gdf_plan* hooked, float* latents_f32, int n_rows
 int gdf_plan_profile(gdf_plan* p, const void* latents, const float* timesteps, const void* ctx,
                      const void* add_text_embeds, const float* add_time_ids, void* const* hook_out, void* noise_pred,
                      void* workspace, void* stream, float* ms, const char** names, double* flops, int cap) {
-  if (!p || !ms) { set_error("null argument"); return -1; }
-  const int rc = plan_forward(p->p, *p->p.model, latents, timesteps, ctx, add_text_embeds, add_time_ids, hook_out,
-                              noise_pred, workspace, (hipStream_t)stream, ms, names, flops, cap);
-  if (rc != GDF_OK) return -1;
-  return (int)p->p.ops.size();
+  return profile_plan(p, ms, [&] {
+    return plan_forward(p->p, *p->p.model, latents, timesteps, ctx, add_text_embeds, add_time_ids, hook_out, noise_pred, workspace,
+                        (hipStream_t)stream, ms, names, flops, cap);
+  });
 }
 
 const char* gdf_plan_op_kernel(const gdf_plan* p, int i) {

@@ -457,8 +457,7 @@ Model* flux_model_create(const gdf_flux_desc& d) {
     m->f8_off = a; m->sc_off = a + a / 2;
     m->weight_bytes = a + a / 2 + a / 16 + 4096;
   }
-  { CaptureExclusive guard; const hipError_t me = hipMalloc(&m->weights, m->weight_bytes); if (me != hipSuccess) { set_error(std::string("hipMalloc(weights, ") + std::to_string(m->weight_bytes) + " bytes) failed: " + hipGetErrorString(me)); (void)hipGetLastError(); delete m; return nullptr; } }
-  (void)hipMemset(m->weights, 0, m->weight_bytes);
+  if (!alloc_weight_arena(m)) return nullptr;
   PlanOpts o{}; o.stream_fp32 = 1;
   Plan dry;
   flux_plan_build(*m, dry, 1, 4, 4, 8, nullptr, 0, o, /*dry=*/true);

@@ -1,5 +1,5 @@
 // Kernel launches of libgdf.so go through gdf::launch_kernel (the hipLaunchKernelGGL spelling is kept at the 56 launch sites and redirected
-// here).  Normally that is hipLaunchKernel.  While the calling THREAD is recording a plan (model.cpp run_ops_graph) the same call appends a
+// here).  Normally that is hipLaunchKernel.  While the calling THREAD is recording a plan (plan_exec.cpp run_ops_graph) the same call appends a
 // kernel node to that plan's hipGraph instead — the graph is built with the explicit graph API, not by stream capture (round 6).
 // Why: a stream capture is a device-wide state on this runtime.  While one thread's plan stream was capturing, another thread's
 // hipFree / hipMalloc / hipGraphExecDestroy (a model being garbage-collected), a second capture, or a plain torch.cuda.synchronize()

@@ -1,5 +1,6 @@
 // Host side of libgdf.so: architecture walk, weight arena + re-layout, static plan builder
-// (op program + workspace arena + hook table) and the forward executor.
+// (op program + workspace arena + hook table) and the UNet front ends (forward, ControlNet, trajectory, sampler).
+// The executor that runs an op program is plan_exec.cpp.
 //
 // The op program restates, for the reference's single-timestep path, the orchestration of
 //   UNet2DConditionModel.forward        /root/reference/feature/diffusers/models/unet/unet_2d_condition.py:1040-1319
@@ -19,7 +20,6 @@
 // pre-allocated concat buffer.  The residual stream additionally keeps an fp32 master copy
 // (stream_fp32) that only the residual adds in GEMM epilogues read and write.
 #include "builder.h"
-#include <shared_mutex>
 
 namespace gdf {
 
@@ -216,15 +216,7 @@ static Model* model_create_impl(const GdfArch& arch, const int* cond, int cond_i
   ModelBuilder b(*m);
   b.build(cond, cond_in);
   if (layout_only) return m;                   // the parameter table alone (gdf_controlnet_layout): no device is touched, weights stays null
-  {
-    CaptureExclusive g;
-    const hipError_t me = hipMalloc(&m->weights, m->weight_bytes);
-    if (me != hipSuccess) {
-      set_error(std::string("hipMalloc(weights, ") + std::to_string(m->weight_bytes) + " bytes) failed: " + hipGetErrorString(me)); (void)hipGetLastError();
-      delete m; return nullptr;
-    }
-    hipMemset(m->weights, 0, m->weight_bytes);
-  }
+  if (!alloc_weight_arena(m)) return nullptr;
   if (m->controlnet) return m;                 // a ControlNet registers no hooks
   // hook ids (dry plan walk)
   PlanOpts o{}; o.stream_fp32 = 1;
@@ -234,12 +226,16 @@ static Model* model_create_impl(const GdfArch& arch, const int* cond, int cond_i
   return m;
 }
 
-static std::shared_mutex& capture_mx() { static std::shared_mutex mx; return mx; }
-static bool capture_guard_on() { static const bool on = [] { const char* e = getenv("GDF_CAPTURE_GUARD"); return !e || atoi(e) != 0; }(); return on; }   // 0: diagnostics (tests/test_gpu_dist.py reproduces the invalidation)
-CaptureShared::CaptureShared() { if (capture_guard_on()) capture_mx().lock_shared(); }
-CaptureShared::~CaptureShared() { if (capture_guard_on()) capture_mx().unlock_shared(); }
-CaptureExclusive::CaptureExclusive() { if (capture_guard_on()) capture_mx().lock(); }
-CaptureExclusive::~CaptureExclusive() { if (capture_guard_on()) capture_mx().unlock(); }
+bool alloc_weight_arena(Model* m) {
+  CaptureExclusive g;
+  const hipError_t me = hipMalloc(&m->weights, m->weight_bytes);
+  if (me != hipSuccess) {
+    set_error(std::string("hipMalloc(weights, ") + std::to_string(m->weight_bytes) + " bytes) failed: " + hipGetErrorString(me)); (void)hipGetLastError();
+    delete m; return false;
+  }
+  hipMemset(m->weights, 0, m->weight_bytes);
+  return true;
+}
 
 void model_destroy(Model* m) {
   if (!m) return;
@@ -554,7 +550,7 @@ struct B : PlanBuilder {   // UNet op program
       const int cic = m.cond_image_channels;
       op("cond_pack_image", 0, [=](const Bind& b, hipStream_t s) {
         if (!b.base[BUF_COND]) return hipErrorInvalidValue;
-        return launch_cond_pack_image(b.base[BUF_COND], b.f[1] != 0.f ? 1 : 0, Bq, cic, ih, iw, (half_t*)b.ws(src), s);
+        return launch_cond_pack_image(b.base[BUF_COND], b.f[F_CONTROL_COND_F32] != 0.f ? 1 : 0, Bq, cic, ih, iw, (half_t*)b.ws(src), s);
       }, "cond_pack_image_kernel");
       for (const CondW& w : m.cond_embed) {
         const int oh = ih / w.stride, ow = iw / w.stride;
@@ -846,49 +842,6 @@ const char* kernel_label(const char* n) {
   return n;
 }
 
-Plan::~Plan() {
-  CaptureExclusive guard;
-  for (auto& v : ev) for (auto e : v) hipEventDestroy(e);
-  for (auto& g : graphs) { if (g.exec) hipGraphExecDestroy(g.exec); if (g.graph) hipGraphDestroy(g.graph); }
-}
-
-static void timing_collect(Plan& P, int set) {
-  if (!P.ev_used[set]) return;
-  auto& v = P.ev[set];
-  size_t k = 0;
-  long nlab = 0;
-  for (auto& op : P.ops) {
-    if (op.label != P.timing_label) continue;
-    if ((nlab++ % P.timing_stride) != 0) continue;
-    float ms = 0.f;
-    hipEventSynchronize(v[k + 1]);
-    if (hipEventElapsedTime(&ms, v[k], v[k + 1]) == hipSuccess) { P.t_ms += ms; P.t_flops += op.flops; P.t_launches++; }
-    k += 2;
-  }
-  P.ev_used[set] = false;
-}
-
-int plan_set_timing(Plan& P, const char* label) {
-  for (int s = 0; s < Plan::EV_RING; ++s) timing_collect(P, s);
-  P.timing_label = -1; P.t_ms = 0; P.t_flops = 0; P.t_launches = 0;
-  if (!label) return GDF_OK;
-  for (size_t i = 0; i < P.labels.size(); ++i) if (P.labels[i] == label) P.timing_label = (int)i;
-  if (P.timing_label < 0) { set_error(std::string("no op with kernel label ") + label); return GDF_ERR_ARG; }
-  size_t n = 0;
-  for (auto& op : P.ops) n += op.label == P.timing_label;          // (an upper bound with a stride > 1)
-  for (int s = 0; s < Plan::EV_RING; ++s)
-    while (P.ev[s].size() < 2 * n) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { set_error("hipEventCreate"); return GDF_ERR_HIP; } P.ev[s].push_back(e); }
-  return GDF_OK;
-}
-
-int plan_read_timing(Plan& P, double* ms, long* launches, double* flops) {
-  for (int s = 0; s < Plan::EV_RING; ++s) timing_collect(P, s);
-  if (ms) *ms = P.t_ms;
-  if (launches) *launches = P.t_launches;
-  if (flops) *flops = P.t_flops;
-  return GDF_OK;
-}
-
 int plan_forward(Plan& P, const Model& m, const void* lat, const float* t, const void* ctx, const void* txt,
                  const float* tid, void* const* hook_out, void* noise, void* ws, hipStream_t s, float* ms,
                  const char** names, double* flops, int cap, const void* residuals) {
@@ -923,29 +876,8 @@ int controlnet_forward(Plan& P, const Model& m, const void* lat, const float* t,
   b.base[BUF_WS] = (char*)ws; b.base[BUF_WT] = (char*)m.weights; b.base[BUF_LAT] = (char*)lat; b.base[BUF_T] = (char*)t;
   b.base[BUF_CTX] = (char*)ctx; b.base[BUF_TXT] = (char*)txt; b.base[BUF_TID] = (char*)tid;
   b.base[BUF_COND] = (char*)cond; b.base[BUF_RES_OUT] = (char*)res_out;
-  b.f[1] = cond_dtype == GDF_F32 ? 1.f : 0.f;        // part of the graph key: the pack kernel reads the image by this type
+  b.f[F_CONTROL_COND_F32] = cond_dtype == GDF_F32 ? 1.f : 0.f;   // part of the graph key: the pack kernel reads the image by this type
   return plan_run(P, b, s, nullptr, nullptr, nullptr, 0);
-}
-
-// ---- explicit graph construction (launch.h): the recorder of the calling thread, kernel / event-record nodes in one chain ----
-GraphRecorder*& thread_recorder() { static thread_local GraphRecorder* r = nullptr; return r; }
-static hipError_t chain(GraphRecorder& r, hipGraphNode_t node) { r.last = node; ++r.nodes; return hipSuccess; }
-hipError_t record_kernel_node(GraphRecorder& r, const void* fn, dim3 grid, dim3 block, void** args, unsigned smem) {
-  hipKernelNodeParams kp{};
-  kp.func = const_cast<void*>(fn); kp.gridDim = grid; kp.blockDim = block; kp.sharedMemBytes = smem; kp.kernelParams = args; kp.extra = nullptr;
-  hipGraphNode_t node = nullptr;
-  const hipError_t e = hipGraphAddKernelNode(&node, r.graph, r.last ? &r.last : nullptr, r.last ? 1 : 0, &kp);     // (the argument VALUES are copied here)
-  return e != hipSuccess ? e : chain(r, node);
-}
-// An event-record NODE at the current end of the chain (fires at every replay): the timed replays of bench.py (gdf_plan_set_timing)
-hipError_t record_event_node(GraphRecorder& r, hipEvent_t ev) {
-  hipGraphNode_t node = nullptr;
-  const hipError_t e = hipGraphAddEventRecordNode(&node, r.graph, r.last ? &r.last : nullptr, r.last ? 1 : 0, ev);
-  return e != hipSuccess ? e : chain(r, node);
-}
-static hipError_t record_in_capture(hipEvent_t ev, hipStream_t) {
-  GraphRecorder* r = thread_recorder();
-  return r ? record_event_node(*r, ev) : hipErrorInvalidValue;
 }
 
 // gdf_sample's state block (include/gdf.h), every part 256-byte aligned: the forwards' fp16 input (batch, 4, H, W), their timestep buffer
@@ -968,11 +900,12 @@ size_t sample_state_bytes(int batch, int H, int W, int n_rows) {
   return sample_layout(batch, H, W, n_rows).end;
 }
 
-// Trajectory calls (plan_trajectory binds the fp32 master): the scheduler update follows the op program — in the same graph when one is recorded.
+// The tail of the op loop (plan_exec.cpp run_ops).  Trajectory calls (plan_trajectory binds the fp32 master): the scheduler update follows the
+// op program — in the same graph when one is recorded.
 // Plans built with hooks never get here with a master bound, and their op program is untouched.
-static int traj_step(const Plan& P, const Bind& b, hipStream_t s) {
-  if (b.base[BUF_SAMPLE] && b.base[BUF_X32] && P.model->kind == 0) { // gdf_sample: either UNet plan, the state is the caller's block; f[0] = guided (part of the graph key)
-    const bool guided = b.f[0] != 0.f;
+int unet_scheduler_step(const Plan& P, const Bind& b, hipStream_t s) {
+  if (b.base[BUF_SAMPLE] && b.base[BUF_X32] && P.model->kind == 0) { // gdf_sample: either UNet plan, the state is the caller's block
+    const bool guided = b.f[F_SAMPLE_GUIDED] != 0.f;
     const SampleLayout L = sample_layout(P.batch, P.H, P.W, 0);
     char* st = b.base[BUF_SAMPLE];
     const hipError_t e = launch_guided_step((float*)b.base[BUF_X32], (const half_t*)b.base[BUF_NOISE], (float*)(st + L.hist), (half_t*)b.base[BUF_LAT],
@@ -985,151 +918,6 @@ static int traj_step(const Plan& P, const Bind& b, hipStream_t s) {
                                           (float*)b.base[BUF_T], (int*)b.ws(traj_layout(P).steps), P.batch, P.H, P.W, 0, s);
   if (e != hipSuccess) { set_error(std::string("op 'latent_step' failed: ") + hipGetErrorString(e)); return GDF_ERR_HIP; }
   return GDF_OK;
-}
-
-// evset >= 0: record the timing events of set `evset` around every op of the timed label; `external` = while this thread records the plan's
-// graph (event-record nodes that fire at every replay)
-static int run_ops_eager(Plan& P, const Bind& b, hipStream_t s, int evset = -1, bool external = false) {
-  size_t evk = 0;
-  long nlab = 0;
-  for (auto& op : P.ops) {
-    const bool timed = evset >= 0 && op.label == P.timing_label && (nlab++ % P.timing_stride) == 0;
-    if (timed) {
-      const hipError_t ee = external ? record_in_capture(P.ev[evset][evk], s) : hipEventRecord(P.ev[evset][evk], s);
-      if (ee != hipSuccess) {
-        char buf[160]; snprintf(buf, sizeof buf, "hipEventRecord failed: %s (event %p, stream %p, evk %zu of %zu, recording %d)",
-                                hipGetErrorString(ee), (void*)P.ev[evset][evk], (void*)s, evk, P.ev[evset].size(), (int)external);
-        set_error(buf); return GDF_ERR_HIP;
-      }
-    }
-    hipError_t e = op.fn(b, s);
-    if (timed) {
-      const hipError_t ee = external ? record_in_capture(P.ev[evset][evk + 1], s) : hipEventRecord(P.ev[evset][evk + 1], s);
-      if (ee != hipSuccess && e == hipSuccess) { set_error("hipEventRecord failed"); return GDF_ERR_HIP; }
-      evk += 2;
-    }
-    if (e != hipSuccess) { set_error(std::string("op '") + op.name + "' failed: " + hipGetErrorString(e)); return GDF_ERR_HIP; }
-  }
-  return traj_step(P, b, s);
-}
-
-// hipGraph path: the op program is recorded once per distinct binding table into a hipGraph (explicit kernel nodes, launch.h) and replayed on
-// the caller's stream with one hipGraphLaunch; ~2400 kernel launches per SDXL forward become one host call.
-static int run_ops_graph(Plan& P, const Bind& b, hipStream_t s, int evset = -1) {
-  const size_t nh = P.hooks.size();
-  const int label = evset >= 0 ? P.timing_label : -1;
-  for (auto& g : P.graphs) {
-    bool same = g.evset == evset && g.label == label && memcmp(g.key.base, b.base, sizeof b.base) == 0 && memcmp(g.key.f, b.f, sizeof b.f) == 0 &&
-                memcmp(&g.key.mt, &b.mt, sizeof b.mt) == 0 &&
-                g.hook_ptrs.size() == nh;
-    for (size_t i = 0; same && i < nh; ++i) same = g.hook_ptrs[i] == b.hooks[i];
-    if (same) {
-      g.stamp = ++P.graph_clock; ++P.graph_launches;
-      if (hipGraphLaunch(g.exec, s) != hipSuccess) { set_error("hipGraphLaunch failed"); return GDF_ERR_HIP; }
-      return GDF_OK;
-    }
-  }
-  Plan::GraphEntry g;
-  g.key = b; g.key.hooks = nullptr; g.evset = evset; g.label = label;
-  for (size_t i = 0; i < nh; ++i) g.hook_ptrs.push_back(b.hooks[i]);
-  // The graph is BUILT, not captured (launch.h): while this thread's recorder is set, every kernel launch of the op program appends a kernel
-  // node (and every timing event an event-record node) to one dependency chain.  No stream is ever in capture mode, so nothing another host
-  // thread does — allocating, freeing, synchronising the device, building its own graphs — can invalidate it (one extractor per thread:
-  // aggregation_network.py:67-95).
-  int rc;
-  hipError_t e = hipGraphCreate(&g.graph, 0);
-  if (e != hipSuccess) { (void)hipGetLastError(); g.graph = nullptr; rc = GDF_ERR_HIP; }
-  else {
-    GraphRecorder rec; rec.graph = g.graph;
-    thread_recorder() = &rec;
-    rc = run_ops_eager(P, b, s, evset, true);
-    thread_recorder() = nullptr;
-    e = rec.err;
-    if (rc == GDF_OK && e != hipSuccess) { set_error(std::string("graph node creation failed: ") + hipGetErrorString(e)); rc = GDF_ERR_HIP; }
-  }
-  static const bool dbg = getenv("GDF_DEBUG_GRAPH") != nullptr;
-  if (dbg) fprintf(stderr, "[gdf] graph build evset=%d rc=%d err=%s graph=%p (%s)\n", evset, rc, hipGetErrorString(e), (void*)g.graph, rc ? last_error() : "");
-  auto failed = [&](const char* what, hipError_t err) {
-    // reported once per plan: a persistently failing capture would otherwise silently turn every forward into ~1000 eager launches
-    if (P.graph_capture_failures++ == 0)
-      fprintf(stderr, "[gdf] hipGraph %s failed (%s%s%s): this forward runs eagerly; gdf_plan_graph_failures() counts such calls\n", what,
-              hipGetErrorString(err), rc != GDF_OK ? "; " : "", rc != GDF_OK ? last_error() : "");
-  };
-  if (rc != GDF_OK || e != hipSuccess || !g.graph) {
-    // a recording that failed has executed nothing: drop it and run this forward eagerly (the ops are pure functions of their inputs);
-    // the next call tries again
-    if (g.graph) hipGraphDestroy(g.graph);
-    (void)hipGetLastError();
-    failed("construction", e);
-    return run_ops_eager(P, b, s, evset);
-  }
-  hipError_t ie;
-  { CaptureExclusive guard; ie = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0); }      // (allocates: not beside another thread's capture)
-  if (ie != hipSuccess) {
-    hipGraphDestroy(g.graph);
-    (void)hipGetLastError();
-    failed("instantiate", ie);
-    return run_ops_eager(P, b, s, evset);
-  }
-  ++P.graph_captures;
-  if (P.graphs.size() >= 12) {                           // evict the least recently used entry (timed replays: one graph per event set)
-    size_t lru = 0;
-    for (size_t i = 1; i < P.graphs.size(); ++i) if (P.graphs[i].stamp < P.graphs[lru].stamp) lru = i;
-    { CaptureExclusive guard; hipGraphExecDestroy(P.graphs[lru].exec); hipGraphDestroy(P.graphs[lru].graph); }
-    P.graphs.erase(P.graphs.begin() + lru);
-  }
-  g.stamp = ++P.graph_clock; ++P.graph_launches;
-  P.graphs.push_back(g);
-  if (hipGraphLaunch(P.graphs.back().exec, s) != hipSuccess) { set_error("hipGraphLaunch failed"); return GDF_ERR_HIP; }
-  return GDF_OK;
-}
-
-int plan_run(Plan& P, const Bind& b, hipStream_t s, float* ms, const char** names, double* flops, int cap) {
-  if (P.graph_mode && !ms && s != nullptr) {
-    if (!P.warmed) { P.warmed = true; return run_ops_eager(P, b, s); }
-    if (P.timing_label < 0) return run_ops_graph(P, b, s);
-    // timed replay: this forward uses event set `evset`; its results are collected when the set comes round again (or on read)
-    if (!P.timed_graph_broken) {
-      const int evset = P.ev_next; P.ev_next = (P.ev_next + 1) % Plan::EV_RING;
-      timing_collect(P, evset);
-      const long fails = P.graph_capture_failures;
-      const int rc = run_ops_graph(P, b, s, evset);
-      if (P.graph_capture_failures != fails) P.timed_graph_broken = true;     // ran eagerly (with plain events); stay eager from now on
-      if (rc == GDF_OK) P.ev_used[evset] = true;
-      return rc;
-    }
-  }
-  P.warmed = true;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ms) { hipEventCreate(&e0); hipEventCreate(&e1); }
-  int i = 0;
-  int evset = -1; size_t evk = 0;
-  if (P.timing_label >= 0 && !ms) {
-    evset = P.ev_next; P.ev_next = (P.ev_next + 1) % Plan::EV_RING;
-    timing_collect(P, evset);           // results of the forward that used this set EV_RING calls ago
-    P.ev_used[evset] = true;
-  }
-  long nlab = 0;
-  for (auto& op : P.ops) {
-    if (ms && i < cap) hipEventRecord(e0, s);
-    const bool timed = evset >= 0 && op.label == P.timing_label && (nlab++ % P.timing_stride) == 0;
-    if (timed) hipEventRecord(P.ev[evset][evk], s);
-    hipError_t e = op.fn(b, s);
-    if (timed) { hipEventRecord(P.ev[evset][evk + 1], s); evk += 2; }
-    if (e != hipSuccess) {
-      set_error(std::string("op '") + op.name + "' failed: " + hipGetErrorString(e));
-      return GDF_ERR_HIP;
-    }
-    if (ms && i < cap) {
-      hipEventRecord(e1, s); hipEventSynchronize(e1);
-      hipEventElapsedTime(&ms[i], e0, e1);
-      if (names) names[i] = op.name;
-      if (flops) flops[i] = op.flops;
-    }
-    ++i;
-  }
-  if (ms) { hipEventDestroy(e0); hipEventDestroy(e1); }
-  return traj_step(P, b, s);
 }
 
 int plan_trajectory(Plan& P, const Model& m, float* x32, int n_steps, const float* table, const void* ctx, const void* txt, const float* tid,
@@ -1207,7 +995,7 @@ int plan_sample(Plan& A, Plan* Hk, float* x32, int n_rows, const float* table, f
   b.base[BUF_WS] = (char*)ws_plain; b.base[BUF_WT] = (char*)m.weights; b.base[BUF_LAT] = st + L.lat16; b.base[BUF_T] = st + L.tbuf;
   b.base[BUF_CTX] = (char*)ctx; b.base[BUF_TXT] = (char*)txt; b.base[BUF_TID] = (char*)tid; b.base[BUF_NOISE] = (char*)noise;
   b.base[BUF_X32] = (char*)x32; b.base[BUF_SAMPLE] = st;
-  b.f[0] = guided ? 1.f : 0.f;
+  b.f[F_SAMPLE_GUIDED] = guided ? 1.f : 0.f;
   // the first forward's input and timestep (row 0); from here on every row is forward + update with the same arguments per plan
   const hipError_t e = launch_guided_step(x32, nullptr, (float*)(st + L.hist), (half_t*)b.base[BUF_LAT], (float*)b.base[BUF_T],
                                           (int*)(st + L.steps), B, A.H, A.W, 1, s);

@@ -130,7 +130,7 @@ struct Model {
 // Flux reuses the slots: LAT = hidden_states, T = timestep, CTX = encoder_hidden_states, TXT = pooled_projections,
 // TID = guidance, NOISE = output; IDS_IMG / IDS_TXT = img_ids / txt_ids
 // SAMPLE: the caller's state block of a guided sampling run (gdf_sample, sample_layout); a slot of its OWN, which only plan_sample fills —
-// the executor appends the guided update wherever it is set, so it must never alias an input of another front end
+// the executor's tail (unet_scheduler_step) appends the guided update wherever it is set, so it must never alias an input of another front end
 // RES: the caller's ControlNet residual block (gdf_forward_res, residual_layout); null on every other call
 // COND / RES_OUT: a ControlNet plan's control image and the residual block it WRITES (gdf_controlnet_forward); null on every other call
 enum { BUF_WS = 0, BUF_WT, BUF_LAT, BUF_T, BUF_CTX, BUF_TXT, BUF_TID, BUF_NOISE, BUF_IDS_IMG, BUF_IDS_TXT, BUF_SAMPLE, BUF_RES, BUF_COND, BUF_RES_OUT,
@@ -138,11 +138,17 @@ enum { BUF_WS = 0, BUF_WT, BUF_LAT, BUF_T, BUF_CTX, BUF_TXT, BUF_TID, BUF_NOISE,
 enum { BUF_X32 = BUF_IDS_IMG };                 // UNet trajectory (gdf_trajectory): the caller's fp32 master latents; null on a plain forward
 enum { BUF_HOOK0 = 1 << 16 };                   // Ref.buf = BUF_HOOK0 + slot: the caller's hook buffer `slot` (an op's output IS the hook)
 struct Ref { int buf = BUF_WS; size_t off = 0; };
+// The slots of Bind::f, one group per front end (a plan belongs to one front end, so the groups share indices).  Unused slots stay 0.
+enum { F_VAE_SCALING = 0, F_VAE_NOISE_A, F_VAE_NOISE_B, F_VAE_IN_SCALE,   // VAE encoder: scaling_factor, noise_a, noise_b, input_scale;
+       F_VAE_SHIFT,                                                      // gdf_vae_encode_packed adds shift_factor and
+       F_VAE_PACKED };                                                   // 1 (fp16) / 2 (bf16) token rows, which selects the packed tail
+enum { F_DEC_C_SAMPLE = 0, F_DEC_C_EPS, F_DEC_INV_SCALING };             // VAE decoder: c_sample, c_eps, 1 / scaling_factor
+enum { F_SAMPLE_GUIDED = 0 };                                            // gdf_sample: != 0 on a guided run (unet_scheduler_step)
+enum { F_CONTROL_COND_F32 = 1 };                                         // gdf_controlnet_forward: != 0 when the control image is fp32
 struct Bind {
   char* base[BUF_COUNT] = {nullptr};
   void* const* hooks = nullptr;
-  float f[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // run-time scalars (VAE: scaling_factor, noise_a, noise_b, input_scale; gdf_vae_encode_packed adds
-                                              // f[4] = shift_factor and f[5] = 1 (fp16) / 2 (bf16), which selects the packed tail: part of the graph key)
+  float f[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // run-time scalars (the F_* slots above): part of the graph key, compared bytewise
   // VAE encode for several timesteps (gdf_vae_encode_multi): n > 0 makes the tail op fan out — row block k of BUF_TXT / BUF_CTX / BUF_NOISE
   // starts k * stride fp16 elements after block 0 and uses the k-th triple.  Part of the graph key, like f (no padding: compared bytewise)
   struct MultiT { long n = 0, stride = 0; float noise_a[GDF_MAX_TIMESTEPS] = {}, noise_b[GDF_MAX_TIMESTEPS] = {}, in_scale[GDF_MAX_TIMESTEPS] = {}; } mt;
@@ -206,6 +212,8 @@ const char* kernel_label(const char* opname);
 int plan_set_timing(Plan& P, const char* label);
 int plan_read_timing(Plan& P, double* ms, long* launches, double* flops);
 
+// The zeroed device arena (weight_bytes) of a model whose layout is complete.  On failure: error set, `m` deleted, false.
+bool alloc_weight_arena(Model* m);
 Model* model_create(const GdfArch& arch);
 // a ControlNetModel over the encoder half of `arch` (include/gdf_control.h)
 Model* controlnet_create(const GdfArch& arch, const int cond_channels[4], int conditioning_channels, bool layout_only = false);
@@ -232,8 +240,12 @@ size_t sample_state_bytes(int batch, int H, int W, int n_rows);
 int plan_sample(Plan& plain, Plan* hooked, float* x32, int n_rows, const float* table, float guidance, const void* ctx, const void* txt,
                 const float* tid, const int* capture_rows, int n_capture, void* const* hook_out, void* noise, void* state, void* ws_plain,
                 void* ws_hooked, hipStream_t s);
-// executes the op program against an already filled binding table (shared by the UNet and Flux front ends)
+// executes the op program against an already filled binding table (plan_exec.cpp; shared by every front end)
 int plan_run(Plan& P, const Bind& b, hipStream_t s, float* ms, const char** names, double* flops, int cap);
+// The UNet's scheduler update, which the executor's op loop ends with (model.cpp): guided_step where BUF_SAMPLE and BUF_X32 are bound
+// (gdf_sample), latent_step where a trajectory plan (traj_off) has BUF_X32 bound, nothing on every other call — so no other front end may
+// bind BUF_SAMPLE.
+int unet_scheduler_step(const Plan& P, const Bind& b, hipStream_t s);
 
 // ---- VAE encoder front end (include/gdf_vae.h) ----
 Model* vae_model_create(const gdf_vae_desc& d);

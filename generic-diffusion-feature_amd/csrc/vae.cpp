@@ -217,18 +217,19 @@ struct VB : PlanBuilder {
       const bool uq = d.use_quant_conv != 0;
       const Ref qw = wt(v.quant.w), qb = wt(v.quant.b);
       op("vae_sample_noise", 0, [=](const Bind& b, hipStream_t s) {
-        if (b.f[5] != 0.f)                                                 // gdf_vae_encode_packed: shift, flow-matching noise, 2x2-packed token rows
+        if (b.f[F_VAE_PACKED] != 0.f)                                      // gdf_vae_encode_packed: shift, flow-matching noise, 2x2-packed token rows
           return launch_vae_finish_packed((const float*)b.ws(mo), Bq, hh, ww, Lc, uq ? (const half_t*)b.p(qw) : nullptr,
                                           uq ? (const float*)b.p(qb) : nullptr, (const half_t*)b.base[BUF_TXT], (const half_t*)b.base[BUF_CTX],
-                                          b.f[0], b.f[4], b.f[1], b.f[2], b.f[5] == 2.f, b.base[BUF_NOISE], s);
+                                          b.f[F_VAE_SCALING], b.f[F_VAE_SHIFT], b.f[F_VAE_NOISE_A], b.f[F_VAE_NOISE_B], b.f[F_VAE_PACKED] == 2.f,
+                                          b.base[BUF_NOISE], s);
         if (b.mt.n > 0)                                                    // gdf_vae_encode_multi: one pass over the moments, n timesteps out
           return launch_vae_finish_multi((const float*)b.ws(mo), Bq, HW, Lc, uq ? (const half_t*)b.p(qw) : nullptr,
                                          uq ? (const float*)b.p(qb) : nullptr, (const half_t*)b.base[BUF_TXT], (const half_t*)b.base[BUF_CTX],
-                                         b.f[0], (int)b.mt.n, b.mt.noise_a, b.mt.noise_b, b.mt.in_scale, (half_t*)b.base[BUF_NOISE],
+                                         b.f[F_VAE_SCALING], (int)b.mt.n, b.mt.noise_a, b.mt.noise_b, b.mt.in_scale, (half_t*)b.base[BUF_NOISE],
                                          b.mt.stride, s);
         return launch_vae_finish((const float*)b.ws(mo), Bq, HW, Lc, uq ? (const half_t*)b.p(qw) : nullptr,
                                  uq ? (const float*)b.p(qb) : nullptr, (const half_t*)b.base[BUF_TXT], (const half_t*)b.base[BUF_CTX],
-                                 b.f[0], b.f[1], b.f[2], b.f[3], (half_t*)b.base[BUF_NOISE], s);
+                                 b.f[F_VAE_SCALING], b.f[F_VAE_NOISE_A], b.f[F_VAE_NOISE_B], b.f[F_VAE_IN_SCALE], (half_t*)b.base[BUF_NOISE], s);
       });
     }
     untmp(mo, mo_b);
@@ -236,7 +237,7 @@ struct VB : PlanBuilder {
 
   // ---- decoder op program (`vae-out`): latents + noise_pred -> image ----
   // BUF_LAT = latents (B, L, h, w) fp16 NCHW, BUF_CTX = noise_pred (same shape) or NULL, BUF_NOISE = image out (B, H, W, 3) fp16
-  // channels-last; Bind::f = {c_sample, c_eps, 1 / scaling_factor}
+  // channels-last; Bind::f = the F_DEC_* slots (model.h)
   void build_decoder(int h, int w) {
     const gdf_vae_desc& d = v.d;
     const int L = d.n_levels, nl = d.layers_per_block, Bq = Bn;
@@ -248,8 +249,8 @@ struct VB : PlanBuilder {
       const bool pq = d.use_quant_conv != 0;
       const Ref qw = wt(v.post_quant.w), qb = wt(v.post_quant.b);
       op("vae_dec_prepare", 0, [=](const Bind& b, hipStream_t s) {
-        return launch_vae_dec_prepare((const half_t*)b.base[BUF_LAT], (const half_t*)b.base[BUF_CTX], Bq, HW, Lc, b.f[0], b.f[1], b.f[2],
-                                      pq ? (const half_t*)b.p(qw) : nullptr, pq ? (const float*)b.p(qb) : nullptr, (half_t*)b.ws(x8), s);
+        return launch_vae_dec_prepare((const half_t*)b.base[BUF_LAT], (const half_t*)b.base[BUF_CTX], Bq, HW, Lc, b.f[F_DEC_C_SAMPLE],
+                                      b.f[F_DEC_C_EPS], b.f[F_DEC_INV_SCALING], pq ? (const half_t*)b.p(qw) : nullptr, pq ? (const float*)b.p(qb) : nullptr, (half_t*)b.ws(x8), s);
       });
     }
     Act cur = new_act(c, h, w, true);
@@ -307,6 +308,27 @@ static bool gn_from_epilogue() {
   return !(e && e[0] == '0');
 }
 
+// sub-batch: the largest divisor of `batch` whose widest fp16 activation (`widest` bytes per image) stays below the 32-bit buffer-offset limit
+static int sub_batch(int batch, size_t widest) {
+  int chunk = 1;
+  for (int c = 1; c <= batch; ++c)
+    if (batch % c == 0 && (size_t)c * widest < (1ull << 31)) chunk = c;
+  return chunk;
+}
+
+// What every entry point binds for images c0 .. c0 + chunk - 1 of a sub-batch pass: workspace, weights, the input advanced by c0 items of in_b
+// bytes, eps and noise (either may be null) by c0 latents of lat_b bytes, the output by c0 items of out_b bytes.  The scalars are the caller's.
+static Bind sub_batch_bind(const Model& m, void* ws, int c0, const void* in, size_t in_b, const void* eps, const void* noise, size_t lat_b,
+                           void* out, size_t out_b) {
+  Bind b;
+  b.base[BUF_WS] = (char*)ws; b.base[BUF_WT] = (char*)m.weights;
+  b.base[BUF_LAT] = (char*)in + (size_t)c0 * in_b;
+  b.base[BUF_TXT] = eps ? (char*)eps + (size_t)c0 * lat_b : nullptr;
+  b.base[BUF_CTX] = noise ? (char*)noise + (size_t)c0 * lat_b : nullptr;
+  b.base[BUF_NOISE] = (char*)out + (size_t)c0 * out_b;
+  return b;
+}
+
 Model* vae_model_create(const gdf_vae_desc& d) {
   if (d.n_levels < 1 || d.n_levels > GDF_MAX_LEVELS || d.in_channels < 1 || d.in_channels > 8 || d.latent_channels < 1 ||
       d.latent_channels > 16 || d.layers_per_block < 1) { set_error("bad vae desc"); return nullptr; }   // (16: the Flux VAE; its tail is gdf_vae_encode_packed)
@@ -317,8 +339,7 @@ Model* vae_model_create(const gdf_vae_desc& d) {
   m->vae.d = d;
   VaeModelBuilder b(*m);
   b.build();
-  { CaptureExclusive guard; const hipError_t me = hipMalloc(&m->weights, m->weight_bytes); if (me != hipSuccess) { set_error(std::string("hipMalloc(weights, ") + std::to_string(m->weight_bytes) + " bytes) failed: " + hipGetErrorString(me)); (void)hipGetLastError(); delete m; return nullptr; } }
-  (void)hipMemset(m->weights, 0, m->weight_bytes);
+  if (!alloc_weight_arena(m)) return nullptr;
   return m;
 }
 
@@ -330,19 +351,15 @@ int vae_plan_build(const Model& m, Plan& P, int batch, int img_h, int img_w, boo
   }
   const size_t S = (size_t)(img_h / down) * (img_w / down);
   if (S > 16384) { set_error("mid-block attention supports up to 16384 latent tokens (1024^2 images)"); return GDF_ERR_UNSUPPORTED; }
-  // sub-batch: largest divisor of `batch` whose widest fp16 activation stays below the 32-bit buffer-offset limit
-  size_t widest = 0;
+  size_t widest = 0;                           // bytes of the widest fp16 activation of one image
   for (int lv = 0; lv < L; ++lv)
     widest = std::max(widest, (size_t)(img_h >> lv) * (img_w >> lv) * m.vae.d.block_out_channels[lv] * 2);
-  int chunk = 1;
-  for (int c = 1; c <= batch; ++c)
-    if (batch % c == 0 && (size_t)c * widest < (1ull << 31)) chunk = c;
   if (widest >= (1ull << 31)) { set_error("image too large for 32-bit buffer offsets"); return GDF_ERR_UNSUPPORTED; }
-  P.batch = batch; P.chunk = chunk; P.H = img_h; P.W = img_w;
+  P.batch = batch; P.chunk = sub_batch(batch, widest); P.H = img_h; P.W = img_w;
   PlanOpts o{}; o.stream_fp32 = 1;
   P.opts = o;
   VB b(m, P, dry, P.opts);
-  b.Bn = chunk;
+  b.Bn = P.chunk;
   // Range: the reference upcasts the SDXL VAE to fp32 because its residual stream exceeds 65504.  Here the stream lives in
   // fp32 masters; its fp16 images (GroupNorm input, shortcut / downsample conv operand) and the resnet-internal conv1 output
   // are stored scaled by 2^-6 (max magnitude 4.2e6), exactly undone by their consumers (builder.h act_scale).
@@ -365,13 +382,8 @@ int vae_encode(Plan& P, const Model& m, const void* image, const void* eps, cons
   const int f = 1 << (d.n_levels - 1);                                               // spatial reduction (8 for the SD VAEs)
   const size_t lat_b = (size_t)d.latent_channels * (P.H / f) * (P.W / f) * 2;        // bytes per latent
   for (int c0 = 0; c0 < P.batch; c0 += P.chunk) {
-    Bind b;
-    b.base[BUF_WS] = (char*)ws; b.base[BUF_WT] = (char*)m.weights;
-    b.base[BUF_LAT] = (char*)image + (size_t)c0 * img_b;
-    b.base[BUF_TXT] = eps ? (char*)eps + (size_t)c0 * lat_b : nullptr;
-    b.base[BUF_CTX] = noise ? (char*)noise + (size_t)c0 * lat_b : nullptr;
-    b.base[BUF_NOISE] = (char*)out + (size_t)c0 * lat_b;
-    b.f[0] = scaling; b.f[1] = noise_a; b.f[2] = noise_b; b.f[3] = in_scale;
+    Bind b = sub_batch_bind(m, ws, c0, image, img_b, eps, noise, lat_b, out, lat_b);
+    b.f[F_VAE_SCALING] = scaling; b.f[F_VAE_NOISE_A] = noise_a; b.f[F_VAE_NOISE_B] = noise_b; b.f[F_VAE_IN_SCALE] = in_scale;
     const int rc = plan_run(P, b, s, ms, names, flops, cap);
     if (rc != GDF_OK) return rc;
     if (ms) break;                                                                  // profile: one sub-batch pass
@@ -379,7 +391,7 @@ int vae_encode(Plan& P, const Model& m, const void* image, const void* eps, cons
   return GDF_OK;
 }
 
-// The packed tail (Bind::f[5]: 1 = fp16, 2 = bf16 token rows; f[4] = shift_factor).  A token row belongs to one image, so a sub-batch pass advances
+// The packed tail (F_VAE_PACKED: 1 = fp16, 2 = bf16 token rows; F_VAE_SHIFT = shift_factor).  A token row belongs to one image, so a sub-batch pass advances
 // the output by whole images: c0 * (h/2)(w/2) * 4L elements = c0 latents, the same byte count as the NCHW layout.
 int vae_encode_packed(Plan& P, const Model& m, const void* image, const void* eps, const void* noise, float scaling, float shift, float noise_a,
                       float noise_b, int out_bf16, void* out, void* ws, hipStream_t s) {
@@ -392,13 +404,9 @@ int vae_encode_packed(Plan& P, const Model& m, const void* image, const void* ep
   const size_t img_b = (size_t)d.in_channels * P.H * P.W * 2;
   const size_t lat_b = (size_t)d.latent_channels * (P.H / f) * (P.W / f) * 2;
   for (int c0 = 0; c0 < P.batch; c0 += P.chunk) {
-    Bind b;
-    b.base[BUF_WS] = (char*)ws; b.base[BUF_WT] = (char*)m.weights;
-    b.base[BUF_LAT] = (char*)image + (size_t)c0 * img_b;
-    b.base[BUF_TXT] = eps ? (char*)eps + (size_t)c0 * lat_b : nullptr;
-    b.base[BUF_CTX] = noise ? (char*)noise + (size_t)c0 * lat_b : nullptr;
-    b.base[BUF_NOISE] = (char*)out + (size_t)c0 * lat_b;
-    b.f[0] = scaling; b.f[1] = noise_a; b.f[2] = noise_b; b.f[3] = 1.0f; b.f[4] = shift; b.f[5] = out_bf16 ? 2.f : 1.f;
+    Bind b = sub_batch_bind(m, ws, c0, image, img_b, eps, noise, lat_b, out, lat_b);
+    b.f[F_VAE_SCALING] = scaling; b.f[F_VAE_NOISE_A] = noise_a; b.f[F_VAE_NOISE_B] = noise_b; b.f[F_VAE_IN_SCALE] = 1.0f;
+    b.f[F_VAE_SHIFT] = shift; b.f[F_VAE_PACKED] = out_bf16 ? 2.f : 1.f;
     const int rc = plan_run(P, b, s, nullptr, nullptr, nullptr, 0);
     if (rc != GDF_OK) return rc;
   }
@@ -420,13 +428,8 @@ int vae_encode_multi(Plan& P, const Model& m, const void* image, const void* eps
   const int f = 1 << (d.n_levels - 1);
   const size_t lat_b = (size_t)d.latent_channels * (P.H / f) * (P.W / f) * 2;
   for (int c0 = 0; c0 < P.batch; c0 += P.chunk) {
-    Bind b;
-    b.base[BUF_WS] = (char*)ws; b.base[BUF_WT] = (char*)m.weights;
-    b.base[BUF_LAT] = (char*)image + (size_t)c0 * img_b;
-    b.base[BUF_TXT] = eps ? (char*)eps + (size_t)c0 * lat_b : nullptr;
-    b.base[BUF_CTX] = noise ? (char*)noise + (size_t)c0 * lat_b : nullptr;
-    b.base[BUF_NOISE] = (char*)out + (size_t)c0 * lat_b;
-    b.f[0] = scaling;
+    Bind b = sub_batch_bind(m, ws, c0, image, img_b, eps, noise, lat_b, out, lat_b);
+    b.f[F_VAE_SCALING] = scaling;
     b.mt.n = n_t; b.mt.stride = (long)((size_t)P.batch * lat_b / 2);
     for (int k = 0; k < n_t; ++k) { b.mt.noise_a[k] = noise_a[k]; b.mt.noise_b[k] = noise_b[k]; b.mt.in_scale[k] = in_scale[k]; }
     const int rc = plan_run(P, b, s, nullptr, nullptr, nullptr, 0);
@@ -452,36 +455,31 @@ Model* vae_decoder_create(const gdf_vae_desc& d) {
   m->vae.d = d;
   VaeModelBuilder b(*m);
   b.build_decoder();
-  { CaptureExclusive guard; const hipError_t me = hipMalloc(&m->weights, m->weight_bytes); if (me != hipSuccess) { set_error(std::string("hipMalloc(weights, ") + std::to_string(m->weight_bytes) + " bytes) failed: " + hipGetErrorString(me)); (void)hipGetLastError(); delete m; return nullptr; } }
-  (void)hipMemset(m->weights, 0, m->weight_bytes);
+  if (!alloc_weight_arena(m)) return nullptr;
   return m;
 }
 
 int vae_dec_plan_build(const Model& m, Plan& P, int batch, int lat_h, int lat_w, bool dry) {
   if (m.kind != 4) { set_error("not a VAE decoder model"); return GDF_ERR_ARG; }
-  const int L = m.vae.d.n_levels, upf = 1 << (L - 1);
+  const int L = m.vae.d.n_levels;
   if (batch < 1 || lat_h < 8 || lat_w < 8 || (lat_h % 8) || (lat_w % 8)) {                     // latent grid multiple of 8: S % 64 == 0
     set_error("latent size must be a positive multiple of 8"); return GDF_ERR_ARG;
   }
   const size_t S = (size_t)lat_h * lat_w;
   if (S > 16384) { set_error("mid-block attention supports up to 16384 latent tokens (1024^2 images)"); return GDF_ERR_UNSUPPORTED; }
-  // sub-batch: largest divisor of `batch` whose widest fp16 activation stays below the 32-bit buffer-offset limit.  Up block i works
-  // at (lat << i) with boc[L-1-i] channels; its upsampler's OUTPUT has the same channels at twice the size
+  // the widest fp16 activation of one image: up block i works at (lat << i) with boc[L-1-i] channels; its upsampler's OUTPUT has the same
+  // channels at twice the size
   size_t widest = 0;
   for (int i = 0; i < L; ++i) {
     const size_t hw = (size_t)(lat_h << i) * (lat_w << i), c = m.vae.d.block_out_channels[L - 1 - i];
     widest = std::max(widest, hw * c * 2 * (i != L - 1 ? 4 : 1));
   }
   if (widest >= (1ull << 31)) { set_error("image too large for 32-bit buffer offsets"); return GDF_ERR_UNSUPPORTED; }
-  int chunk = 1;
-  for (int c = 1; c <= batch; ++c)
-    if (batch % c == 0 && (size_t)c * widest < (1ull << 31)) chunk = c;
-  P.batch = batch; P.chunk = chunk; P.H = lat_h; P.W = lat_w;
-  (void)upf;
+  P.batch = batch; P.chunk = sub_batch(batch, widest); P.H = lat_h; P.W = lat_w;
   PlanOpts o{}; o.stream_fp32 = 1;
   P.opts = o;
   VB b(m, P, dry, P.opts);
-  b.Bn = chunk;
+  b.Bn = P.chunk;
   b.act_scale = 1.0f / 64.0f;          // fp16 range control of the stream images, as in the encoder (vae_plan_build)
   b.gn_epi = gn_from_epilogue();
   b.build_decoder(lat_h, lat_w);
@@ -499,12 +497,8 @@ int vae_decode(Plan& P, const Model& m, const void* latents, const void* noise_p
   const size_t lat_b = (size_t)d.latent_channels * P.H * P.W * 2;                    // bytes per latent
   const size_t img_b = (size_t)d.in_channels * (P.H * f) * (P.W * f) * 2;            // bytes per image
   for (int c0 = 0; c0 < P.batch; c0 += P.chunk) {
-    Bind b;
-    b.base[BUF_WS] = (char*)ws; b.base[BUF_WT] = (char*)m.weights;
-    b.base[BUF_LAT] = (char*)latents + (size_t)c0 * lat_b;
-    b.base[BUF_CTX] = noise_pred ? (char*)noise_pred + (size_t)c0 * lat_b : nullptr;
-    b.base[BUF_NOISE] = (char*)image_out + (size_t)c0 * img_b;
-    b.f[0] = c_sample; b.f[1] = c_eps; b.f[2] = inv_scaling;
+    Bind b = sub_batch_bind(m, ws, c0, latents, lat_b, /*eps=*/nullptr, noise_pred, lat_b, image_out, img_b);
+    b.f[F_DEC_C_SAMPLE] = c_sample; b.f[F_DEC_C_EPS] = c_eps; b.f[F_DEC_INV_SCALING] = inv_scaling;
     const int rc = plan_run(P, b, s, ms, names, flops, cap);
     if (rc != GDF_OK) return rc;
     if (ms) break;                                                                  // profile: one sub-batch pass
