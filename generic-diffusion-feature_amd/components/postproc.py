@@ -6,6 +6,8 @@ the hot path:
                      F.interpolate(v, size, mode='bilinear') of every layer + torch.cat(dim=1), one launch per 16 layers
   nn_match / find_nn_source_correspondences   correspondence/correspondence/correspondence_utils.py:113-138   the evaluators' second step:
                      nearest neighbours of N source points among the load-size target pixels, without either load-size map (csrc/corres.hip)
+  PixelClassifierEnsemble / predict_labels    scarce_segmentation/segmentation/pixel_classifier.py:14-36, 70-107   the label-scarce evaluator's
+                     second step: an ensemble of per-pixel MLPs, majority vote and Jensen-Shannon uncertainty (csrc/pixcls.hip)
   avg_pool           components/feature_extractor.py:51-53   `feature_resize` (adaptive_avg_pool2d to (H/r, W/r))
   aggregate_maps     components/attention.py:238-244, 141-161 + diffusion_feature.py:492-500   aggregated `attn` feature
 
@@ -41,6 +43,11 @@ AGG_MAX = 16                                             # sources of one gdf_op
 _SIG["gdf_op_nn_match_workspace"] = (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int])
 _SIG["gdf_op_nn_match"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p])
+_SIG["gdf_pixcls_create"] = (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 6 + [C.POINTER(C.c_void_p)])
+_SIG["gdf_pixcls_destroy"] = (None, [C.c_void_p])
+_SIG["gdf_pixcls_workspace"] = (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int])
+_SIG["gdf_pixcls_predict"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_void_p])
 _lib = None
 
 
@@ -191,6 +198,182 @@ def find_nn_source_correspondences(img1_feats, img2_feats, source_points, output
     B = img1_feats.shape[0]
     points2, _ = nn_match(img1_feats, img2_feats, torch.from_numpy(idx)[None].expand(B, -1, -1), (LH, LW))
     return torch.from_numpy(source_points), points2[0]
+
+
+_PC_KEYS = ("0.weight", "0.bias", "2.weight", "2.bias", "2.running_mean", "2.running_var", "3.weight", "3.bias", "5.weight", "5.bias",
+            "5.running_mean", "5.running_var", "6.weight", "6.bias")
+PC_BN_EPS = 1e-5                                         # nn.BatchNorm1d's default, what pixel_classifier builds
+
+
+def pixel_classifier_params(model):
+    """One member of the ensemble -> {"0.weight": fp32 CPU tensor, ...} for the keys of layers.{0,2,3,5,6}: `model` is a reference pixel_classifier
+    module (in eval mode: training-mode BatchNorm uses batch statistics, which no folded network reproduces) or its state dict, with or without
+    the `module.` prefix nn.DataParallel saves."""
+    if isinstance(model, torch.nn.Module):
+        if model.training:
+            raise ValueError("pixel classifier in training mode: call .eval() (BatchNorm must use its running statistics)")
+        model = model.state_dict()
+    sd = {}
+    for k, v in model.items():
+        k = k[len("module."):] if k.startswith("module.") else k
+        if k.startswith("layers."):
+            sd[k[len("layers."):]] = v.detach().to("cpu", torch.float32)
+    missing = [k for k in _PC_KEYS if k not in sd]
+    if missing:
+        raise ValueError("not a pixel_classifier state dict: no layers.%s" % missing[0])
+    w1, w2, w3 = sd["0.weight"], sd["3.weight"], sd["6.weight"]
+    if w1.dim() != 2 or w2.dim() != 2 or w3.dim() != 2 or w2.shape[1] != w1.shape[0] or w3.shape[1] != w2.shape[0]:
+        raise ValueError("not a pixel_classifier state dict: the three Linear layers do not chain")
+    return {k: sd[k] for k in _PC_KEYS}
+
+
+def fold_pixel_classifier(sd):
+    """BatchNorm-folded fp32 parameters (W1, b1, W2, b2, W3, b3) of one pixel_classifier_params dict.  Eval-mode BatchNorm1d after ReLU is
+    y = a h + d with a = gamma / sqrt(var + eps), d = beta - mean a, so the next Linear becomes (W diag(a)) h + (W d + b): computed in fp64 and
+    rounded once to fp32."""
+    d = {k: v.double() for k, v in sd.items()}
+    out = [d["0.weight"], d["0.bias"]]
+    for bn, lin in (("2", "3"), ("5", "6")):
+        a = d[bn + ".weight"] / torch.sqrt(d[bn + ".running_var"] + PC_BN_EPS)
+        sh = d[bn + ".bias"] - d[bn + ".running_mean"] * a
+        out += [d[lin + ".weight"] * a[None, :], d[lin + ".weight"] @ sh + d[lin + ".bias"]]
+    return tuple(v.float().contiguous() for v in out)
+
+
+class PixelClassifierEnsemble:
+    """The reference's list of pixel_classifier models (load_ensemble) as one device op.  models: a list of modules or of state dicts, all of one
+    architecture, recognised from the shapes: dim -> 128 -> 32 -> classes, or dim -> 256 -> 128 -> classes from 30 classes up."""
+
+    def __init__(self, models):
+        models = list(models)
+        if not models:
+            raise ValueError("an ensemble has at least one model")
+        self.params = [pixel_classifier_params(m) for m in models]
+        shapes = [tuple(tuple(v.shape) for v in p.values()) for p in self.params]
+        if any(s != shapes[0] for s in shapes):
+            raise ValueError("the models of an ensemble have the same shapes")
+        w1, w2, w3 = (self.params[0][k] for k in ("0.weight", "3.weight", "6.weight"))
+        self.M, self.C, self.h1, self.h2, self.K = len(models), w1.shape[1], w1.shape[0], w2.shape[0], w3.shape[0]
+        folded = [fold_pixel_classifier(p) for p in self.params]
+        self.folded = tuple(torch.stack([f[i] for f in folded]).contiguous() for i in range(6))     # W1 (M, h1, C), b1, W2, b2, W3, b3
+        self._handles = {}
+
+    def _handle(self, dev):
+        """gdf_pixcls of this ensemble on `dev` (created on first use there; the library refuses sizes it has no kernel for)"""
+        key = torch.device(dev).index or 0
+        if key not in self._handles:
+            h = C.c_void_p()
+            with torch.cuda.device(dev):
+                native._check(_L().gdf_pixcls_create(self.C, self.M, self.h1, self.h2, self.K, *[C.c_void_p(t.data_ptr()) for t in self.folded],
+                                                     C.byref(h)), "pixcls_create")
+            self._handles[key] = h
+        return self._handles[key]
+
+    def __del__(self):
+        for h in getattr(self, "_handles", {}).values():
+            try:
+                _lib.gdf_pixcls_destroy(h)
+            except Exception:
+                pass
+
+    def _map(self, features, size):
+        """-> (the logical (B, C, H, W) view, the shape of the label tensor)"""
+        if features.dim() == 4:
+            v, shape = features, (features.shape[0], features.shape[2], features.shape[3])
+        elif features.dim() == 2:
+            if size is None:
+                raise ValueError("a (P, dim) matrix needs size=(H, W)")
+            size = tuple(int(s) for s in size)
+            if len(size) != 2 or size[0] * size[1] != features.shape[0]:
+                raise ValueError("size is (H, W) with H * W = P")
+            v, shape = features.t().unflatten(1, size).unsqueeze(0), size
+        else:
+            raise ValueError("features is a (B, C, H, W) map or a (P, dim) matrix")
+        if v.shape[1] != self.C:
+            raise ValueError(f"the features have {v.shape[1]} channels, the ensemble takes {self.C}")
+        if v.shape[2] < 1 or v.shape[3] < 1:
+            raise ValueError("H and W >= 1")
+        return v, shape
+
+    def _host(self, v):
+        """the reference's torch chain in fp32 on a host map -> (labels, js, model labels, logits)"""
+        from torch.distributions import Categorical
+        B, _, H, W = v.shape
+        x = v.permute(0, 2, 3, 1).reshape(-1, self.C).float()
+        logits, ent, labs, mean = [], [], [], None
+        for p in self.params:
+            h = x
+            for lin, bn in (("0", "2"), ("3", "5")):
+                h = F.batch_norm(F.relu(F.linear(h, p[lin + ".weight"], p[lin + ".bias"])), p[bn + ".running_mean"], p[bn + ".running_var"],
+                                 p[bn + ".weight"], p[bn + ".bias"], False, 0.0, PC_BN_EPS)
+            preds = F.linear(h, p["6.weight"], p["6.bias"])
+            logits.append(preds)
+            ent.append(Categorical(logits=preds).entropy())
+            sm = torch.softmax(preds, 1)
+            mean = sm if mean is None else mean + sm
+            labs.append(torch.max(torch.log_softmax(preds, 1), 1)[1])
+        mean = mean / self.M
+        js = Categorical(mean).entropy() - torch.mean(torch.stack(ent), 0)
+        labs = torch.stack(labs)
+        return (torch.mode(labs, 0)[0].reshape(B, H, W), js.reshape(B, H, W), labs.to(torch.uint8).reshape(self.M, B, H, W), torch.stack(logits))
+
+    def predict_full(self, features, size=None):
+        """-> (labels int64, top_k, js fp32, model_labels uint8 (M, ...), logits fp32 (M, P, K)), on the device of `features`.
+        features: a (B, C, H, W) map, fp16 or fp32 with any strides -> labels and js (B, H, W), top_k (B,); or the reference's (P, dim) matrix with
+        size = (H, W) -> labels and js of that size, top_k 0-d.  top_k is the reference's js.sort()[0][-int(P / 10):].mean() per image."""
+        v, shape = self._map(features, size)
+        B, _, H, W = v.shape
+        if not v.is_cuda:
+            labels, js, mlab, logits = self._host(v)
+        else:
+            dev = v.device
+            v = v if v.dtype in (torch.float16, torch.float32) else v.float()
+            with torch.cuda.device(dev):
+                labels = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+                js = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+                mlab = torch.empty(self.M, B, H, W, dtype=torch.uint8, device=dev)
+                logits = torch.empty(self.M, B * H * W, self.K, dtype=torch.float32, device=dev)
+                if B > 0:
+                    L, h = _L(), self._handle(dev)
+                    nbytes = L.gdf_pixcls_workspace(h, B, H, W)
+                    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                    src = _agg_src(v)
+                    native._check(L.gdf_pixcls_predict(h, C.addressof(src), B, C.c_void_p(labels.data_ptr()), C.c_void_p(js.data_ptr()),
+                                                       C.c_void_p(mlab.data_ptr()), C.c_void_p(logits.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes,
+                                                       _stream(dev)), "pixcls_predict")
+        P = H * W
+        top_k = torch.stack([row.sort()[0][-int(P / 10):].mean() for row in js.reshape(B, P)]) if B > 0 else js.new_zeros(0)
+        if features.dim() == 2:
+            return labels.reshape(shape), top_k[0], js.reshape(shape), mlab.reshape(self.M, *shape), logits
+        return labels, top_k, js, mlab, logits
+
+    def predict(self, features, size=None):
+        """-> (labels int64, top_k): see predict_full"""
+        return self.predict_full(features, size)[:2]
+
+
+_pc_cache = {}
+
+
+def predict_labels(models, features, size):
+    """The reference's function (scarce_segmentation/segmentation/pixel_classifier.py:70-107), same signature and return value: features a
+    (P, dim) matrix (tensor or numpy array), size = (H, W) -> (labels int64 of that size on the CPU, 0-d top_k).  models: a
+    PixelClassifierEnsemble, or the reference's list of modules; the ensemble built from a list is kept, with the list, under the list's identity
+    (and rebuilt when its length changes).  Host features are moved to the GPU as the reference moves them, when there is one."""
+    if isinstance(features, np.ndarray):
+        features = torch.from_numpy(features)
+    if isinstance(models, PixelClassifierEnsemble):
+        ens = models
+    else:
+        hit = _pc_cache.get(id(models))
+        if hit is None or hit[0] is not models or hit[1] != len(models):
+            hit = (models, len(models), PixelClassifierEnsemble(models))
+            _pc_cache[id(models)] = hit
+        ens = hit[2]
+    if not features.is_cuda and torch.cuda.is_available():
+        features = features.cuda()
+    labels, top_k = ens.predict(features, size)
+    return labels.cpu(), top_k
 
 
 def avg_pool(feat, r):

@@ -342,6 +342,23 @@ enum { NN_MAXQ = 24, NN_FINE_BLOCKS = 1024 };
 size_t nn_match_workspace(int B, int N, int C, int h2, int w2);
 hipError_t launch_nn_match(const AggSrc& f1, const AggSrc& f2, int B, const float* points, int N, int LH, int LW, long long* out_yx,
                            float* out_score, void* workspace, hipStream_t s);
+// predict_labels of the label-scarce segmentation evaluator (pixcls.hip): an ensemble of M BatchNorm-folded per-pixel MLPs C -> h1 -> h2 -> K over
+// every pixel of a logical (B, C, H, W) map, then the per-pixel vote.  pixcls_create packs W1 and W2 as scaled fp16 (hi, lo) pairs in MFMA fragment order
+// and uploads everything once (host fp32 arrays: W1 (M, h1, C), b1 (M, h1), W2 (M, h2, h1), b2 (M, h2), W3 (M, K, h2), b3 (M, K)); widths are
+// padded with zero weights to (H1P, H2P) = (128, 32) or (256, 128).  launch_pixcls: fp32 logits (M, P, K), P = B * H * W, go to `logits` or, if null,
+// to the workspace (pixcls_workspace bytes, 16-byte aligned); labels (P) int64, js (P) fp32 or null, model_labels (M, P) uint8 or null.
+enum { PC_MAXM = 16, PC_MAXK = 64, PC_MAXH = 256 };
+struct PixCls {
+  int C, M, h1, h2, K, H1P, H2P, nkt;
+  void* dev;
+  const void* w1; const float *inv_s, *b1; const void* w2; const float *inv_s2, *b2, *w3, *b3;
+};
+hipError_t pixcls_create(int C, int M, int h1, int h2, int K, const float* W1, const float* b1, const float* W2, const float* b2,
+                         const float* W3, const float* b3, PixCls** out);
+void pixcls_destroy(PixCls* pc);
+size_t pixcls_workspace(const PixCls* pc, long P);
+hipError_t launch_pixcls(const PixCls* pc, const AggSrc& x, int B, long long* labels, float* js, unsigned char* model_labels, float* logits,
+                         void* workspace, hipStream_t s);
 // adaptive_avg_pool2d to (H/r, W/r) of a channels-last hook (B,C,H,W; strides sb, 1, sy, sx) -> (B, H/r, W/r, C) fp16: the r x r mean
 // where r divides H and W, ATen's longer windows [floor(o H / OH), ceil((o + 1) H / OH)) otherwise
 hipError_t launch_avg_pool(const half_t* src, long sb, long sy, long sx, int B, int C, int H, int W, int r, half_t* out, hipStream_t s);

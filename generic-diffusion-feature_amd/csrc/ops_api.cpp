@@ -503,6 +503,44 @@ int gdf_op_nn_match(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const f
   const AggSrc b{f2->ptr, f2->f32, f2->sb, f2->sc, f2->sy, f2->sx, f2->C, f2->H, f2->W, 0};
   return fin(launch_nn_match(a, b, B, points, N, LH, LW, out_yx, out_score, workspace, (hipStream_t)stream), "gdf_op_nn_match");
 }
+int gdf_pixcls_create(int C, int M, int h1, int h2, int K, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
+                      const float* b3, gdf_pixcls* out) {
+  auto bad = [](const char* msg) { set_error(std::string("gdf_pixcls_create: ") + msg); return GDF_ERR_ARG; };
+  if (out) *out = nullptr;
+  if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !out) return bad("null pointer");
+  if (C < 1 || M < 1 || h1 < 1 || h2 < 1 || K < 1) return bad("C, M, h1, h2 and K >= 1");
+  if (M > PC_MAXM || K > PC_MAXK || h1 > PC_MAXH || h2 > PC_MAXH || h1 % 32 || h2 % 32) {
+    set_error("gdf_pixcls_create: M <= 16, K <= 64, h1 and h2 multiples of 32 up to 256");
+    return GDF_ERR_UNSUPPORTED;
+  }
+  PixCls* pc = nullptr;
+  const int rc = fin(pixcls_create(C, M, h1, h2, K, W1, b1, W2, b2, W3, b3, &pc), "gdf_pixcls_create");
+  if (rc == GDF_OK) *out = (gdf_pixcls)pc;
+  return rc;
+}
+void gdf_pixcls_destroy(gdf_pixcls h) { pixcls_destroy((PixCls*)h); }
+size_t gdf_pixcls_workspace(gdf_pixcls h, int B, int H, int W) {
+  if (!h) return 0;
+  return pixcls_workspace((const PixCls*)h, (long)std::max(B, 1) * std::max(H, 1) * std::max(W, 1));
+}
+int gdf_pixcls_predict(gdf_pixcls h, const gdf_agg_src* x, int B, long long* labels, float* js, uint8_t* model_labels, float* logits,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  auto bad = [](const char* msg) { set_error(std::string("gdf_pixcls_predict: ") + msg); return GDF_ERR_ARG; };
+  if (!h || !x || !labels || !workspace) return bad("null pointer");
+  if (!x->ptr) return bad("null feature pointer");
+  const PixCls* pc = (const PixCls*)h;
+  if (B < 0 || x->H < 1 || x->W < 1) return bad("B >= 0, H and W >= 1");
+  if (x->C != pc->C) return bad("the map's C differs from the ensemble's");
+  if ((uintptr_t)workspace & 15) return bad("workspace not 16-byte aligned");
+  if ((long long)std::max(B, 1) * x->H * x->W >= (1ll << 31)) {
+    set_error("gdf_pixcls_predict: B * H * W >= 2^31; split the batch");
+    return GDF_ERR_UNSUPPORTED;
+  }
+  if (workspace_bytes < gdf_pixcls_workspace(h, B, x->H, x->W)) return bad("workspace smaller than gdf_pixcls_workspace says");
+  if (B == 0) return GDF_OK;
+  const AggSrc a{x->ptr, x->f32, x->sb, x->sc, x->sy, x->sx, x->C, x->H, x->W, 0};
+  return fin(launch_pixcls(pc, a, B, labels, js, model_labels, logits, workspace, (hipStream_t)stream), "gdf_pixcls_predict");
+}
 int gdf_op_avg_pool(const void* src, long sb, long sy, long sx, int B, int C, int H, int W, int r, void* out, void* stream) {
   return fin(launch_avg_pool((const half_t*)src, sb, sy, sx, B, C, H, W, r, (half_t*)out, (hipStream_t)stream), "avg_pool");
 }

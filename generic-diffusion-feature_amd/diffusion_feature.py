@@ -630,6 +630,15 @@ class FeatureExtractor(nn.Module):
         from components.postproc import nn_match
         return nn_match(feats1, feats2, source_points, load_size)
 
+    def segment(self, ensemble, feats=None, size=256):
+        """The label-scarce segmentation evaluator on a feature dict (reference scarce_segmentation/task-pixel.py:85-103): aggregate(feats, size)
+        (bilinear) and the pixel-classifier ensemble's vote on the result -> (labels int64 (B, OH, OW), top_k (B,)), on the device.
+        ensemble: a components.postproc.PixelClassifierEnsemble, or the reference's list of pixel_classifier modules."""
+        from components.postproc import PixelClassifierEnsemble
+        if not isinstance(ensemble, PixelClassifierEnsemble):
+            ensemble = PixelClassifierEnsemble(ensemble)
+        return ensemble.predict(self.aggregate(feats, size))
+
     def set_background_extraction(self, idxs):
         self.feature_store.store_idx = idxs
 

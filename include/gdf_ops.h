@@ -343,6 +343,40 @@ int gdf_op_aggregate(const gdf_agg_src* srcs, int n, int B, void* out, int out_f
 size_t gdf_op_nn_match_workspace(int B, int N, int C, int h2, int w2);
 int gdf_op_nn_match(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const float* points /* device, (B, N, 2) */, int N, int LH, int LW,
                     long long* out_yx /* (B, N, 2) */, float* out_score /* (B, N) */, void* workspace, size_t workspace_bytes, void* stream);
+/* The label-scarce segmentation evaluator's second step on an aggregated map (scarce_segmentation/segmentation/pixel_classifier.py:70-107,
+ * predict_labels): an ensemble of M per-pixel MLPs (pixel_classifier, :14-36) over every pixel, the per-pixel majority vote and the ensemble's
+ * Jensen-Shannon uncertainty (csrc/pixcls.hip).  The networks are given BATCHNORM-FOLDED: eval-mode BatchNorm1d after ReLU is an
+ * affine map and folds into the next Linear, so model m is  logits = W3 relu(W2 relu(W1 x + b1) + b2) + b3.
+ *   gdf_pixcls_create   host fp32 arrays W1 (M, h1, C), b1 (M, h1), W2 (M, h2, h1), b2 (M, h2), W3 (M, K, h2), b3 (M, K), row-major as nn.Linear
+ *                       stores them.  Uploads once; W1 and W2 are packed as an fp16 (hi, lo) pair per element, each row scaled by a power of two that
+ *                       the kernel's fp32 epilogue undoes (the pair carries 22 bits of every weight).  Synchronous; the arrays may be freed afterwards.
+ *                       M <= 16, K <= 64, h1 and h2 multiples of 32 up to 256, anything beyond: GDF_ERR_UNSUPPORTED; a null pointer or a size
+ *                       below 1: GDF_ERR_ARG.
+ *   gdf_pixcls_workspace  bytes of the workspace of one predict call on a (B, C, H, W) map; 0 for a null handle.
+ *   gdf_pixcls_predict  x: a logical (B, C, H, W) tensor, fp16 (f32 = 0) or fp32, element strides sb/sc/sy/sx, read only, `coff` ignored; pixel
+ *                       p = (b H + y) W + x.  sx == 1 (NCHW, what gdf_op_aggregate writes; the reference's (P, dim) view of it has strides (1, P))
+ *                       is read with lanes along the pixels; sc == 1 with C a multiple of 8 (fp32: 4) and 16-byte aligned pixels (a channels-last
+ *                       hook; the pixel may be longer than C) with 16-byte loads along C; any other strides are correct, not fast.
+ *                       Layer 1 runs on the MFMA units with fp32 accumulation: an fp16 map is multiplied as given with W1's hi and lo halves, an
+ *                       fp32 map is split into an fp16 (hi, lo) pair as it is loaded (hi hi + hi lo + lo hi; it must lie in the fp16 range).
+ *                       Layer 2 runs on the MFMA units too, on the workgroup's hidden tile in LDS: hidden 1 as an fp16 (hi, lo) pair, W2 packed like
+ *                       W1, three products; layer 3 is fp32 FMAs.  No hidden activation is ever a single 16-bit number; none reaches memory.
+ *       logits          (M, B H W, K) fp32, or NULL: they are then kept in the workspace only
+ *       model_labels    (M, B, H, W) uint8 or NULL: per model the LOWEST index among equal maxima
+ *       js              (B, H, W) fp32 or NULL: H(mean_m softmax_m) - mean_m H(softmax_m) in fp32 with expf / logf; the mean is renormalised and its
+ *                       entropy is -sum p log(clamp(p, eps, 1 - eps)), eps = 2^-23, as torch.distributions.Categorical(probs) computes it
+ *       labels          (B, H, W) int64: the most frequent per-model label, the SMALLEST among equally frequent ones (torch.mode's rule)
+ * Two launches, stream-ordered, no atomics, fixed summation order (the same inputs give the same bits on any stream), nothing read back, no
+ * allocation.  A null pointer (handle, x, labels, workspace), H or W below 1, B < 0, x->C != C, a workspace that is not 16-byte aligned or smaller
+ * than gdf_pixcls_workspace says: GDF_ERR_ARG before any launch.  B * H * W >= 2^31: GDF_ERR_UNSUPPORTED.  B == 0 is a successful no-op. */
+typedef struct gdf_pixcls_s* gdf_pixcls;
+int gdf_pixcls_create(int C, int M, int h1, int h2, int K, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
+                      const float* b3, gdf_pixcls* out);
+void gdf_pixcls_destroy(gdf_pixcls h);
+size_t gdf_pixcls_workspace(gdf_pixcls h, int B, int H, int W);
+int gdf_pixcls_predict(gdf_pixcls h, const gdf_agg_src* x, int B, long long* labels /* (B, H, W) */, float* js /* (B, H, W) or NULL */,
+                       uint8_t* model_labels /* (M, B, H, W) or NULL */, float* logits /* (M, B H W, K) or NULL */, void* workspace,
+                       size_t workspace_bytes, void* stream);
 /* `feature_resize` (components/feature_extractor.py:51-53): adaptive_avg_pool2d to (OH, OW) = (H / r, W / r) (integer division) of a
  * channels-last hook (strides sb, 1, sy, sx; C % 8 == 0) -> (B, OH, OW, C) fp16, fp32 accumulation.  Output row o averages source rows
  * [floor(o H / OH), ceil((o + 1) H / OH)), columns likewise: the r x r window where r divides the size, otherwise longer windows that may
