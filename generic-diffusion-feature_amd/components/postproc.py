@@ -8,6 +8,8 @@ the hot path:
                      nearest neighbours of N source points among the load-size target pixels, without either load-size map (csrc/corres.hip)
   PixelClassifierEnsemble / predict_labels    scarce_segmentation/segmentation/pixel_classifier.py:14-36, 70-107   the label-scarce evaluator's
                      second step: an ensemble of per-pixel MLPs, majority vote and Jensen-Shannon uncertainty (csrc/pixcls.hip)
+  AggregationHead    correspondence/correspondence/aggregation_network.py:20-22, 97-100   the correspondence evaluator's trained head: the fp32
+                     3 x 3 output convolution on the aggregated map (csrc/agghead.hip)
   avg_pool           components/feature_extractor.py:51-53   `feature_resize` (adaptive_avg_pool2d to (H/r, W/r))
   aggregate_maps     components/attention.py:238-244, 141-161 + diffusion_feature.py:492-500   aggregated `attn` feature
 
@@ -48,6 +50,9 @@ _SIG["gdf_pixcls_destroy"] = (None, [C.c_void_p])
 _SIG["gdf_pixcls_workspace"] = (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int])
 _SIG["gdf_pixcls_predict"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.c_void_p])
+_SIG["gdf_agghead_create"] = (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])
+_SIG["gdf_agghead_destroy"] = (None, [C.c_void_p])
+_SIG["gdf_agghead_forward"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])
 _lib = None
 
 
@@ -374,6 +379,101 @@ def predict_labels(models, features, size):
         features = features.cuda()
     labels, top_k = ens.predict(features, size)
     return labels.cpu(), top_k
+
+
+def _head_conv(conv):
+    """an nn.Conv2d -> (weight, bias); anything but the reference's 3 x 3, stride 1, padding 1 convolution is refused"""
+    want = dict(kernel_size=(3, 3), stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1)
+    for k, v in want.items():
+        got = getattr(conv, k)
+        if (tuple(got) if isinstance(got, (tuple, list)) else got) != v:
+            raise ValueError(f"AggregationHead: the convolution has {k} = {got}, the head is a 3 x 3 convolution with stride 1, padding 1, "
+                             "no dilation and no groups")
+    if getattr(conv, "padding_mode", "zeros") != "zeros":
+        raise ValueError(f"AggregationHead: padding_mode = {conv.padding_mode!r}, the head pads with zeros")
+    return conv.weight, conv.bias
+
+
+def aggregation_head_params(source):
+    """-> (weight (Cout, Cin, 3, 3), bias (Cout) or None) as fp32 CPU tensors.  source: the reference's AggregationNetwork (its `.out`), an
+    nn.Conv2d, a weight tensor, a state dict holding `out.weight` (and `out.bias`), with or without the `module.` prefix, or the checkpoint
+    task-corres.py saves ({"aggregation_network": state dict, ...})."""
+    bias = None
+    if isinstance(source, torch.nn.Conv2d):
+        weight, bias = _head_conv(source)
+    elif isinstance(source, torch.nn.Module):
+        if not isinstance(getattr(source, "out", None), torch.nn.Conv2d):
+            raise ValueError("AggregationHead: the module has no `out` convolution")
+        weight, bias = _head_conv(source.out)
+    elif isinstance(source, dict):
+        sd = source.get("aggregation_network", source)
+        if not isinstance(sd, dict):
+            raise ValueError("AggregationHead: `aggregation_network` is not a state dict")
+        sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+        if "out.weight" not in sd:
+            raise ValueError("AggregationHead: not an aggregation-network state dict: no out.weight")
+        weight, bias = sd["out.weight"], sd.get("out.bias")
+    elif torch.is_tensor(source):
+        weight = source
+    else:
+        raise ValueError("AggregationHead: source is an aggregation network, an nn.Conv2d, a weight tensor, a state dict or a checkpoint")
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[0] < 1 or weight.shape[1] < 1:
+        raise ValueError(f"AggregationHead: the weight is (Cout, Cin, 3, 3), not {tuple(weight.shape)}")
+    weight = weight.detach().to("cpu", torch.float32).contiguous()
+    if bias is not None:
+        bias = bias.detach().to("cpu", torch.float32).contiguous()
+        if tuple(bias.shape) != (weight.shape[0],):
+            raise ValueError("AggregationHead: the bias is (Cout,)")
+    return weight, bias
+
+
+class AggregationHead:
+    """The reference AggregationNetwork's output convolution (x.type(torch.float32); self.out(x)) as one device op: (B, Cin, H, W) or the
+    reference's unbatched (Cin, H, W), fp16 or fp32 with any strides -> (B, Cout, H, W) / (Cout, H, W) fp32.  source: see aggregation_head_params."""
+
+    def __init__(self, source):
+        self.weight, self.bias = aggregation_head_params(source)
+        self.Cout, self.Cin = int(self.weight.shape[0]), int(self.weight.shape[1])
+        self._handles = {}
+
+    def _handle(self, dev):
+        """gdf_agghead of this head on `dev` (packed and uploaded on first use there)"""
+        key = torch.device(dev).index or 0
+        if key not in self._handles:
+            h = C.c_void_p()
+            with torch.cuda.device(dev):
+                native._check(_L().gdf_agghead_create(self.Cin, self.Cout, C.c_void_p(self.weight.data_ptr()),
+                                                      C.c_void_p(self.bias.data_ptr()) if self.bias is not None else None, C.byref(h)),
+                              "agghead_create")
+            self._handles[key] = h
+        return self._handles[key]
+
+    def __del__(self):
+        for h in getattr(self, "_handles", {}).values():
+            try:
+                _lib.gdf_agghead_destroy(h)
+            except Exception:
+                pass
+
+    def __call__(self, x):
+        if x.dim() == 3:
+            return self(x[None])[0]
+        if x.dim() != 4 or x.shape[1] != self.Cin:
+            raise ValueError(f"AggregationHead: x is (B, {self.Cin}, H, W) or ({self.Cin}, H, W), not {tuple(x.shape)}")
+        if x.shape[2] < 1 or x.shape[3] < 1:
+            raise ValueError("AggregationHead: H and W >= 1")
+        if not x.is_cuda:
+            return F.conv2d(x.float(), self.weight, self.bias, padding=1)
+        dev = x.device
+        x = x if x.dtype in (torch.float16, torch.float32) else x.float()
+        B, _, H, W = x.shape
+        with torch.cuda.device(dev):
+            out = torch.empty(B, self.Cout, H, W, dtype=torch.float32, device=dev)
+            if B > 0:
+                src = _agg_src(x)
+                native._check(_L().gdf_agghead_forward(self._handle(dev), C.addressof(src), B, C.c_void_p(out.data_ptr()), _stream(dev)),
+                              "agghead_forward")
+        return out
 
 
 def avg_pool(feat, r):

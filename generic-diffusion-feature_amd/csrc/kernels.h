@@ -359,6 +359,18 @@ void pixcls_destroy(PixCls* pc);
 size_t pixcls_workspace(const PixCls* pc, long P);
 hipError_t launch_pixcls(const PixCls* pc, const AggSrc& x, int B, long long* labels, float* js, unsigned char* model_labels, float* logits,
                          void* workspace, hipStream_t s);
+// the output convolution of the correspondence evaluator's aggregation network (agghead.hip): 3 x 3, stride 1, zero padding 1, fp32 result, on a
+// logical (B, Cin, H, W) map.  agghead_create packs the host fp32 OIHW weights (Cout, Cin, 3, 3) as row-scaled fp16 (hi, lo) pairs in MFMA fragment
+// order, one 32-row block at a time, and uploads them with 1 / scale and the bias (null: zeros) per output channel; the packed image is addressed
+// with 64-bit offsets (7360 -> 3680 is close to 1 GB).  launch_agghead: out (B, Cout, H, W) fp32 contiguous; B * H * W < 2^31.
+struct AggHead {
+  int Cin, Cout, nkt, nrb;
+  void* dev;
+  const void* w; const float *inv_s, *bias;
+};
+hipError_t agghead_create(int Cin, int Cout, const float* W, const float* bias, AggHead** out);
+void agghead_destroy(AggHead* h);
+hipError_t launch_agghead(const AggHead* h, const AggSrc& x, int B, float* out, hipStream_t s);
 // adaptive_avg_pool2d to (H/r, W/r) of a channels-last hook (B,C,H,W; strides sb, 1, sy, sx) -> (B, H/r, W/r, C) fp16: the r x r mean
 // where r divides H and W, ATen's longer windows [floor(o H / OH), ceil((o + 1) H / OH)) otherwise
 hipError_t launch_avg_pool(const half_t* src, long sb, long sy, long sx, int B, int C, int H, int W, int r, half_t* out, hipStream_t s);

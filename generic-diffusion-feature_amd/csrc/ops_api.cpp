@@ -541,6 +541,34 @@ int gdf_pixcls_predict(gdf_pixcls h, const gdf_agg_src* x, int B, long long* lab
   const AggSrc a{x->ptr, x->f32, x->sb, x->sc, x->sy, x->sx, x->C, x->H, x->W, 0};
   return fin(launch_pixcls(pc, a, B, labels, js, model_labels, logits, workspace, (hipStream_t)stream), "gdf_pixcls_predict");
 }
+int gdf_agghead_create(int Cin, int Cout, const float* W, const float* bias, gdf_agghead* out) {
+  auto bad = [](const char* msg) { set_error(std::string("gdf_agghead_create: ") + msg); return GDF_ERR_ARG; };
+  if (out) *out = nullptr;
+  if (!W || !out) return bad("null pointer");
+  if (Cin < 1 || Cout < 1) return bad("Cin and Cout >= 1");
+  const size_t n = (size_t)Cout * Cin * 9;
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(W[i])) return bad("a weight is not finite");
+  for (int i = 0; bias && i < Cout; ++i)
+    if (!std::isfinite(bias[i])) return bad("a bias is not finite");
+  AggHead* h = nullptr;
+  const int rc = fin(agghead_create(Cin, Cout, W, bias, &h), "gdf_agghead_create");
+  if (rc == GDF_OK) *out = (gdf_agghead)h;
+  return rc;
+}
+void gdf_agghead_destroy(gdf_agghead h) { agghead_destroy((AggHead*)h); }
+int gdf_agghead_forward(gdf_agghead h, const gdf_agg_src* x, int B, float* out, void* stream) {
+  auto bad = [](const char* msg) { set_error(std::string("gdf_agghead_forward: ") + msg); return GDF_ERR_ARG; };
+  if (!h || !x || !out) return bad("null pointer");
+  if (!x->ptr) return bad("null feature pointer");
+  const AggHead* ah = (const AggHead*)h;
+  if (B < 0 || x->H < 1 || x->W < 1) return bad("B >= 0, H and W >= 1");
+  if (x->C != ah->Cin) return bad("the map's C differs from the head's Cin");
+  if ((long long)std::max(B, 1) * x->H * x->W >= (1ll << 31)) return bad("B * H * W >= 2^31; split the batch");
+  if (B == 0) return GDF_OK;
+  const AggSrc a{x->ptr, x->f32, x->sb, x->sc, x->sy, x->sx, x->C, x->H, x->W, 0};
+  return fin(launch_agghead(ah, a, B, out, (hipStream_t)stream), "gdf_agghead_forward");
+}
 int gdf_op_avg_pool(const void* src, long sb, long sy, long sx, int B, int C, int H, int W, int r, void* out, void* stream) {
   return fin(launch_avg_pool((const half_t*)src, sb, sy, sx, B, C, H, W, r, (half_t*)out, (hipStream_t)stream), "avg_pool");
 }

@@ -377,6 +377,30 @@ size_t gdf_pixcls_workspace(gdf_pixcls h, int B, int H, int W);
 int gdf_pixcls_predict(gdf_pixcls h, const gdf_agg_src* x, int B, long long* labels /* (B, H, W) */, float* js /* (B, H, W) or NULL */,
                        uint8_t* model_labels /* (M, B, H, W) or NULL */, float* logits /* (M, B H W, K) or NULL */, void* workspace,
                        size_t workspace_bytes, void* stream);
+/* The trained head of the correspondence evaluator on an aggregated map (correspondence/correspondence/aggregation_network.py:20-22, 97-100:
+ * self.out = nn.Conv2d(dim, out_dim, kernel_size=3, stride=1, padding=1, bias=False); x = x.type(torch.float32); x = self.out(x); run on the
+ * source and on the target map of every pair, task-corres.py:60-67):
+ *   out[b, co, y, x] = bias[co] + sum_{ci, dy, dx} W[co, ci, dy, dx] in[b, ci, y + dy - 1, x + dx - 1],  zeros outside the image
+ * (torch's cross-correlation: stride 1, padding 1, no dilation, no groups) as an implicit GEMM on the MFMA units (csrc/agghead.hip).
+ *   gdf_agghead_create   host fp32 W (Cout, Cin, 3, 3) as nn.Conv2d stores it, bias (Cout) or NULL.  Uploads once: every weight becomes an fp16
+ *                        (hi, lo) pair, each output channel's 9 Cin row scaled by a power of two that the fp32 epilogue undoes (the pair carries
+ *                        22 bits of every weight), in MFMA fragment order, 8 bytes per weight (Cin padded to 32, Cout to 32) addressed with 64-bit
+ *                        offsets: 7360 -> 3680 takes 975 MB of device memory.  Synchronous; the arrays may be freed afterwards.  An all-zero row
+ *                        yields that row's bias.  A null W or out, Cin or Cout below 1, a weight or bias that is not finite: GDF_ERR_ARG.
+ *   gdf_agghead_forward  x: a logical (B, Cin, H, W) tensor, fp16 (f32 = 0) or fp32, element strides sb/sc/sy/sx, read only, `coff` ignored.  sx == 1
+ *                        (NCHW, what gdf_op_aggregate writes) is read with lanes along x; sc == 1 with C a multiple of 8 (fp32: 4) and 16-byte
+ *                        aligned pixels (a channels-last hook; the pixel may be longer than C) with 16-byte loads along C; any other strides are
+ *                        correct, not fast.  An fp16 map is multiplied as given with the hi and lo halves of W; an fp32 map is split into an fp16
+ *                        (hi, lo) pair as it is staged (hi hi + hi lo + lo hi; it must lie in the fp16 range).  fp32 accumulation, folded into a
+ *                        second fp32 total after every 32 input channels.  The padding is zeros the kernel writes: nothing beside the map is read.
+ *       out              (B, Cout, H, W) fp32 contiguous, as the reference returns it
+ * One launch, stream-ordered, no atomics, no workspace, fixed summation order; every workgroup's tile lies inside one image, so an image's bits depend
+ * neither on B nor on its place in the batch, and the same inputs give the same bits on any stream.  A null pointer (handle, x, x->ptr, out), H or W
+ * below 1, B < 0, x->C != Cin, B * H * W >= 2^31: GDF_ERR_ARG before any launch.  B == 0 is a successful no-op. */
+typedef struct gdf_agghead_s* gdf_agghead;
+int gdf_agghead_create(int Cin, int Cout, const float* W /* host, (Cout, Cin, 3, 3) */, const float* bias /* host (Cout) or NULL */, gdf_agghead* out);
+void gdf_agghead_destroy(gdf_agghead h);
+int gdf_agghead_forward(gdf_agghead h, const gdf_agg_src* x, int B, float* out /* (B, Cout, H, W) */, void* stream);
 /* `feature_resize` (components/feature_extractor.py:51-53): adaptive_avg_pool2d to (OH, OW) = (H / r, W / r) (integer division) of a
  * channels-last hook (strides sb, 1, sy, sx; C % 8 == 0) -> (B, OH, OW, C) fp16, fp32 accumulation.  Output row o averages source rows
  * [floor(o H / OH), ceil((o + 1) H / OH)), columns likewise: the r x r window where r divides the size, otherwise longer windows that may
