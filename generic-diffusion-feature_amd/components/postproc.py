@@ -6,6 +6,8 @@ the hot path:
                      F.interpolate(v, size, mode='bilinear') of every layer + torch.cat(dim=1), one launch per 16 layers
   nn_match / find_nn_source_correspondences   correspondence/correspondence/correspondence_utils.py:113-138   the evaluators' second step:
                      nearest neighbours of N source points among the load-size target pixels, without either load-size map (csrc/corres.hip)
+  clip_loss / compute_clip_loss   correspondence/task-corres.py:70-80   the evaluator's loss on two hyperfeature maps, forward and backward,
+                     without either P x P similarity matrix (csrc/cliploss.hip); a torch.autograd.Function on device tensors
   PixelClassifierEnsemble / predict_labels    scarce_segmentation/segmentation/pixel_classifier.py:14-36, 70-107   the label-scarce evaluator's
                      second step: an ensemble of per-pixel MLPs, majority vote and Jensen-Shannon uncertainty (csrc/pixcls.hip)
   AggregationHead    correspondence/correspondence/aggregation_network.py:20-22, 97-100   the correspondence evaluator's trained head: the fp32
@@ -45,6 +47,11 @@ AGG_MAX = 16                                             # sources of one gdf_op
 _SIG["gdf_op_nn_match_workspace"] = (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int])
 _SIG["gdf_op_nn_match"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p])
+_SIG["gdf_op_clip_loss_workspace"] = (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int])
+_SIG["gdf_op_clip_loss"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.c_void_p])
+_SIG["gdf_op_clip_loss_backward"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
 _SIG["gdf_pixcls_create"] = (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 6 + [C.POINTER(C.c_void_p)])
 _SIG["gdf_pixcls_destroy"] = (None, [C.c_void_p])
 _SIG["gdf_pixcls_workspace"] = (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int])
@@ -203,6 +210,129 @@ def find_nn_source_correspondences(img1_feats, img2_feats, source_points, output
     B = img1_feats.shape[0]
     points2, _ = nn_match(img1_feats, img2_feats, torch.from_numpy(idx)[None].expand(B, -1, -1), (LH, LW))
     return torch.from_numpy(source_points), points2[0]
+
+
+CLIP_SCALE = 1 / 0.07                                   # exp(logit_scale) of the reference's AggregationNetwork (aggregation_network.py:25)
+
+
+class _ClipLoss(torch.autograd.Function):
+    """gdf_op_clip_loss / gdf_op_clip_loss_backward on device maps: the forward leaves the backward's state in a workspace tensor that the graph
+    keeps; grad_output goes down as the device (B,) tensor, nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, feats1, feats2, src, tgt, scale):
+        dev = feats1.device
+        B, N = src.shape
+        with torch.cuda.device(dev):
+            L = _L()
+            loss = torch.empty(B, dtype=torch.float32, device=dev)
+            P1, P2 = feats1.shape[2] * feats1.shape[3], feats2.shape[2] * feats2.shape[3]
+            nbytes = L.gdf_op_clip_loss_workspace(B, N, feats1.shape[1], P1, P2)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            s1, s2 = _agg_src(feats1), _agg_src(feats2)
+            native._check(L.gdf_op_clip_loss(C.addressof(s1), C.addressof(s2), B, C.c_void_p(src.data_ptr()), C.c_void_p(tgt.data_ptr()), N, scale,
+                                             C.c_void_p(loss.data_ptr()), None, C.c_void_p(ws.data_ptr()), nbytes, _stream(dev)), "clip_loss")
+        ctx.save_for_backward(feats1, feats2, src, tgt, ws)
+        ctx.scale = scale
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        feats1, feats2, src, tgt, ws = ctx.saved_tensors
+        dev = feats1.device
+        B, N = src.shape
+        need = ctx.needs_input_grad[:2]
+        with torch.cuda.device(dev):
+            grad = grad.to(torch.float32).contiguous()
+            g = [torch.empty(v.shape, dtype=torch.float32, device=dev) if n else None for v, n in zip((feats1, feats2), need)]
+            if any(need):
+                s1, s2 = _agg_src(feats1), _agg_src(feats2)
+                L = _L()
+                native._check(L.gdf_op_clip_loss_backward(
+                    C.addressof(s1), C.addressof(s2), B, C.c_void_p(src.data_ptr()), C.c_void_p(tgt.data_ptr()), N, ctx.scale,
+                    C.c_void_p(grad.data_ptr()), *(C.c_void_p(t.data_ptr()) if t is not None else None for t in g), C.c_void_p(ws.data_ptr()),
+                    ws.numel(), _stream(dev)), "clip_loss_backward")
+        g = [t if t is None or t.dtype == v.dtype else t.to(v.dtype) for t, v in zip(g, (feats1, feats2))]
+        return g[0], g[1], None, None, None
+
+
+def clip_loss(feats1, feats2, src_idx, tgt_idx, scale=CLIP_SCALE):
+    """feats1 (B, C, h1, w1), feats2 (B, C, h2, w2), fp16 or fp32 with any strides; src_idx, tgt_idx int64 (B, N) or, for B = 1, (N,): flat pixel
+    indices y w + x into feats1 and feats2 -> the loss of every pair, (B,) fp32.
+    The reference's compute_clip_loss per pair: with both maps L2-normalised per pixel, scale * (rows src_idx of feats1) @ feats2^T against the labels
+    tgt_idx and the same with the roles swapped, cross_entropy of each, the mean of the two.  Device tensors: gdf_op_clip_loss as an autograd
+    Function (neither P x P matrix is built; gradients come back as fp32 computed, cast to the map's dtype); host tensors: that torch chain in fp32
+    on the needed rows, differentiable by torch."""
+    if feats1.dim() != 4 or feats2.dim() != 4 or feats1.shape[0] != feats2.shape[0] or feats1.shape[1] != feats2.shape[1]:
+        raise ValueError("feats1 and feats2 are (B, C, h, w) tensors with the same B and C")
+    if min(feats1.shape[1:]) < 1 or min(feats2.shape[1:]) < 1:
+        raise ValueError("C, h and w >= 1")
+    scale = float(scale)
+    if not (scale > 0 and math.isfinite(scale)):
+        raise ValueError("scale is positive and finite")
+    B = feats1.shape[0]
+    idx = []
+    for v in (src_idx, tgt_idx):
+        v = torch.as_tensor(v)
+        if v.is_floating_point() or v.dtype == torch.bool:
+            raise ValueError("src_idx and tgt_idx are integer tensors")
+        if v.dim() == 1 and B == 1:
+            v = v[None]
+        idx.append(v)
+    if idx[0].dim() != 2 or idx[0].shape != idx[1].shape or idx[0].shape[0] != B or idx[0].shape[1] < 1:
+        raise ValueError("src_idx and tgt_idx are (B, N), or (N,) for B = 1, with N >= 1")
+    dev = feats1.device
+    if feats2.device != dev:
+        raise ValueError("feats1 and feats2 are on the same device")
+    src, tgt = (v.to(device=dev, dtype=torch.int64).contiguous() for v in idx)
+    if not feats1.is_cuda:
+        k1, k2 = (v.float().flatten(2).permute(0, 2, 1) for v in (feats1, feats2))
+        k1 = k1 / torch.linalg.norm(k1, dim=-1)[:, :, None]
+        k2 = k2 / torch.linalg.norm(k2, dim=-1)[:, :, None]
+        out = []
+        for b in range(B):
+            l1 = F.cross_entropy(scale * (k1[b, src[b]] @ k2[b].T), tgt[b])
+            l2 = F.cross_entropy(scale * (k2[b, tgt[b]] @ k1[b].T), src[b])
+            out.append((l1 + l2) / 2)
+        return torch.stack(out) if out else torch.zeros(0)
+    feats1, feats2 = (v if v.dtype in (torch.float16, torch.float32) else v.float() for v in (feats1, feats2))
+    if B == 0:
+        return torch.zeros(0, dtype=torch.float32, device=dev)
+    return _ClipLoss.apply(feats1, feats2, src, tgt, scale)
+
+
+def points_to_idxs(points, output_size):
+    """The reference's formula (correspondence/correspondence/correspondence_utils.py:140-146) verbatim, in the points' own precision: (N, 2) (y, x)
+    -> output_size[1] * round(clip(y, 0, output_size[1] - 1)) + round(clip(x, 0, output_size[0] - 1)); np.round rounds half to even."""
+    points = np.asarray(points)
+    if points.ndim != 2 or points.shape[1] != 2 or points.shape[0] < 1:
+        raise ValueError("points is a numpy (N, 2) array of (y, x) with N >= 1")
+    points_y = np.clip(points[:, 0], 0, output_size[1] - 1)
+    points_x = np.clip(points[:, 1], 0, output_size[0] - 1)
+    return output_size[1] * np.round(points_y) + np.round(points_x)
+
+
+def compute_clip_loss(aggregation_network, img1_hyperfeats, img2_hyperfeats, source_points, target_points, output_size):
+    """The reference's function (correspondence/task-corres.py:70-80), same signature and return value: a 0-dim tensor.  B must be 1, as there.
+    aggregation_network: anything with a `logit_scale` (a tensor or a number), or None for log(1 / 0.07).  The points are numpy (N, 2) (y, x)
+    arrays in output-size coordinates; an index that leaves its map is a ValueError (the reference fails inside its gather)."""
+    if img1_hyperfeats.dim() != 4 or img2_hyperfeats.dim() != 4 or img1_hyperfeats.shape[0] != 1 or img2_hyperfeats.shape[0] != 1:
+        raise ValueError("compute_clip_loss takes (1, C, h, w) hyperfeatures")
+    output_size = (int(output_size), int(output_size)) if isinstance(output_size, int) else (int(output_size[0]), int(output_size[1]))
+    if aggregation_network is None:
+        scale = CLIP_SCALE
+    else:
+        ls = aggregation_network.logit_scale
+        scale = math.exp(float(ls.detach()) if isinstance(ls, torch.Tensor) else float(ls))
+    idx = []
+    for pts, v in ((source_points, img1_hyperfeats), (target_points, img2_hyperfeats)):
+        i = points_to_idxs(pts, output_size)
+        if not np.isfinite(i).all() or (i < 0).any() or (i >= v.shape[2] * v.shape[3]).any():
+            raise ValueError("a point's index leaves its %d x %d map (output_size %r)" % (v.shape[2], v.shape[3], output_size))
+        idx.append(torch.from_numpy(i.astype(np.int64)))
+    if idx[0].shape != idx[1].shape:
+        raise ValueError("source_points and target_points have the same length")
+    return clip_loss(img1_hyperfeats, img2_hyperfeats, idx[0], idx[1], scale)[0]
 
 
 _PC_KEYS = ("0.weight", "0.bias", "2.weight", "2.bias", "2.running_mean", "2.running_var", "3.weight", "3.bias", "5.weight", "5.bias",

@@ -342,6 +342,18 @@ enum { NN_MAXQ = 24, NN_FINE_BLOCKS = 1024 };
 size_t nn_match_workspace(int B, int N, int C, int h2, int w2);
 hipError_t launch_nn_match(const AggSrc& f1, const AggSrc& f2, int B, const float* points, int N, int LH, int LW, long long* out_yx,
                            float* out_score, void* workspace, hipStream_t s);
+// compute_clip_loss of the correspondence evaluator (cliploss.hip): the symmetric cross-entropy of scale * cosine similarity between N source pixels of
+// f1 and N target pixels of f2 (flat indices (B, N) int64 on the device), without either P x P similarity matrix, and its gradient with respect to
+// both maps.  loss (B) fp32, terms (B, 2, N) fp32 or null.  The forward leaves the backward's state (cos, inverse norms, log-sum-exps, validity) in
+// the workspace (clip_loss_workspace bytes, 16-byte aligned); the backward takes the same arguments and that workspace, grad_loss (B) on the device,
+// and writes grad_f1 / grad_f2 (B, C, H, W) fp32 contiguous (either may be null).  Queries go in chunks of CL_MAXQ; a map's pixels are split into at
+// most CL_RANGES ranges whose partial sums the workspace holds.
+enum { CL_MAXQ = 24, CL_RANGES = 16 };
+size_t clip_loss_workspace(int B, int N, int C, int P1, int P2);
+hipError_t launch_clip_loss(const AggSrc& f1, const AggSrc& f2, int B, const long long* src_idx, const long long* tgt_idx, int N, float scale,
+                            float* loss, float* terms, void* workspace, hipStream_t s);
+hipError_t launch_clip_loss_backward(const AggSrc& f1, const AggSrc& f2, int B, const long long* src_idx, const long long* tgt_idx, int N,
+                                     float scale, const float* grad_loss, float* grad_f1, float* grad_f2, void* workspace, hipStream_t s);
 // predict_labels of the label-scarce segmentation evaluator (pixcls.hip): an ensemble of M BatchNorm-folded per-pixel MLPs C -> h1 -> h2 -> K over
 // every pixel of a logical (B, C, H, W) map, then the per-pixel vote.  pixcls_create packs W1 and W2 as scaled fp16 (hi, lo) pairs in MFMA fragment order
 // and uploads everything once (host fp32 arrays: W1 (M, h1, C), b1 (M, h1), W2 (M, h2, h1), b2 (M, h2), W3 (M, K, h2), b3 (M, K)); widths are

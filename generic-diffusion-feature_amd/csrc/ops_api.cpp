@@ -503,6 +503,47 @@ int gdf_op_nn_match(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const f
   const AggSrc b{f2->ptr, f2->f32, f2->sb, f2->sc, f2->sy, f2->sx, f2->C, f2->H, f2->W, 0};
   return fin(launch_nn_match(a, b, B, points, N, LH, LW, out_yx, out_score, workspace, (hipStream_t)stream), "gdf_op_nn_match");
 }
+size_t gdf_op_clip_loss_workspace(int B, int N, int C, int P1, int P2) {
+  return clip_loss_workspace(std::max(B, 1), std::max(N, 1), std::max(C, 1), std::max(P1, 1), std::max(P2, 1));
+}
+// the checks the forward and the backward share; 0 = go on, -1 = B == 0 (a successful no-op)
+static int clip_loss_args(const char* what, const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const void* src_idx, const void* tgt_idx, int N,
+                          float scale, const void* workspace, size_t workspace_bytes) {
+  auto bad = [&](const char* msg) { set_error(std::string(what) + ": " + msg); return GDF_ERR_ARG; };
+  auto big = [&](const char* msg) { set_error(std::string(what) + ": " + msg); return GDF_ERR_UNSUPPORTED; };
+  if (!f1 || !f2 || !src_idx || !tgt_idx || !workspace) return bad("null pointer");
+  if (!f1->ptr || !f2->ptr) return bad("null feature pointer");
+  if (B < 0 || N < 1) return bad("B >= 0 and N >= 1");
+  if (f1->C < 1 || f1->H < 1 || f1->W < 1 || f2->C < 1 || f2->H < 1 || f2->W < 1) return bad("C, H and W >= 1");
+  if (f1->C != f2->C) return bad("the two maps differ in C");
+  if (!(scale > 0.f) || !std::isfinite(scale)) return bad("the scale must be positive and finite");
+  if ((uintptr_t)workspace & 15) return bad("the workspace must be 16-byte aligned");
+  if (B > 65535) return big("B > 65535; split the batch");
+  if ((long long)f1->H * f1->W >= (1ll << 30) || (long long)f2->H * f2->W >= (1ll << 30)) return big("H * W >= 2^30 pixels (32-bit flat indices)");
+  if (workspace_bytes < gdf_op_clip_loss_workspace(B, N, f1->C, f1->H * f1->W, f2->H * f2->W))
+    return bad("workspace smaller than gdf_op_clip_loss_workspace says");
+  return B == 0 ? -1 : 0;
+}
+int gdf_op_clip_loss(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const long long* src_idx, const long long* tgt_idx, int N, float scale,
+                     float* loss, float* terms, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!loss) { set_error("gdf_op_clip_loss: null pointer"); return GDF_ERR_ARG; }
+  const int rc = clip_loss_args("gdf_op_clip_loss", f1, f2, B, src_idx, tgt_idx, N, scale, workspace, workspace_bytes);
+  if (rc) return rc < 0 ? GDF_OK : rc;
+  const AggSrc a{f1->ptr, f1->f32, f1->sb, f1->sc, f1->sy, f1->sx, f1->C, f1->H, f1->W, 0};
+  const AggSrc b{f2->ptr, f2->f32, f2->sb, f2->sc, f2->sy, f2->sx, f2->C, f2->H, f2->W, 0};
+  return fin(launch_clip_loss(a, b, B, src_idx, tgt_idx, N, scale, loss, terms, workspace, (hipStream_t)stream), "gdf_op_clip_loss");
+}
+int gdf_op_clip_loss_backward(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const long long* src_idx, const long long* tgt_idx, int N,
+                              float scale, const float* grad_loss, float* grad_f1, float* grad_f2, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+  if (!grad_loss) { set_error("gdf_op_clip_loss_backward: null pointer"); return GDF_ERR_ARG; }
+  const int rc = clip_loss_args("gdf_op_clip_loss_backward", f1, f2, B, src_idx, tgt_idx, N, scale, workspace, workspace_bytes);
+  if (rc) return rc < 0 ? GDF_OK : rc;
+  const AggSrc a{f1->ptr, f1->f32, f1->sb, f1->sc, f1->sy, f1->sx, f1->C, f1->H, f1->W, 0};
+  const AggSrc b{f2->ptr, f2->f32, f2->sb, f2->sc, f2->sy, f2->sx, f2->C, f2->H, f2->W, 0};
+  return fin(launch_clip_loss_backward(a, b, B, src_idx, tgt_idx, N, scale, grad_loss, grad_f1, grad_f2, workspace, (hipStream_t)stream),
+             "gdf_op_clip_loss_backward");
+}
 int gdf_pixcls_create(int C, int M, int h1, int h2, int K, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
                       const float* b3, gdf_pixcls* out) {
   auto bad = [](const char* msg) { set_error(std::string("gdf_pixcls_create: ") + msg); return GDF_ERR_ARG; };

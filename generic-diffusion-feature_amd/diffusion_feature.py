@@ -630,6 +630,23 @@ class FeatureExtractor(nn.Module):
         from components.postproc import nn_match
         return nn_match(feats1, feats2, source_points, load_size)
 
+    def correspondence_loss(self, feats1, feats2, source_points, target_points, scale=None):
+        """The correspondence evaluator's loss (reference correspondence/task-corres.py:70-80, compute_clip_loss) on two maps from hyperfeature()
+        or aggregate(): the symmetric cross-entropy of scale * cosine similarity between the N source pixels of feats1 and the N target pixels of
+        feats2 -> (B,) fp32, differentiable with respect to both maps.  source_points / target_points: (B, N, 2) or, for B = 1, (N, 2) (y, x) in
+        the maps' own pixel coordinates, clipped and rounded half to even as the reference's points_to_idxs does; scale: exp(logit_scale),
+        None = 1 / 0.07.  Device tensors: gdf_op_clip_loss, neither similarity matrix is built (components/postproc.py clip_loss)."""
+        import numpy as np
+        from components.postproc import CLIP_SCALE, clip_loss
+        idx = []
+        for pts, v in ((source_points, feats1), (target_points, feats2)):
+            p = np.asarray(pts.detach().cpu() if isinstance(pts, torch.Tensor) else pts)
+            if p.ndim < 2 or p.shape[-1] != 2:
+                raise ValueError("points are (B, N, 2) or (N, 2) arrays of (y, x)")
+            h, w = v.shape[2], v.shape[3]
+            idx.append(torch.from_numpy((w * np.round(np.clip(p[..., 0], 0, h - 1)) + np.round(np.clip(p[..., 1], 0, w - 1))).astype(np.int64)))
+        return clip_loss(feats1, feats2, idx[0], idx[1], CLIP_SCALE if scale is None else scale)
+
     def segment(self, ensemble, feats=None, size=256):
         """The label-scarce segmentation evaluator on a feature dict (reference scarce_segmentation/task-pixel.py:85-103): aggregate(feats, size)
         (bilinear) and the pixel-classifier ensemble's vote on the result -> (labels int64 (B, OH, OW), top_k (B,)), on the device.

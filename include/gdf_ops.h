@@ -343,6 +343,40 @@ int gdf_op_aggregate(const gdf_agg_src* srcs, int n, int B, void* out, int out_f
 size_t gdf_op_nn_match_workspace(int B, int N, int C, int h2, int w2);
 int gdf_op_nn_match(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const float* points /* device, (B, N, 2) */, int N, int LH, int LW,
                     long long* out_yx /* (B, N, 2) */, float* out_score /* (B, N) */, void* workspace, size_t workspace_bytes, void* stream);
+/* The correspondence evaluator's loss on two hyperfeature maps (correspondence/task-corres.py:70-80, compute_clip_loss, called per image pair from
+ * validate() :103 and per step from train() :159) and its gradient with respect to both maps — computed WITHOUT either P x P similarity matrix
+ * (csrc/cliploss.hip).  With a^_p = f1[:, p] / ||f1[:, p]|| and b^_p likewise for f2 (pixel p = y W + x):
+ *     direction 1   z[n, p] = scale <a^_src[n], b^_p>,   term1[n] = logsumexp_p z[n, p] - z[n, tgt[n]]
+ *     direction 2   the roles swapped: queries b^_tgt[n], keys a^_p, labels src[n]
+ *     loss = (mean_n term1 + mean_n term2) / 2
+ *   f1, f2     logical (B, C, H, W) tensors, fp16 (f32 = 0) or fp32 independently, with element strides sb/sc/sy/sx, read only; the two C must
+ *              agree, the grids need not; `coff` is ignored.  A map with sx == 1 (NCHW, what gdf_agghead_forward and gdf_op_aggregate write) is read
+ *              with lanes along the pixels; one with sc == 1, C a multiple of 8 (fp32: 4) and 16-byte aligned pixels with 16-byte loads along C;
+ *              any other strides are correct, not fast.
+ *   src_idx, tgt_idx   device, (B, N) int64: flat pixel indices into f1 (P1 = H1 W1 pixels) and f2 (P2).  Duplicates are allowed.
+ *   scale      exp(logit_scale), 1 / 0.07 in the reference; positive and finite.  The log-sum-exp subtracts the exact maximum.
+ *   loss       (B) fp32, one value per pair.  terms, if not null: (B, 2, N) fp32, the 2 N cross-entropy terms before the means, direction 1 first.
+ *   backward   grad_loss: device, (B) fp32, the upstream gradient.  grad_f1 (B, C, H1, W1) and grad_f2 (B, C, H2, W2): fp32 contiguous, every
+ *              element written; either may be null and the other's bits do not depend on that.  With G[n, p] = grad_loss scale / (2 N)
+ *              (softmax_p(z[n, .])[p] - [p == label_n]) every key pixel receives (sum_n G[n, p] q^_n - k^_p sum_n G[n, p] cos[n, p]) / ||k_p|| and
+ *              every query pixel (sum_p G[n, p] k^_p - q^_n sum_p G[n, p] cos[n, p]) / ||q_n|| on top, duplicates accumulating in n order.
+ *   workspace  gdf_op_clip_loss_workspace(B, N, C, P1, P2) bytes, 16-byte aligned, caller-owned.  After the forward call it holds the state of the
+ *              backward (cos of both directions, the inverse norms, the log-sum-exps, a validity flag per pair) in an opaque layout, and the space
+ *              for the backward's partial sums; the backward requires the same arguments and that workspace untouched, and may be called
+ *              repeatedly.  Any N: queries are processed 24 at a time.
+ *   invalid pairs   an index outside its map, or a pixel of zero or non-finite norm anywhere in either map of a pair (the reference's 0 / 0):
+ *              that pair's loss, terms and gradients are all NaN, nothing outside the maps is read or written, other pairs are unaffected.
+ * fp32 throughout, no atomics, every reduction in a fixed order: the same inputs give the same bits on any stream and at any batch position.
+ * Stream-ordered, nothing read back, no allocation.  A null required pointer, C, H, W or N below 1, differing C, B < 0, a scale that is not
+ * positive and finite, a misaligned or too small workspace: GDF_ERR_ARG before any launch.  B > 65535 or H * W >= 2^30: GDF_ERR_UNSUPPORTED.
+ * B == 0 is a successful no-op. */
+size_t gdf_op_clip_loss_workspace(int B, int N, int C, int P1, int P2);
+int gdf_op_clip_loss(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const long long* src_idx, const long long* tgt_idx /* device, (B, N) */,
+                     int N, float scale, float* loss /* (B) */, float* terms /* (B, 2, N) or NULL */, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int gdf_op_clip_loss_backward(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const long long* src_idx, const long long* tgt_idx, int N,
+                              float scale, const float* grad_loss /* device, (B) */, float* grad_f1 /* (B, C, H1, W1) fp32 contiguous, or NULL */,
+                              float* grad_f2 /* likewise, or NULL */, void* workspace, size_t workspace_bytes, void* stream);
 /* The label-scarce segmentation evaluator's second step on an aggregated map (scarce_segmentation/segmentation/pixel_classifier.py:70-107,
  * predict_labels): an ensemble of M per-pixel MLPs (pixel_classifier, :14-36) over every pixel, the per-pixel majority vote and the ensemble's
  * Jensen-Shannon uncertainty (csrc/pixcls.hip).  The networks are given BATCHNORM-FOLDED: eval-mode BatchNorm1d after ReLU is an
