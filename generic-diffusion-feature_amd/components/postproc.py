@@ -12,6 +12,10 @@ the hot path:
                      second step: an ensemble of per-pixel MLPs, majority vote and Jensen-Shannon uncertainty (csrc/pixcls.hip)
   AggregationHead    correspondence/correspondence/aggregation_network.py:20-22, 97-100   the correspondence evaluator's trained head: the fp32
                      3 x 3 output convolution on the aggregated map (csrc/agghead.hip)
+  TrainableAggregationHead   correspondence/task-corres.py:144-162 train() on aggregation_network.out   the same head as a torch.nn.Module whose
+                     forward is that device convolution and whose backward is the device weight gradient (csrc/aggwgrad.hip); updated weights
+                     are repacked on the device
+  rescale_points / compute_pck   correspondence/correspondence/correspondence_utils.py:53-59, 160-167   validate()'s two host helpers (numpy)
   avg_pool           components/feature_extractor.py:51-53   `feature_resize` (adaptive_avg_pool2d to (H/r, W/r))
   aggregate_maps     components/attention.py:238-244, 141-161 + diffusion_feature.py:492-500   aggregated `attn` feature
 
@@ -60,6 +64,10 @@ _SIG["gdf_pixcls_predict"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_voi
 _SIG["gdf_agghead_create"] = (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])
 _SIG["gdf_agghead_destroy"] = (None, [C.c_void_p])
 _SIG["gdf_agghead_forward"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])
+_SIG["gdf_agghead_create_device"] = (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])
+_SIG["gdf_agghead_update"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])
+_SIG["gdf_agghead_wgrad_workspace"] = (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int])
+_SIG["gdf_agghead_wgrad"] = (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
 _lib = None
 
 
@@ -604,6 +612,147 @@ class AggregationHead:
                 native._check(_L().gdf_agghead_forward(self._handle(dev), C.addressof(src), B, C.c_void_p(out.data_ptr()), _stream(dev)),
                               "agghead_forward")
         return out
+
+
+class _HeadConv(torch.autograd.Function):
+    """gdf_agghead_forward on a TrainableAggregationHead's handle; the backward is gdf_agghead_wgrad and returns the gradient of the weight.  The map
+    gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, weight, x, handle):
+        dev = x.device
+        B, _, H, W = x.shape
+        with torch.cuda.device(dev):
+            out = torch.empty(B, weight.shape[0], H, W, dtype=torch.float32, device=dev)
+            if B > 0:
+                src = _agg_src(x)
+                native._check(_L().gdf_agghead_forward(handle, C.addressof(src), B, C.c_void_p(out.data_ptr()), _stream(dev)), "agghead_forward")
+        ctx.save_for_backward(x)
+        ctx.wshape = tuple(weight.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        dev = x.device
+        B, Cin, H, W = x.shape
+        Cout = ctx.wshape[0]
+        with torch.cuda.device(dev):
+            if B == 0:
+                return torch.zeros(ctx.wshape, dtype=torch.float32, device=dev), None, None
+            grad = grad.to(torch.float32).contiguous()
+            dw = torch.empty(ctx.wshape, dtype=torch.float32, device=dev)
+            L = _L()
+            nbytes = L.gdf_agghead_wgrad_workspace(B, Cin, Cout, H, W)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            src = _agg_src(x)
+            native._check(L.gdf_agghead_wgrad(C.addressof(src), B, C.c_void_p(grad.data_ptr()), Cout, C.c_void_p(dw.data_ptr()), 0,
+                                              C.c_void_p(ws.data_ptr()), nbytes, _stream(dev)), "agghead_wgrad")
+        return dw, None, None
+
+
+class TrainableAggregationHead(torch.nn.Module):
+    """The reference AggregationNetwork's trained part as a torch.nn.Module: `self.out = nn.Conv2d(Cin, Cout, 3, padding=1, bias=False)` holds the
+    only parameter, so state_dict() has the reference's key `out.weight`, a task-corres.py checkpoint loads into it, and what it saves loads into
+    the reference and into AggregationHead.  `logit_scale` is the reference's constant log(1 / 0.07), a plain tensor that is not trained.
+
+    source: anything aggregation_head_params accepts (a source with a bias is a ValueError: the reference's head has none), or Cin with Cout for
+    nn.Conv2d's own initialisation.
+
+    head(x) on a device map ((B, Cin, H, W) or (Cin, H, W), fp16 or fp32, any strides; the module must be on that device) runs
+    gdf_agghead_forward; its backward runs gdf_agghead_wgrad and gives out.weight its gradient.  x gets none: extraction is not differentiable on
+    the native path, and a device x that requires a gradient is a ValueError.  The packed weights are refreshed lazily: when out.weight's
+    version counter or storage differs from what was packed (an optimiser step, load_state_dict, copy_, .to(device)), the next forward runs
+    gdf_agghead_update first; refresh() forces that.  Writes that bypass the version counter (through `.data`) need refresh().  One handle per
+    device.  .eval() and .train() change nothing.  Host tensors take F.conv2d through self.out with torch's own autograd."""
+
+    def __init__(self, source, Cout=None):
+        super().__init__()
+        if isinstance(source, int) and not isinstance(source, bool):
+            if Cout is None or int(Cout) < 1 or source < 1:
+                raise ValueError("TrainableAggregationHead(Cin, Cout): Cin and Cout >= 1")
+            self.out = torch.nn.Conv2d(source, int(Cout), kernel_size=3, stride=1, padding=1, bias=False)
+        else:
+            if Cout is not None:
+                raise ValueError("TrainableAggregationHead: Cout goes with Cin, not with a source of weights")
+            weight, bias = aggregation_head_params(source)
+            if bias is not None:
+                raise ValueError("TrainableAggregationHead: the source has a bias; the reference's head has none")
+            self.out = torch.nn.Conv2d(weight.shape[1], weight.shape[0], kernel_size=3, stride=1, padding=1, bias=False)
+            with torch.no_grad():
+                self.out.weight.copy_(weight)
+        self.Cout, self.Cin = int(self.out.weight.shape[0]), int(self.out.weight.shape[1])
+        self.logit_scale = torch.ones([]) * math.log(1 / 0.07)
+        self._handles = {}                               # device index -> [gdf_agghead, packed version, packed data_ptr]
+
+    def _handle(self, dev, force=False):
+        """gdf_agghead of this head on `dev`, holding the weights as they are now"""
+        w = self.out.weight
+        if w.device != dev:
+            raise ValueError(f"TrainableAggregationHead: the map is on {dev}, the module on {w.device}; move the module with .to(device)")
+        if w.dtype != torch.float32 or not w.is_contiguous():
+            raise ValueError("TrainableAggregationHead: out.weight is a contiguous fp32 tensor")
+        key = dev.index or 0
+        state = (w._version, w.data_ptr())
+        with torch.cuda.device(dev):
+            if key not in self._handles:
+                h = C.c_void_p()
+                native._check(_L().gdf_agghead_create_device(self.Cin, self.Cout, C.c_void_p(w.data_ptr()), None, _stream(dev), C.byref(h)),
+                              "agghead_create_device")
+                self._handles[key] = [h, state]
+            elif force or self._handles[key][1] != state:
+                native._check(_L().gdf_agghead_update(self._handles[key][0], C.c_void_p(w.data_ptr()), _stream(dev)), "agghead_update")
+                self._handles[key][1] = state
+        return self._handles[key][0]
+
+    def refresh(self):
+        """repack out.weight now (on the device the module is on), whatever the version counter says"""
+        if self.out.weight.is_cuda:
+            self._handle(self.out.weight.device, force=True)
+
+    def __del__(self):
+        for h in getattr(self, "_handles", {}).values():
+            try:
+                _lib.gdf_agghead_destroy(h[0])
+            except Exception:
+                pass
+
+    def forward(self, x):
+        if x.dim() == 3:
+            return self(x[None])[0]
+        if x.dim() != 4 or x.shape[1] != self.Cin:
+            raise ValueError(f"TrainableAggregationHead: x is (B, {self.Cin}, H, W) or ({self.Cin}, H, W), not {tuple(x.shape)}")
+        if x.shape[2] < 1 or x.shape[3] < 1:
+            raise ValueError("TrainableAggregationHead: H and W >= 1")
+        if not x.is_cuda:
+            return self.out(x.float())
+        if x.requires_grad:
+            raise ValueError("TrainableAggregationHead: a device map that requires a gradient: the native head has no input gradient (extraction "
+                             "is not differentiable on the native path); detach the map")
+        x = x if x.dtype in (torch.float16, torch.float32) else x.float()
+        return _HeadConv.apply(self.out.weight, x, self._handle(x.device))
+
+
+def rescale_points(points, old_shape, new_shape):
+    """The reference's helper (correspondence/correspondence/correspondence_utils.py:53-59), same signature: points (N, 2) in (y, x) order, the
+    shapes in (w, h) order -> the points scaled by (new h / old h, new w / old w)."""
+    return np.multiply(points, np.array([new_shape[1] / old_shape[1], new_shape[0] / old_shape[0]]))
+
+
+def compute_pck(predicted_points, target_points, load_size, pck_threshold=0.1, target_bounding_box=None):
+    """The reference's helper (correspondence_utils.py:160-167), same signature -> (distances (N,), correct (N,) bool, their fraction): a point is
+    correct when its Euclidean distance to the target is at most pck_threshold times the longer side of the image (load_size) or, when given, of
+    the target's bounding box (left, top, right, bottom)."""
+    distances = np.linalg.norm(predicted_points - target_points, axis=-1)
+    if target_bounding_box is None:
+        side = max(load_size)
+    else:
+        left, top, right, bottom = target_bounding_box
+        side = max(right - left, bottom - top)
+    pck = distances <= pck_threshold * side
+    return distances, pck, pck.sum() / len(pck)
 
 
 def avg_pool(feat, r):

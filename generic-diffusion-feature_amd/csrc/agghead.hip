@@ -257,14 +257,83 @@ uint16_t ah_half_bits(float v) {                 // round to nearest even, subno
   return u;
 }
 
+// the device image of a head: [packed fragments][1 / scale][bias]
+struct AhLayout { int nkt, nrb; size_t blk, o_is, o_b, bytes; };
+AhLayout ah_layout(int Cin, int Cout) {
+  AhLayout l;
+  l.nkt = (Cin + AH_KT - 1) / AH_KT;
+  l.nrb = (Cout + 31) / 32;
+  l.blk = (size_t)l.nkt * AH_STEPS * 2 * 64 * 8;                            // halves of one 32-row block
+  l.o_is = ah_up256((size_t)l.nrb * l.blk * 2);
+  l.o_b = l.o_is + ah_up256((size_t)l.nrb * 32 * 4);
+  l.bytes = l.o_b + ah_up256((size_t)l.nrb * 32 * 4);
+  return l;
+}
+
+__device__ __forceinline__ int ah_shift_of(float m) { return (m > 0.f && m < INFINITY) ? 13 - ilogbf(m) : 0; }
+
+// agghead_create's rule for one row on the device: the row's largest magnitude, sh = 13 - ilogb(max) (0 for a zero or non-finite maximum) and
+// 1 / scale = 2^-sh; rows from Cout up to the end of the last 32-row block get 1
+__global__ __launch_bounds__(256) void ah_rowscale_kernel(const float* __restrict__ W, int Cout, long rowlen, float* inv_s) {
+  __shared__ float red[256];
+  const int co = blockIdx.x, t = threadIdx.x;
+  float m = 0.f;
+  if (co < Cout)
+    for (long i = t; i < rowlen; i += 256) m = fmaxf(m, fabsf(W[(long)co * rowlen + i]));
+  red[t] = m;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) red[t] = fmaxf(red[t], red[t + s]);
+    __syncthreads();
+  }
+  if (t == 0) inv_s[co] = ldexpf(1.f, -ah_shift_of(red[0]));
+}
+
+// One thread = one lane entry (32-row block, channel tile, 16-channel step, lane) of the fragment image: 8 channels x 9 taps of one row, 72
+// consecutive floats of W, become the lane's 16 bytes of the 18 (tap, hi / lo) fragments; the 64 lanes of a fragment store 1 KB in a row.  The
+// row's shift is read back from 1 / scale = 2^-sh (an exact power of two, subnormals included), so the handle needs no scratch; only where 2^-sh
+// has underflowed to 0 (a row whose largest magnitude is below 2^-136) the thread finds the row's maximum again.
+__global__ __launch_bounds__(256) void ah_pack_kernel(const float* __restrict__ W, const float* __restrict__ inv_s, int Cin, int Cout, int nkt,
+                                                      long n, ah_u32x4* img) {
+  const long id = (long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= n) return;
+  const int lane = (int)(id & 63), s = (int)((id >> 6) & 1), kt = (int)((id >> 7) % nkt);
+  const long rb = (id >> 7) / nkt;
+  const int co = (int)rb * 32 + (lane & 31), ci0 = kt * AH_KT + s * 16 + (lane >> 5) * 8;
+  int shv = 0;
+  if (co < Cout) {
+    const float inv = inv_s[co];
+    if (inv > 0.f) {
+      shv = -ilogbf(inv);
+    } else {
+      float m = 0.f;
+      for (long i = 0; i < (long)Cin * 9; ++i) m = fmaxf(m, fabsf(W[(long)co * Cin * 9 + i]));
+      shv = ah_shift_of(m);
+    }
+  }
+  ah_u32x4* o = img + ((rb * nkt + kt) * 9 * (AH_KT / 16) + s) * 2 * 64 + lane;
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap) {
+    ah_f16x8 hi, lo;
+#pragma unroll
+    for (int el = 0; el < 8; ++el) {
+      const float v = (co < Cout && ci0 + el < Cin) ? ldexpf(W[((long)co * Cin + ci0 + el) * 9 + tap], shv) : 0.f;
+      hi[el] = (_Float16)v;
+      lo[el] = (_Float16)(v - (float)hi[el]);
+    }
+    o[(long)tap * (AH_KT / 16) * 2 * 64] = __builtin_bit_cast(ah_u32x4, hi);
+    o[(long)tap * (AH_KT / 16) * 2 * 64 + 64] = __builtin_bit_cast(ah_u32x4, lo);
+  }
+}
+
 }  // namespace
 
 hipError_t agghead_create(int Cin, int Cout, const float* W, const float* bias, AggHead** out) {
-  const int nkt = (Cin + AH_KT - 1) / AH_KT, nrb = (Cout + 31) / 32;
-  const size_t blk = (size_t)nkt * AH_STEPS * 2 * 64 * 8;                   // halves of one 32-row block
-  const size_t o_is = ah_up256((size_t)nrb * blk * 2), o_b = o_is + ah_up256((size_t)nrb * 32 * 4), bytes = o_b + ah_up256((size_t)nrb * 32 * 4);
+  const AhLayout l = ah_layout(Cin, Cout);
+  const int nkt = l.nkt, nrb = l.nrb;
+  const size_t blk = l.blk, o_is = l.o_is, o_b = l.o_b;
   void* dev = nullptr;
-  hipError_t e = hipMalloc(&dev, bytes);
+  hipError_t e = hipMalloc(&dev, l.bytes);
   if (e != hipSuccess) return e;
   char* d = (char*)dev;
   // one 32-row block at a time (the packed image of the largest head is close to 1 GB: it is never held on the host as a whole)
@@ -300,6 +369,33 @@ hipError_t agghead_create(int Cin, int Cout, const float* W, const float* bias, 
   if (e == hipSuccess) e = hipMemcpy(d + o_b, bs.data(), bs.size() * 4, hipMemcpyHostToDevice);
   if (e != hipSuccess) { (void)hipFree(dev); return e; }
   *out = new AggHead{Cin, Cout, nkt, nrb, dev, (const void*)d, (const float*)(d + o_is), (const float*)(d + o_b)};
+  return hipSuccess;
+}
+
+// the packed image and 1 / scale of `h` from fp32 OIHW weights on the device: two launches, stream-ordered, nothing else
+hipError_t agghead_update(AggHead* h, const float* W_dev, hipStream_t s) {
+  if (!h || !W_dev) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ah_rowscale_kernel, dim3(h->nrb * 32), dim3(256), 0, s, W_dev, h->Cout, (long)h->Cin * 9, (float*)h->inv_s);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const long n = (long)h->nrb * h->nkt * 2 * 64;
+  hipLaunchKernelGGL(ah_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W_dev, h->inv_s, h->Cin, h->Cout, h->nkt, n,
+                     (ah_u32x4*)h->w);
+  return hipGetLastError();
+}
+
+hipError_t agghead_create_device(int Cin, int Cout, const float* W_dev, const float* bias_dev, hipStream_t s, AggHead** out) {
+  const AhLayout l = ah_layout(Cin, Cout);
+  void* dev = nullptr;
+  hipError_t e = hipMalloc(&dev, l.bytes);
+  if (e != hipSuccess) return e;
+  char* d = (char*)dev;
+  AggHead* h = new AggHead{Cin, Cout, l.nkt, l.nrb, dev, (const void*)d, (const float*)(d + l.o_is), (const float*)(d + l.o_b)};
+  e = hipMemsetAsync(d + l.o_b, 0, (size_t)l.nrb * 32 * 4, s);
+  if (e == hipSuccess && bias_dev) e = hipMemcpyAsync(d + l.o_b, bias_dev, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = agghead_update(h, W_dev, s);
+  if (e != hipSuccess) { agghead_destroy(h); return e; }
+  *out = h;
   return hipSuccess;
 }
 

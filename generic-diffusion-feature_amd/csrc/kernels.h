@@ -375,14 +375,25 @@ hipError_t launch_pixcls(const PixCls* pc, const AggSrc& x, int B, long long* la
 // logical (B, Cin, H, W) map.  agghead_create packs the host fp32 OIHW weights (Cout, Cin, 3, 3) as row-scaled fp16 (hi, lo) pairs in MFMA fragment
 // order, one 32-row block at a time, and uploads them with 1 / scale and the bias (null: zeros) per output channel; the packed image is addressed
 // with 64-bit offsets (7360 -> 3680 is close to 1 GB).  launch_agghead: out (B, Cout, H, W) fp32 contiguous; B * H * W < 2^31.
+// agghead_update repacks fp32 OIHW weights that live on the device into h's image and 1 / scale in place (two launches on `s`, no allocation, no
+// host synchronisation; for finite weights the same bits agghead_create packs on the host); agghead_create_device
+// is the allocation, the bias (device, or null: zeros) and the same kernels.
 struct AggHead {
   int Cin, Cout, nkt, nrb;
   void* dev;
   const void* w; const float *inv_s, *bias;
 };
 hipError_t agghead_create(int Cin, int Cout, const float* W, const float* bias, AggHead** out);
+hipError_t agghead_create_device(int Cin, int Cout, const float* W_dev, const float* bias_dev, hipStream_t s, AggHead** out);
+hipError_t agghead_update(AggHead* h, const float* W_dev, hipStream_t s);
 void agghead_destroy(AggHead* h);
 hipError_t launch_agghead(const AggHead* h, const AggSrc& x, int B, float* out, hipStream_t s);
+// the weight gradient of that convolution (aggwgrad.hip): dW (Cout, x.C, 3, 3) fp32 OIHW = sum over (b, y, x) of grad_out (B, Cout, H, W) fp32
+// contiguous times the shifted map x (logical (B, C, H, W), fp16 or fp32, any strides); accumulate: the complete sum is added once to what dW
+// holds.  The workspace (agghead_wgrad_workspace bytes, 16-byte aligned) receives max |grad_out| (Cout floats), the shift (Cout ints) per
+// output channel and grad_out as scaled fp16 (hi, lo) pairs in MFMA fragment order.  B * H * W < 2^31.
+size_t agghead_wgrad_workspace(int B, int Cout, int H, int W);
+hipError_t launch_agghead_wgrad(const AggSrc& x, int B, const float* grad_out, int Cout, float* dW, int accumulate, void* workspace, hipStream_t s);
 // adaptive_avg_pool2d to (H/r, W/r) of a channels-last hook (B,C,H,W; strides sb, 1, sy, sx) -> (B, H/r, W/r, C) fp16: the r x r mean
 // where r divides H and W, ATen's longer windows [floor(o H / OH), ceil((o + 1) H / OH)) otherwise
 hipError_t launch_avg_pool(const half_t* src, long sb, long sy, long sx, int B, int C, int H, int W, int r, half_t* out, hipStream_t s);

@@ -610,6 +610,37 @@ int gdf_agghead_forward(gdf_agghead h, const gdf_agg_src* x, int B, float* out, 
   const AggSrc a{x->ptr, x->f32, x->sb, x->sc, x->sy, x->sx, x->C, x->H, x->W, 0};
   return fin(launch_agghead(ah, a, B, out, (hipStream_t)stream), "gdf_agghead_forward");
 }
+int gdf_agghead_create_device(int Cin, int Cout, const float* W_dev, const float* bias_dev, void* stream, gdf_agghead* out) {
+  auto bad = [](const char* msg) { set_error(std::string("gdf_agghead_create_device: ") + msg); return GDF_ERR_ARG; };
+  if (out) *out = nullptr;
+  if (!W_dev || !out) return bad("null pointer");
+  if (Cin < 1 || Cout < 1) return bad("Cin and Cout >= 1");
+  AggHead* h = nullptr;
+  const int rc = fin(agghead_create_device(Cin, Cout, W_dev, bias_dev, (hipStream_t)stream, &h), "gdf_agghead_create_device");
+  if (rc == GDF_OK) *out = (gdf_agghead)h;
+  return rc;
+}
+int gdf_agghead_update(gdf_agghead h, const float* W_dev, void* stream) {
+  if (!h || !W_dev) { set_error("gdf_agghead_update: null pointer"); return GDF_ERR_ARG; }
+  return fin(agghead_update((AggHead*)h, W_dev, (hipStream_t)stream), "gdf_agghead_update");
+}
+size_t gdf_agghead_wgrad_workspace(int B, int Cin, int Cout, int H, int W) {
+  (void)Cin;
+  return agghead_wgrad_workspace(std::max(B, 1), std::max(Cout, 1), std::max(H, 1), std::max(W, 1));
+}
+int gdf_agghead_wgrad(const gdf_agg_src* x, int B, const float* grad_out, int Cout, float* dW, int accumulate, void* ws, size_t ws_bytes,
+                      void* stream) {
+  auto bad = [](const char* msg) { set_error(std::string("gdf_agghead_wgrad: ") + msg); return GDF_ERR_ARG; };
+  if (!x || !grad_out || !dW || !ws) return bad("null pointer");
+  if (!x->ptr) return bad("null feature pointer");
+  if (B < 0 || Cout < 1 || x->C < 1 || x->H < 1 || x->W < 1) return bad("B >= 0, Cout, C, H and W >= 1");
+  if ((long long)std::max(B, 1) * x->H * x->W >= (1ll << 31)) return bad("B * H * W >= 2^31; split the batch");
+  if ((uintptr_t)ws & 15) return bad("the workspace must be 16-byte aligned");
+  if (ws_bytes < gdf_agghead_wgrad_workspace(B, x->C, Cout, x->H, x->W)) return bad("workspace smaller than gdf_agghead_wgrad_workspace says");
+  if (B == 0) return GDF_OK;
+  const AggSrc a{x->ptr, x->f32, x->sb, x->sc, x->sy, x->sx, x->C, x->H, x->W, 0};
+  return fin(launch_agghead_wgrad(a, B, grad_out, Cout, dW, accumulate, ws, (hipStream_t)stream), "gdf_agghead_wgrad");
+}
 int gdf_op_avg_pool(const void* src, long sb, long sy, long sx, int B, int C, int H, int W, int r, void* out, void* stream) {
   return fin(launch_avg_pool((const half_t*)src, sb, sy, sx, B, C, H, W, r, (half_t*)out, (hipStream_t)stream), "avg_pool");
 }

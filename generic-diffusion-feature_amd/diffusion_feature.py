@@ -660,13 +660,14 @@ class FeatureExtractor(nn.Module):
         """The correspondence evaluator's descriptor map from a feature dict (reference correspondence/correspondence/aggregation_network.py:62-66,
         97-100, AggregationNetwork.forward(x, do_conv) from the extraction onward): aggregate(feats, size) (bilinear, fp16) and, when a head is
         given, its fp32 3 x 3 output convolution -> (B, Cout, OH, OW) fp32; head=None is do_conv=False and returns the aggregated map.  Either
-        result feeds correspond() as it is.  head: a components.postproc.AggregationHead, or anything it is built from (the reference's
+        result feeds correspond() as it is.  head: a components.postproc.AggregationHead, a TrainableAggregationHead (passed through as it is: the
+        result then carries the graph for out.weight), or anything an AggregationHead is built from (the reference's
         AggregationNetwork, an nn.Conv2d, a weight, a state dict, a task-corres.py checkpoint)."""
-        from components.postproc import AggregationHead
+        from components.postproc import AggregationHead, TrainableAggregationHead
         agg = self.aggregate(feats, size)
         if head is None:
             return agg
-        if not isinstance(head, AggregationHead):
+        if not isinstance(head, (AggregationHead, TrainableAggregationHead)):
             head = AggregationHead(head)
         return head(agg)
 

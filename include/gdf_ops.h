@@ -435,6 +435,38 @@ typedef struct gdf_agghead_s* gdf_agghead;
 int gdf_agghead_create(int Cin, int Cout, const float* W /* host, (Cout, Cin, 3, 3) */, const float* bias /* host (Cout) or NULL */, gdf_agghead* out);
 void gdf_agghead_destroy(gdf_agghead h);
 int gdf_agghead_forward(gdf_agghead h, const gdf_agg_src* x, int B, float* out /* (B, Cout, H, W) */, void* stream);
+/* Training that head (correspondence/task-corres.py train(), `--algorithm conv`: loss.backward() through aggregation_network.out, then AdamW):
+ * the weight gradient of the convolution and the repack of updated weights, both on the device (csrc/aggwgrad.hip, csrc/agghead.hip).
+ *   gdf_agghead_wgrad    dW[co, ci, dy, dx] = sum_{b, y, x} grad_out[b, co, y, x] x[b, ci, y + dy - 1, x + dx - 1], zeros outside the image.
+ *       x                the map the forward took: logical (B, Cin, H, W), fp16 or fp32, element strides sb/sc/sy/sx, read only, `coff` ignored;
+ *                        read with its own strides, lanes along x (coalesced where sx == 1; a channels-last map is correct, not fast)
+ *       grad_out         (B, Cout, H, W) fp32 contiguous: what gdf_op_clip_loss_backward writes
+ *       dW               (Cout, Cin, 3, 3) fp32 contiguous, nn.Conv2d.weight's layout, addressed with 64-bit offsets.  accumulate = 0 writes it;
+ *                        accumulate = 1 forms the complete sum first and adds it once to what dW holds, so dW0 + (accumulate = 0) and
+ *                        (accumulate = 1 onto dW0) have the same bits
+ *       ws               gdf_agghead_wgrad_workspace bytes, 16-byte aligned; afterwards it holds max |grad_out| per output channel (Cout floats)
+ *                        and, 256-byte aligned behind them, the power-of-two shift used for that channel (Cout ints)
+ *                        Arithmetic: grad_out becomes an fp16 (hi, lo) pair per element after a power-of-two scale per output channel that puts
+ *                        the channel's maximum into [2^13, 2^14) (saturating; an all-zero channel yields exactly 0; the epilogue undoes the scale
+ *                        exactly); an fp16 map is multiplied as given (lo x, hi x), an fp32 map is split as it is staged (lo lo dropped); fp32
+ *                        accumulation on the MFMA units, folded into a second fp32 total every 128 pixels.  grad_out is not validated: a
+ *                        non-finite value gives unspecified values in its output channel's rows of dW, never an access outside the buffers.
+ *                        One pre-pass and one launch, stream-ordered, no atomics, no split-K, fixed summation order (the same inputs give the same
+ *                        bits on any stream), no allocation.  A null pointer (x, x->ptr, grad_out, dW, ws), Cout, C, H or W below 1, B < 0,
+ *                        B * H * W >= 2^31, a workspace that is too small or misaligned: GDF_ERR_ARG before any launch.  B == 0 is a successful
+ *                        no-op that launches nothing: with accumulate = 0 it does NOT zero dW.
+ *   gdf_agghead_update   overwrites the handle's packed fragment image and 1 / scale from W_dev, an fp32 OIHW (Cout, Cin, 3, 3) DEVICE tensor, by
+ *                        gdf_agghead_create's rule (row maximum, sh = 13 - ilogb(max), hi = fp16(v 2^sh), lo = fp16(v 2^sh - hi), the same
+ *                        fragment order, zeros in the padding): for finite weights the image is bit-identical to what gdf_agghead_create packs
+ *                        on the host from the same values.  Two launches, stream-ordered after the forwards already queued on `stream`, no host
+ *                        synchronisation, no allocation; the bias stays.  The weights are not validated (that would need a read-back).
+ *   gdf_agghead_create_device   the allocation plus the same kernels; bias_dev (Cout) on the device or NULL.  Asynchronous on `stream`.
+ * A null handle, W_dev or out, Cin or Cout below 1: GDF_ERR_ARG. */
+size_t gdf_agghead_wgrad_workspace(int B, int Cin, int Cout, int H, int W);
+int gdf_agghead_wgrad(const gdf_agg_src* x, int B, const float* grad_out /* (B, Cout, H, W) */, int Cout, float* dW /* (Cout, Cin, 3, 3) */,
+                      int accumulate, void* ws, size_t ws_bytes, void* stream);
+int gdf_agghead_create_device(int Cin, int Cout, const float* W_dev, const float* bias_dev, void* stream, gdf_agghead* out);
+int gdf_agghead_update(gdf_agghead h, const float* W_dev, void* stream);
 /* `feature_resize` (components/feature_extractor.py:51-53): adaptive_avg_pool2d to (OH, OW) = (H / r, W / r) (integer division) of a
  * channels-last hook (strides sb, 1, sy, sx; C % 8 == 0) -> (B, OH, OW, C) fp16, fp32 accumulation.  Output row o averages source rows
  * [floor(o H / OH), ceil((o + 1) H / OH)), columns likewise: the r x r window where r divides the size, otherwise longer windows that may
