@@ -15,6 +15,7 @@ the hot path:
   TrainableAggregationHead   correspondence/task-corres.py:144-162 train() on aggregation_network.out   the same head as a torch.nn.Module whose
                      forward is that device convolution and whose backward is the device weight gradient (csrc/aggwgrad.hip); updated weights
                      are repacked on the device
+  pca / pca_rgb      feature_visualization.py:84-101   plot_pca: the PCA of a feature map and its picture (csrc/pca.hip)
   rescale_points / compute_pck   correspondence/correspondence/correspondence_utils.py:53-59, 160-167   validate()'s two host helpers (numpy)
   avg_pool           components/feature_extractor.py:51-53   `feature_resize` (adaptive_avg_pool2d to (H/r, W/r))
   aggregate_maps     components/attention.py:238-244, 141-161 + diffusion_feature.py:492-500   aggregated `attn` feature
@@ -22,8 +23,10 @@ the hot path:
 Device tensors go through the HIP kernels (and fail loudly if the library is missing); host tensors (accept-all mode hands
 out `.cpu()` copies, feature_extractor.py:65-66) are plain data already off the GPU path and use torch on the CPU.
 """
+import collections
 import ctypes as C
 import math
+import warnings
 
 import numpy as np
 import torch
@@ -68,6 +71,10 @@ _SIG["gdf_agghead_create_device"] = (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c
 _SIG["gdf_agghead_update"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])
 _SIG["gdf_agghead_wgrad_workspace"] = (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int])
 _SIG["gdf_agghead_wgrad"] = (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
+_SIG["gdf_op_pca_workspace"] = (C.c_size_t, [C.c_int] * 6)
+_SIG["gdf_op_pca"] = (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
+_SIG["gdf_op_pca_rgb"] = (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p])
 _lib = None
 
 
@@ -733,6 +740,120 @@ class TrainableAggregationHead(torch.nn.Module):
                              "is not differentiable on the native path); detach the map")
         x = x if x.dtype in (torch.float16, torch.float32) else x.float()
         return _HeadConv.apply(self.out.weight, x, self._handle(x.device))
+
+
+PCAResult = collections.namedtuple("PCAResult", "mean components explained_variance explained_variance_ratio projection n_iter converged")
+PCA_MAX_COMPONENTS, PCA_MAX_C = 8, 4096
+
+
+def _pca_args(features, n_components, joint):
+    if not torch.is_tensor(features) or features.dim() != 4:
+        raise ValueError("features is a (B, C, H, W) tensor")
+    B, C_, H, W = features.shape
+    if min(C_, H, W) < 1:
+        raise ValueError("C, H and W >= 1")
+    k = int(n_components)
+    n = (B if joint else 1) * H * W
+    if not 1 <= k <= PCA_MAX_COMPONENTS:
+        raise ValueError(f"1 <= n_components <= {PCA_MAX_COMPONENTS}")
+    if k > min(C_, n - 1):
+        raise ValueError(f"n_components = {k} exceeds min(C, samples - 1) = {min(C_, n - 1)}")
+    return B, C_, H, W, k
+
+
+def _pca_host(features, k, joint):
+    """the reference's arithmetic in float64 on a host tensor: eigh of the centred covariance, the sign rule -> float64 tensors"""
+    B, C_, H, W = features.shape
+    x = features.double().permute(0, 2, 3, 1).reshape(B, H * W, C_)
+    x = x.reshape(1, B * H * W, C_) if joint else x
+    mean = x.mean(1, keepdim=True)
+    xc = x - mean
+    cov = xc.transpose(1, 2) @ xc / (x.shape[1] - 1)
+    w, v = torch.linalg.eigh(cov)
+    w, v = w.flip(-1)[:, :k], v.flip(-1)[:, :, :k].transpose(1, 2)                        # (G, k), (G, k, C), descending
+    big = v.abs().argmax(-1, keepdim=True)
+    sign = torch.sign(torch.gather(v, 2, big))
+    v = v * torch.where(sign == 0, torch.ones_like(sign), sign)
+    keep = (w > 2.0 ** -20 * w[:, :1]) & (w > 0)                                          # as the device op: such a direction is rounding, not data
+    w, v = torch.where(keep, w, torch.zeros_like(w)), v * keep[:, :, None]
+    proj = (xc @ v.transpose(1, 2)).reshape(B, H * W, k).permute(0, 2, 1).reshape(B, k, H, W)
+    return mean[:, 0], v, w, cov.diagonal(dim1=1, dim2=2).sum(-1), proj
+
+
+def pca(features, n_components=3, joint=False, max_iter=256, tol=2.0 ** -20):
+    """features (B, C, H, W), fp16 or fp32 with any strides -> PCAResult(mean (G, C), components (G, k, C), explained_variance (G, k),
+    explained_variance_ratio (G, k), projection (B, k, H, W), n_iter (G,) int32, converged (G,) bool), fp32 on the device of `features`.
+    The reference's PCA(n_components).fit(f).transform(f) (feature_visualization.py:84-88) of every image's H W samples (G = B) or, joint, of the
+    B H W samples of the batch (G = 1): per-channel mean, the leading eigenvectors of the sample covariance (divisor n - 1), each signed so that
+    its entry of largest magnitude is positive.  Device tensors: gdf_op_pca (block subspace iteration, at most max_iter iterations, converged when
+    every residual is at most tol x the largest eigenvalue; a run that does not converge warns once and returns its last estimate).  Host
+    tensors: torch.linalg.eigh in float64 (n_iter 0, converged).  On either path a component whose eigenvalue is not above 2^-20 of the first is
+    the zero vector with variance 0."""
+    B, C_, H, W, k = _pca_args(features, n_components, joint)
+    max_iter, tol = int(max_iter), float(tol)
+    if not 1 <= max_iter <= 1024:
+        raise ValueError("1 <= max_iter <= 1024")
+    if not (tol >= 0 and math.isfinite(tol)):
+        raise ValueError("tol is finite and not negative")
+    G = 1 if joint else B
+    if not features.is_cuda:
+        mean, comp, var, total, proj = _pca_host(features, k, joint)
+        return PCAResult(mean.float(), comp.float(), var.float(), (var / total[:, None]).float(), proj.float(),
+                         torch.zeros(G, dtype=torch.int32), torch.ones(G, dtype=torch.bool))
+    if C_ > PCA_MAX_C:
+        raise ValueError(f"C = {C_}: the device PCA takes at most {PCA_MAX_C} channels")
+    dev = features.device
+    features = features if features.dtype in (torch.float16, torch.float32) else features.float()
+    with torch.cuda.device(dev):
+        f32 = dict(dtype=torch.float32, device=dev)
+        mean, comp, var, total = torch.empty(G, C_, **f32), torch.empty(G, k, C_, **f32), torch.empty(G, k, **f32), torch.empty(G, **f32)
+        proj = torch.empty(B, k, H, W, **f32)
+        info = torch.zeros(G, 2, dtype=torch.int32, device=dev)
+        if B > 0:
+            L = _L()
+            nbytes = L.gdf_op_pca_workspace(B, C_, H, W, k, int(bool(joint)))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            src = _agg_src(features)
+            native._check(L.gdf_op_pca(C.addressof(src), B, k, int(bool(joint)), max_iter, tol, C.c_void_p(mean.data_ptr()), C.c_void_p(comp.data_ptr()),
+                                       C.c_void_p(var.data_ptr()), C.c_void_p(total.data_ptr()), C.c_void_p(proj.data_ptr()),
+                                       C.c_void_p(info.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes, _stream(dev)), "pca")
+        converged = info[:, 1] != 0
+        if B > 0 and not bool(converged.all()):
+            warnings.warn("pca: the subspace iteration did not converge in %d iterations (tol %.3g); the last estimate is returned" % (max_iter, tol))
+    return PCAResult(mean, comp, var, var / total[:, None], proj, info[:, 0].contiguous(), converged)
+
+
+def pca_rgb(features, size=512, joint=False):
+    """features (B, C, H, W) -> (B, OH, OW, 3) uint8 on the device of `features`: the reference's plot_pca picture (feature_visualization.py:84-94)
+    of every image: the projection onto the three leading principal components, (p - min) / (max - min) per component over the image (over the
+    batch when joint, which also shares one PCA), (. * 255) truncated, and Pillow's nearest resize of the short side to `size` (the long side to
+    int(size * long / short)); size=None keeps the grid.  A component of zero range is 0.  Device tensors: gdf_op_pca and gdf_op_pca_rgb;
+    host tensors: float64 torch."""
+    B, C_, H, W, _ = _pca_args(features, 3, joint)
+    if size is None:
+        OH, OW = H, W
+    else:
+        size = int(size)
+        if size < 1:
+            raise ValueError("size >= 1")
+        OH, OW = (size, int(size * W / H)) if H <= W else (int(size * H / W), size)
+    if not features.is_cuda:
+        proj = _pca_host(features, 3, joint)[4]
+        dims = (0, 2, 3) if joint else (2, 3)
+        lo, hi = proj.amin(dims, keepdim=True), proj.amax(dims, keepdim=True)
+        n = torch.where(hi > lo, (proj - lo) / (hi - lo), torch.zeros_like(proj))
+        u8 = (n * 255).to(torch.uint8)
+        iy = torch.clamp(((2 * torch.arange(OH) + 1) * H) // (2 * OH), max=H - 1)
+        ix = torch.clamp(((2 * torch.arange(OW) + 1) * W) // (2 * OW), max=W - 1)
+        return u8[:, :, iy][:, :, :, ix].permute(0, 2, 3, 1).contiguous()
+    proj = pca(features, 3, joint).projection
+    dev = features.device
+    with torch.cuda.device(dev):
+        out = torch.empty(B, OH, OW, 3, dtype=torch.uint8, device=dev)
+        if B > 0:
+            native._check(_L().gdf_op_pca_rgb(C.c_void_p(proj.data_ptr()), B, H, W, int(bool(joint)), C.c_void_p(out.data_ptr()), OH, OW,
+                                              _stream(dev)), "pca_rgb")
+    return out
 
 
 def rescale_points(points, old_shape, new_shape):

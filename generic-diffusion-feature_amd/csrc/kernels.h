@@ -354,6 +354,16 @@ hipError_t launch_clip_loss(const AggSrc& f1, const AggSrc& f2, int B, const lon
                             float* loss, float* terms, void* workspace, hipStream_t s);
 hipError_t launch_clip_loss_backward(const AggSrc& f1, const AggSrc& f2, int B, const long long* src_idx, const long long* tgt_idx, int N,
                                      float scale, const float* grad_loss, float* grad_f1, float* grad_f2, void* workspace, hipStream_t s);
+// PCA of a feature map (pca.hip): the k <= 8 leading principal components of the (H W, C) samples of every image, or of the (B H W, C) samples of
+// the batch (joint): mean (G, C), components (G, k, C), variance (G, k), total_variance (G), projection (B, k, H, W) or null, info (G, 2) int32
+// (iterations, converged), all fp32 but info; G = joint ? 1 : B.  Centred covariance on the MFMA units from fp16 (hi, lo) pairs, block subspace
+// iteration with 8 vectors and a Rayleigh-Ritz step per iteration, every iteration enqueued.  workspace: pca_workspace bytes, 16-byte aligned.
+// launch_pca_rgb: the reference's picture of a (B, 3, H, W) projection -> (B, OH, OW, 3) uint8.
+enum { PCA_MAXC = 4096, PCA_MAXITER = 1024 };
+size_t pca_workspace(int B, int C, int H, int W, int joint);
+hipError_t launch_pca(const AggSrc& f, int B, int k, int joint, int max_iter, float tol, float* mean, float* components, float* variance,
+                      float* total_variance, float* projection, int* info, void* workspace, hipStream_t s);
+hipError_t launch_pca_rgb(const float* projection, int B, int H, int W, int joint, unsigned char* out, int OH, int OW, hipStream_t s);
 // predict_labels of the label-scarce segmentation evaluator (pixcls.hip): an ensemble of M BatchNorm-folded per-pixel MLPs C -> h1 -> h2 -> K over
 // every pixel of a logical (B, C, H, W) map, then the per-pixel vote.  pixcls_create packs W1 and W2 as scaled fp16 (hi, lo) pairs in MFMA fragment order
 // and uploads everything once (host fp32 arrays: W1 (M, h1, C), b1 (M, h1), W2 (M, h2, h1), b2 (M, h2), W3 (M, K, h2), b3 (M, K)); widths are

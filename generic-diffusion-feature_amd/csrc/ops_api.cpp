@@ -544,6 +544,46 @@ int gdf_op_clip_loss_backward(const gdf_agg_src* f1, const gdf_agg_src* f2, int 
   return fin(launch_clip_loss_backward(a, b, B, src_idx, tgt_idx, N, scale, grad_loss, grad_f1, grad_f2, workspace, (hipStream_t)stream),
              "gdf_op_clip_loss_backward");
 }
+size_t gdf_op_pca_workspace(int B, int C, int H, int W, int k, int joint) {
+  (void)k;                                             // (the block always has 8 vectors)
+  return pca_workspace(std::max(B, 1), std::min(std::max(C, 1), (int)PCA_MAXC), std::max(H, 1), std::max(W, 1), joint ? 1 : 0);
+}
+int gdf_op_pca(const gdf_agg_src* src, int B, int k, int joint, int max_iter, float tol, float* mean, float* components, float* variance,
+               float* total_variance, float* projection, int* info, void* workspace, size_t workspace_bytes, void* stream) {
+  auto bad = [](const char* msg) { set_error(std::string("gdf_op_pca: ") + msg); return GDF_ERR_ARG; };
+  auto big = [](const char* msg) { set_error(std::string("gdf_op_pca: ") + msg); return GDF_ERR_UNSUPPORTED; };
+  if (!src || !mean || !components || !variance || !total_variance || !info || !workspace) return bad("null pointer");
+  if (!src->ptr) return bad("null feature pointer");
+  if (B < 0) return bad("B >= 0");
+  if (src->C < 1 || src->H < 1 || src->W < 1) return bad("C, H and W >= 1");
+  if (joint != 0 && joint != 1) return bad("joint is 0 or 1");
+  if (k < 1 || k > 8) return bad("1 <= k <= 8");
+  if (max_iter < 1 || max_iter > PCA_MAXITER) return bad("1 <= max_iter <= 1024");
+  if (!(tol >= 0.f) || !std::isfinite(tol)) return bad("tol is finite and not negative");
+  if ((uintptr_t)workspace & 15) return bad("the workspace must be 16-byte aligned");
+  const long long samples = (long long)(joint ? std::max(B, 1) : 1) * src->H * src->W;
+  if (k > src->C || k > samples - 1) return bad("k <= min(C, samples - 1)");
+  if (src->C > PCA_MAXC) return big("C > 4096");
+  if (B > 65535) return big("B > 65535; split the batch");
+  if ((long long)std::max(B, 1) * src->H * src->W >= (1ll << 31)) return big("B * H * W >= 2^31; split the batch");
+  if (workspace_bytes < gdf_op_pca_workspace(B, src->C, src->H, src->W, k, joint)) return bad("workspace smaller than gdf_op_pca_workspace says");
+  if (B == 0) return GDF_OK;
+  const AggSrc a{src->ptr, src->f32, src->sb, src->sc, src->sy, src->sx, src->C, src->H, src->W, 0};
+  return fin(launch_pca(a, B, k, joint, max_iter, tol, mean, components, variance, total_variance, projection, info, workspace,
+                        (hipStream_t)stream), "gdf_op_pca");
+}
+int gdf_op_pca_rgb(const float* projection, int B, int H, int W, int joint, unsigned char* out, int OH, int OW, void* stream) {
+  auto bad = [](const char* msg) { set_error(std::string("gdf_op_pca_rgb: ") + msg); return GDF_ERR_ARG; };
+  if (!projection || !out) return bad("null pointer");
+  if (B < 0 || H < 1 || W < 1 || OH < 1 || OW < 1) return bad("B >= 0, H, W, OH and OW >= 1");
+  if (joint != 0 && joint != 1) return bad("joint is 0 or 1");
+  if (B > 65535 || (long long)std::max(B, 1) * H * W >= (1ll << 31) || (long long)std::max(B, 1) * OH * OW >= (1ll << 31)) {
+    set_error("gdf_op_pca_rgb: B > 65535, B * H * W or B * OH * OW >= 2^31; split the batch");
+    return GDF_ERR_UNSUPPORTED;
+  }
+  if (B == 0) return GDF_OK;
+  return fin(launch_pca_rgb(projection, B, H, W, joint, out, OH, OW, (hipStream_t)stream), "gdf_op_pca_rgb");
+}
 int gdf_pixcls_create(int C, int M, int h1, int h2, int K, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
                       const float* b3, gdf_pixcls* out) {
   auto bad = [](const char* msg) { set_error(std::string("gdf_pixcls_create: ") + msg); return GDF_ERR_ARG; };

@@ -671,6 +671,23 @@ class FeatureExtractor(nn.Module):
             head = AggregationHead(head)
         return head(agg)
 
+    def visualize(self, feats=None, layers=None, size=512, joint=False):
+        """The reference's PCA pictures (feature_visualization.py:84-101, plot_pca) of a feature dict -> {layer id: (B, OH, OW, 3) uint8 tensor}:
+        every map projected onto its three leading principal components, each component scaled to 0 .. 255 over the image, resized (nearest) so
+        that the short side is `size` (None keeps the grid).  feats defaults to the dict of the last extract(); layers: the ids to draw (None =
+        all, in dict order; `attn` included, its C is the token count).  joint: one PCA and one colour scale for the whole batch of a layer.
+        Device tensors: gdf_op_pca and gdf_op_pca_rgb (components/postproc.py pca_rgb)."""
+        from components.postproc import pca_rgb
+        if feats is None:
+            feats = self.feature_store.stored_feats
+        if not feats:
+            raise ValueError("visualize: no features (call extract() first or pass feats=)")
+        ids = list(feats) if layers is None else list(layers)
+        missing = [i for i in ids if i not in feats]
+        if missing:
+            raise ValueError("visualize: no layer %r among the features" % (missing[0],))
+        return {i: pca_rgb(feats[i], size, joint) for i in ids}
+
     def set_background_extraction(self, idxs):
         self.feature_store.store_idx = idxs
 

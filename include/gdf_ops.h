@@ -377,6 +377,53 @@ int gdf_op_clip_loss(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const 
 int gdf_op_clip_loss_backward(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const long long* src_idx, const long long* tgt_idx, int N,
                               float scale, const float* grad_loss /* device, (B) */, float* grad_f1 /* (B, C, H1, W1) fp32 contiguous, or NULL */,
                               float* grad_f2 /* likewise, or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+/* The PCA picture of a feature map (feature_visualization.py:84-101, plot_pca: sklearn PCA(n_components=3).fit(f).transform(f) on the (H W, C)
+ * samples of a hooked layer or of the cross-attention maps, then the colouring) as two device ops (csrc/pca.hip).
+ * gdf_op_pca: with x_p the C values of sample p, n samples, mu = sum_p x_p / n and cov = sum_p (x_p - mu)(x_p - mu)^T / (n - 1):
+ *     components   the k leading eigenvectors v_1 .. v_k of cov, unit norm, each signed so that its entry of largest magnitude is positive
+ *                  (the lowest channel among equal magnitudes): scikit-learn's svd_flip(u_based_decision=False)
+ *     variance     their eigenvalues, descending;  total_variance = trace(cov);  projection[b, j, p] = <x_p - mu, v_j>
+ *   src        one logical (B, C, H, W) tensor, fp16 (f32 = 0) or fp32, with element strides sb/sc/sy/sx, read only; `coff` is ignored.  A map with
+ *              sx == 1 (NCHW, what gdf_op_aggregate writes) is read with lanes along the pixels; one with sc == 1, C a multiple of 8 (fp32: 4) and
+ *              16-byte aligned pixels with 16-byte loads along C; any other strides are correct, not fast.
+ *   joint      0: B independent PCAs, one per image (G = B, n = H W).  1: one PCA over the B H W pixels of the batch (G = 1), so that the images
+ *              share their components.
+ *   outputs    fp32: mean (G, C), components (G, k, C), variance (G, k), total_variance (G), projection (B, k, H, W) or NULL;
+ *              info (G, 2) int32: the iterations used and 1 if converged, else 0.
+ *   mean       fp32, compensated sums in a fixed order.
+ *   covariance of the CENTRED values (never the Gram matrix minus n mu mu^T) on the MFMA units with fp32 accumulation: (x - mu) times a power of
+ *              two is split into an fp16 (hi, lo) pair as it is staged, lo lo + lo hi + hi lo + hi hi; upper-triangular 128 x 128 tiles, mirrored, so cov
+ *              is exactly symmetric; the samples are split over at most 64 workgroups per tile whose partial tiles are added in a fixed order
+ *              (one fp32 accumulation chain covers at most 8192 samples up to n = 524 288 and n / 64 beyond: a joint run of more than 32
+ *              128 x 128 images accumulates longer chains, which no test covers); C is padded to the tile
+ *              with zeros the kernel writes.
+ *   eigenpairs block subspace iteration with min(8, C) vectors from a fixed starting block, fp32; per iteration cov @ V over many workgroups, then
+ *              one workgroup: the Rayleigh-Ritz step (an 8 x 8 Jacobi solve) and the orthonormalisation of the next block.  The PCA has converged
+ *              when max_j ||cov v_j - lambda_j v_j|| <= tol lambda_1 over the k wanted pairs; tol = 2^-20 (16 fp32 roundings) and max_iter = 256
+ *              are the Python defaults.  That criterion bounds an eigenvector's error by tol lambda_1 / gap only, so when it is first met, at
+ *              iteration i, converged is reported and i / 2 + 2 further iterations take the residual to its fp32 floor; info counts them all.
+ *              All max_iter iterations are enqueued as ordinary launches; after the last of those further iterations a device flag makes the
+ *              remaining launches return at once.  A run that reaches max_iter before the criterion is met reports converged = 0 with the
+ *              last Ritz pairs: not an error.  variance_j = <v_j, cov v_j> / <v_j, v_j> of the final vectors, accumulated in double, rounded
+ *              once.  An eigenvalue that is not above 2^-20 lambda_1 cannot be told from rounding in fp32: that component is the zero vector
+ *              with variance 0 (so a map whose third direction is exactly constant projects to exactly 0), and such a direction leaves the
+ *              block.
+ *   workspace  gdf_op_pca_workspace(B, C, H, W, k, joint) bytes, 16-byte aligned, caller-owned, contents undefined before and after: the padded
+ *              covariance (G, Cpad, Cpad), the partial tiles and the blocks.
+ * gdf_op_pca_rgb: projection (B, 3, H, W) fp32 contiguous -> out (B, OH, OW, 3) uint8: per component min and max over the image (over the batch
+ * when joint), n = (p - min) / (max - min) in fp32, n * 255 truncated; output pixel (oy, ox) takes the source pixel floor((o + 0.5) in / out) of
+ * each axis, clamped: Pillow's nearest resize.  A component of zero range is written as 0 (the reference casts NaN there).  The op has no
+ * workspace, so every workgroup takes the min and max itself: with joint = 1 and B > 64 that is B * B * H * W reads.
+ * No atomics, every reduction in a fixed order, no grid-wide wait: the same inputs give the same bits on any stream, and with joint = 0 at any
+ * batch position.  Stream-ordered, nothing read back, no allocation.  A null required pointer, C, H or W below 1, B < 0, k outside 1 .. 8 or above
+ * min(C, n - 1), max_iter outside 1 .. 1024, a tol that is negative or not finite, a misaligned or too small workspace: GDF_ERR_ARG before any
+ * launch.  C > 4096, B > 65535, B * H * W >= 2^31: GDF_ERR_UNSUPPORTED.  B == 0 is a successful no-op. */
+size_t gdf_op_pca_workspace(int B, int C, int H, int W, int k, int joint);
+int gdf_op_pca(const gdf_agg_src* src, int B, int k, int joint, int max_iter, float tol, float* mean /* (G, C) */,
+               float* components /* (G, k, C) */, float* variance /* (G, k) */, float* total_variance /* (G) */,
+               float* projection /* (B, k, H, W) or NULL */, int* info /* (G, 2) */, void* workspace, size_t workspace_bytes, void* stream);
+int gdf_op_pca_rgb(const float* projection /* (B, 3, H, W) */, int B, int H, int W, int joint, unsigned char* out /* (B, OH, OW, 3) */, int OH,
+                   int OW, void* stream);
 /* The label-scarce segmentation evaluator's second step on an aggregated map (scarce_segmentation/segmentation/pixel_classifier.py:70-107,
  * predict_labels): an ensemble of M per-pixel MLPs (pixel_classifier, :14-36) over every pixel, the per-pixel majority vote and the ensemble's
  * Jensen-Shannon uncertainty (csrc/pixcls.hip).  The networks are given BATCHNORM-FOLDED: eval-mode BatchNorm1d after ReLU is an
