@@ -6,6 +6,9 @@ the hot path:
                      F.interpolate(v, size, mode='bilinear') of every layer + torch.cat(dim=1), one launch per 16 layers
   nn_match / find_nn_source_correspondences   correspondence/correspondence/correspondence_utils.py:113-138   the evaluators' second step:
                      nearest neighbours of N source points among the load-size target pixels, without either load-size map (csrc/corres.hip)
+  dense_match / mutual_nn / dense_nn_correspondences / find_best_buddies_correspondences   correspondence/correspondence/correspondence_utils.py:
+                     73-111, 230-323   dense matching of two maps: best pixel and cosine in both directions from one MFMA pass, the P1 x P2
+                     matrix never built (csrc/densematch.hip)
   clip_loss / compute_clip_loss   correspondence/task-corres.py:70-80   the evaluator's loss on two hyperfeature maps, forward and backward,
                      without either P x P similarity matrix (csrc/cliploss.hip); a torch.autograd.Function on device tensors
   PixelClassifierEnsemble / predict_labels    scarce_segmentation/segmentation/pixel_classifier.py:14-36, 70-107   the label-scarce evaluator's
@@ -54,6 +57,9 @@ AGG_MAX = 16                                             # sources of one gdf_op
 _SIG["gdf_op_nn_match_workspace"] = (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int])
 _SIG["gdf_op_nn_match"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p])
+_SIG["gdf_op_dense_match_workspace"] = (C.c_size_t, [C.c_int] * 6)
+_SIG["gdf_op_dense_match"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_void_p])
 _SIG["gdf_op_clip_loss_workspace"] = (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int])
 _SIG["gdf_op_clip_loss"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_size_t, C.c_void_p])
@@ -227,7 +233,136 @@ def find_nn_source_correspondences(img1_feats, img2_feats, source_points, output
     return torch.from_numpy(source_points), points2[0]
 
 
-CLIP_SCALE = 1 / 0.07                                   # exp(logit_scale) of the reference's AggregationNetwork (aggregation_network.py:25)
+def dense_match(feats1, feats2, directions="both"):
+    """feats1 (B, C, h1, w1), feats2 (B, C, h2, w2), fp16 or fp32 with any strides -> (nn12 int64 (B, P1), sim12 fp32 (B, P1), nn21 int64 (B, P2),
+    sim21 fp32 (B, P2)), P = h * w, pixel p = y * w + x: for every pixel of feats1 its pixel of feats2 with the highest cosine similarity (lowest
+    index of the maximum) and that cosine, and the same for every pixel of feats2 among those of feats1.
+    The reference's batch_cosine_sim followed by max over both axes of the (B, P1, P2) matrix.  Device tensors: gdf_op_dense_match, which never
+    builds the matrix; host tensors: that torch chain in fp32.  directions: "both", "12" or "21"; the pair not asked for is returned as None.
+    A pixel of zero norm never wins; its own entry is index 0 with a NaN score on the device (the host chain propagates NaN as the reference)."""
+    if feats1.dim() != 4 or feats2.dim() != 4 or feats1.shape[0] != feats2.shape[0] or feats1.shape[1] != feats2.shape[1]:
+        raise ValueError("feats1 and feats2 are (B, C, h, w) tensors with the same B and C")
+    if directions not in ("both", "12", "21"):
+        raise ValueError(f"directions is 'both', '12' or '21', not {directions!r}")
+    if min(feats1.shape[1:]) < 1 or min(feats2.shape[1:]) < 1:
+        raise ValueError("C, h and w >= 1")
+    B, Cn = feats1.shape[:2]
+    P1, P2 = feats1.shape[2] * feats1.shape[3], feats2.shape[2] * feats2.shape[3]
+    d12, d21 = directions != "21", directions != "12"
+    if not feats2.is_cuda:
+        a = feats1.float().flatten(2).permute(0, 2, 1)
+        b = feats2.float().flatten(2).permute(0, 2, 1)
+        a = a / torch.linalg.norm(a, dim=-1)[:, :, None]
+        b = b / torch.linalg.norm(b, dim=-1)[:, :, None]
+        sims = torch.matmul(a, b.permute(0, 2, 1))
+        sim12, nn12 = sims.max(dim=-1) if d12 else (None, None)
+        sim21, nn21 = sims.max(dim=-2) if d21 else (None, None)
+        return nn12, sim12, nn21, sim21
+    dev = feats2.device
+    if feats1.device != dev:
+        raise ValueError("feats1 and feats2 are on the same device")
+    feats1, feats2 = (v if v.dtype in (torch.float16, torch.float32) else v.float() for v in (feats1, feats2))
+    with torch.cuda.device(dev):
+        nn12 = torch.empty(B, P1, dtype=torch.int32, device=dev) if d12 else None
+        sim12 = torch.empty(B, P1, dtype=torch.float32, device=dev) if d12 else None
+        nn21 = torch.empty(B, P2, dtype=torch.int32, device=dev) if d21 else None
+        sim21 = torch.empty(B, P2, dtype=torch.float32, device=dev) if d21 else None
+        if B > 0:
+            L = _L()
+            f32 = [int(v.dtype == torch.float32) for v in (feats1, feats2)]
+            nbytes = L.gdf_op_dense_match_workspace(B, Cn, P1, P2, f32[0], f32[1])
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            s1, s2 = _agg_src(feats1), _agg_src(feats2)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None       # noqa: E731
+            native._check(L.gdf_op_dense_match(C.addressof(s1), C.addressof(s2), B, ptr(nn12), ptr(sim12), ptr(nn21), ptr(sim21),
+                                               C.c_void_p(ws.data_ptr()), nbytes, _stream(dev)), "dense_match")
+    return (nn12.long() if d12 else None), sim12, (nn21.long() if d21 else None), sim21
+
+
+def cycle_index(nn12, nn21):
+    """nn21.gather(1, nn12) (B, P1): where the cycle image 1 -> image 2 -> image 1 ends for every pixel of image 1; the input of cycle-consistency
+    masks and distances (the reference's find_cyclical_correspondences computes it as torch.gather(nn_2, dim=-1, index=nn_1))."""
+    return nn21.gather(1, nn12)
+
+
+def _mutual_mask(nn12, nn21, saliency1, saliency2, thresh):
+    B, P1 = nn12.shape
+    mask = cycle_index(nn12, nn21) == torch.arange(P1, device=nn12.device)[None]
+    if saliency1 is not None:
+        mask = mask & (torch.as_tensor(saliency1).to(nn12.device).reshape(B, P1) > thresh)
+    if saliency2 is not None:
+        fg2 = torch.as_tensor(saliency2).to(nn12.device).reshape(B, nn21.shape[1]) > thresh
+        hit = torch.zeros(B, P1, dtype=torch.int32, device=nn12.device)
+        hit.scatter_add_(1, nn21, fg2.to(torch.int32))
+        mask = mask & (hit > 0)
+    return mask
+
+
+def mutual_nn(feats1, feats2, saliency1=None, saliency2=None, thresh=0.05):
+    """Mutual nearest neighbours ("best buddies") of two maps -> (mask (B, P1) bool, nn12 int64 (B, P1), sim12 fp32 (B, P1)):
+    mask[b, p] = nn21[b, nn12[b, p]] == p, i.e. pixel p of feats1 and its best pixel of feats2 choose each other.  Both directions come from
+    ONE dense_match call, so they reduce the same similarity bits.
+    With saliencies ((B, P1) and (B, P2), or (B, h, w) maps) the mask is combined with the two foreground conditions of the reference's
+    find_best_buddies_correspondences: saliency1[p] > thresh, and p is the nearest neighbour of at least one pixel q of feats2 with
+    saliency2[q] > thresh.  Either saliency may be given alone.  O(P) torch ops on the vectors of dense_match; cycle_index(nn12, nn21) is
+    the gather this mask compares with arange."""
+    nn12, sim12, nn21, _ = dense_match(feats1, feats2)
+    return _mutual_mask(nn12, nn21, saliency1, saliency2, thresh), nn12, sim12
+
+
+def dense_nn_correspondences(feats1, feats2):
+    """(points1, points2) in the layout of the reference's find_nn_correspondences (correspondence_utils.py:90-111): float32 (b, P, 2), points1 its
+    meshgrid of the (h, w) grid of feats2 (it derives the grid from the matrix's last axis and assumes a square one; here w and h are taken
+    from feats2, so square grids give the reference's values), points2 = (nn12 // h, nn12 % h).  Deliberate deviation: this function takes the two
+    maps, not the (b, P, P) matrix, which is never built (dense_match); the two maps must have the same number of pixels, as the reference's
+    expand() requires."""
+    w, h = feats2.shape[2], feats2.shape[3]
+    if feats1.shape[2] * feats1.shape[3] != w * h:
+        raise ValueError("find_nn_correspondences' layout needs maps of the same number of pixels")
+    nn12 = dense_match(feats1, feats2, "12")[0]
+    b = nn12.shape[0]
+    points1 = torch.stack(torch.meshgrid(torch.arange(w, device=nn12.device), torch.arange(h, device=nn12.device), indexing="ij"), dim=-1).expand((b, w, h, 2)).reshape((b, -1, 2))
+    points2 = torch.stack([nn12 // h, nn12 % h], dim=-1)
+    return points1.to(torch.float32), points2.to(torch.float32)
+
+
+def find_best_buddies_correspondences(descriptors1, descriptors2, saliency_map1, saliency_map2, num_pairs=10, thresh=0.05):
+    """The reference's function (correspondence_utils.py:230-323), same signature and return value: descriptors B x 1 x T x D of a square token
+    grid, saliency maps B x T -> (points1, points2), (k, 2) (y, x) in token coordinates of batch element 0 (y is the true quotient idx / n, a
+    float, as in the reference), k <= num_pairs; ([], []) if no pair survives.  The similarity matrix and its two max go through dense_match
+    (mutual_nn); the selection — k-means on the normalised concatenated descriptors of the surviving pairs, the most salient pair per
+    cluster — uses scikit-learn's KMeans(random_state=0) as the reference does."""
+    try:
+        from sklearn.cluster import KMeans
+    except ImportError as e:
+        raise ImportError("find_best_buddies_correspondences selects its pairs with scikit-learn's KMeans, which is not importable here; "
+                          "mutual_nn gives the best-buddies mask without it") from e
+    B, _, T, D = descriptors1.shape
+    n = int(np.sqrt(T))
+    f1 = descriptors1[:1, 0].permute(0, 2, 1)[..., None]                  # (1, D, T, 1): a logical (B, C, h, w) map, any strides
+    f2 = descriptors2[:1, 0].permute(0, 2, 1)[..., None]
+    sal1, sal2 = saliency_map1[0], saliency_map2[0]
+    mask, nn1, _ = mutual_nn(f1, f2, sal1[None], sal2[None], thresh)
+    mask, nn1 = mask[0], nn1[0]
+    d1 = descriptors1[0, 0, mask, :].float().cpu().numpy()
+    d2 = descriptors2[0, 0, nn1[mask], :].float().cpu().numpy()
+    both = np.concatenate((d1, d2), axis=1)
+    if len(both) == 0:
+        return [], []
+    both = both / np.sqrt((both ** 2).sum(axis=1))[:, None]
+    k = min(num_pairs, len(both))
+    labels = KMeans(n_clusters=k, random_state=0).fit(both).labels_
+    rank = ((sal1[mask] + sal2[nn1[mask]]) / 2).cpu().numpy()
+    best, pick = np.full(k, -np.inf), np.zeros(k, dtype=np.int64)
+    for i, (lab, rk) in enumerate(zip(labels, rank)):                     # the first pair of the highest mean saliency in every cluster
+        if rk > best[lab]:
+            best[lab], pick[lab] = rk, i
+    idx1 = torch.nonzero(mask, as_tuple=False).squeeze(1)[pick]
+    idx2 = nn1[idx1]
+    return torch.stack([idx1 / n, idx1 % n], dim=-1), torch.stack([idx2 / n, idx2 % n], dim=-1)
+
+
+CLIP_SCALE = 1 / 0.07                                 # exp(logit_scale) of the reference's AggregationNetwork (aggregation_network.py:25)
 
 
 class _ClipLoss(torch.autograd.Function):

@@ -342,6 +342,14 @@ enum { NN_MAXQ = 24, NN_FINE_BLOCKS = 1024 };
 size_t nn_match_workspace(int B, int N, int C, int h2, int w2);
 hipError_t launch_nn_match(const AggSrc& f1, const AggSrc& f2, int B, const float* points, int N, int LH, int LW, long long* out_yx,
                            float* out_score, void* workspace, hipStream_t s);
+// batch_cosine_sim + find_nn_correspondences / the two torch.max of find_best_buddies_correspondences (densematch.hip): for every pixel of f1 the pixel
+// of f2 with the highest cosine similarity and that cosine (nn12, sim12: (B, P1)), and the reverse (nn21, sim21: (B, P2)), from one MFMA pass over the
+// P1 x P2 matrix, which is never written.  f1 / f2 are logical (B, C, H, W) tensors (coff unused), P = H * W; either output pair may be null.  The
+// matrix is tiled DM_TILE x DM_TILE, C is padded to DM_KPAD; workspace of dense_match_workspace bytes, 16-byte aligned.
+enum { DM_TILE = 256, DM_KPAD = 64, DM_GROUP = 8, DM_MAXP = 1 << 30 };
+size_t dense_match_workspace(int B, int C, long P1, long P2, int f32_1, int f32_2);
+hipError_t launch_dense_match(const AggSrc& f1, const AggSrc& f2, int B, int* nn12, float* sim12, int* nn21, float* sim21, void* workspace,
+                              hipStream_t s);
 // compute_clip_loss of the correspondence evaluator (cliploss.hip): the symmetric cross-entropy of scale * cosine similarity between N source pixels of
 // f1 and N target pixels of f2 (flat indices (B, N) int64 on the device), without either P x P similarity matrix, and its gradient with respect to
 // both maps.  loss (B) fp32, terms (B, 2, N) fp32 or null.  The forward leaves the backward's state (cos, inverse norms, log-sum-exps, validity) in

@@ -503,6 +503,33 @@ int gdf_op_nn_match(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const f
   const AggSrc b{f2->ptr, f2->f32, f2->sb, f2->sc, f2->sy, f2->sx, f2->C, f2->H, f2->W, 0};
   return fin(launch_nn_match(a, b, B, points, N, LH, LW, out_yx, out_score, workspace, (hipStream_t)stream), "gdf_op_nn_match");
 }
+size_t gdf_op_dense_match_workspace(int B, int C, int P1, int P2, int f32_1, int f32_2) {
+  return dense_match_workspace(std::max(B, 1), std::max(C, 1), std::min(std::max(P1, 1), (int)DM_MAXP), std::min(std::max(P2, 1), (int)DM_MAXP),
+                               f32_1 != 0, f32_2 != 0);
+}
+int gdf_op_dense_match(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, int* nn12, float* sim12, int* nn21, float* sim21, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  auto bad = [](const char* msg) { set_error(std::string("gdf_op_dense_match: ") + msg); return GDF_ERR_ARG; };
+  auto big = [](const char* msg) { set_error(std::string("gdf_op_dense_match: ") + msg); return GDF_ERR_UNSUPPORTED; };
+  if (!f1 || !f2 || !workspace) return bad("null pointer");
+  if (!f1->ptr || !f2->ptr) return bad("null feature pointer");
+  if ((!nn12) != (!sim12) || (!nn21) != (!sim21)) return bad("an output pair is given whole or not at all");
+  if (!nn12 && !nn21) return bad("both output pairs are null");
+  if (B < 0) return bad("B >= 0");
+  if (f1->C < 1 || f1->H < 1 || f1->W < 1 || f2->C < 1 || f2->H < 1 || f2->W < 1) return bad("C, H and W >= 1");
+  if (f1->C != f2->C) return bad("the two maps differ in C");
+  if ((uintptr_t)workspace & 15) return bad("the workspace must be 16-byte aligned");
+  const long long P1 = (long long)f1->H * f1->W, P2 = (long long)f2->H * f2->W;
+  if (B > 65535) return big("B > 65535; split the batch");
+  if (P1 > DM_MAXP || P2 > DM_MAXP) return big("more than 2^30 pixels in a map (32-bit indices)");
+  if (((P1 + DM_TILE - 1) / DM_TILE) * ((P2 + DM_TILE - 1) / DM_TILE) >= (1ll << 31)) return big("2^31 tiles or more; split a map");
+  if (workspace_bytes < gdf_op_dense_match_workspace(B, f1->C, (int)P1, (int)P2, f1->f32, f2->f32))
+    return bad("workspace smaller than gdf_op_dense_match_workspace says");
+  if (B == 0) return GDF_OK;
+  const AggSrc a{f1->ptr, f1->f32, f1->sb, f1->sc, f1->sy, f1->sx, f1->C, f1->H, f1->W, 0};
+  const AggSrc b{f2->ptr, f2->f32, f2->sb, f2->sc, f2->sy, f2->sx, f2->C, f2->H, f2->W, 0};
+  return fin(launch_dense_match(a, b, B, nn12, sim12, nn21, sim21, workspace, (hipStream_t)stream), "gdf_op_dense_match");
+}
 size_t gdf_op_clip_loss_workspace(int B, int N, int C, int P1, int P2) {
   return clip_loss_workspace(std::max(B, 1), std::max(N, 1), std::max(C, 1), std::max(P1, 1), std::max(P2, 1));
 }

@@ -630,6 +630,15 @@ class FeatureExtractor(nn.Module):
         from components.postproc import nn_match
         return nn_match(feats1, feats2, source_points, load_size)
 
+    def match(self, feats1, feats2, mutual=False):
+        """Dense matching of two maps (reference correspondence/correspondence/correspondence_utils.py:73-111, batch_cosine_sim +
+        find_nn_correspondences, and the two torch.max of find_best_buddies_correspondences): for every pixel of feats1 its best pixel of feats2 by
+        cosine similarity and the reverse -> (nn12 int64 (B, P1), sim12 fp32, nn21 int64 (B, P2), sim21 fp32); mutual=True: the mutual
+        nearest-neighbour mask instead -> (mask (B, P1) bool, nn12, sim12).  Device tensors: gdf_op_dense_match, the P1 x P2 matrix is never
+        built (components/postproc.py dense_match, mutual_nn)."""
+        from components.postproc import dense_match, mutual_nn
+        return mutual_nn(feats1, feats2) if mutual else dense_match(feats1, feats2)
+
     def correspondence_loss(self, feats1, feats2, source_points, target_points, scale=None):
         """The correspondence evaluator's loss (reference correspondence/task-corres.py:70-80, compute_clip_loss) on two maps from hyperfeature()
         or aggregate(): the symmetric cross-entropy of scale * cosine similarity between the N source pixels of feats1 and the N target pixels of

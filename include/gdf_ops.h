@@ -343,6 +343,32 @@ int gdf_op_aggregate(const gdf_agg_src* srcs, int n, int B, void* out, int out_f
 size_t gdf_op_nn_match_workspace(int B, int N, int C, int h2, int w2);
 int gdf_op_nn_match(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const float* points /* device, (B, N, 2) */, int N, int LH, int LW,
                     long long* out_yx /* (B, N, 2) */, float* out_score /* (B, N) */, void* workspace, size_t workspace_bytes, void* stream);
+/* Dense matching of two descriptor maps (correspondence/correspondence/correspondence_utils.py:73-111, batch_cosine_sim + find_nn_correspondences,
+ * and :264-274, the similarity matrix and the two torch.max of find_best_buddies_correspondences): both maps flattened and L2-normalised,
+ * sims = f1^ @ f2^T (B, P1, P2), argmax / max along both axes — computed WITHOUT the matrix (csrc/densematch.hip): one tiled MFMA
+ * pass with fp32 accumulation whose epilogue reduces each 256 x 256 tile to per-row and per-column (score, index) partials.
+ *   f1, f2     logical (B, C, H, W) tensors, fp16 (f32 = 0) or fp32 independently, with element strides sb/sc/sy/sx (NCHW, channels-last or any
+ *              other), read only and once; the two C must agree, the grids need not (P1 = H1 W1, P2 = H2 W2, pixel p = y W + x); `coff` is ignored.
+ *   operands   an fp16 map enters the product as it is, its 1 / ||v|| (fp32) is applied in the epilogue: the fp16 x fp16 products are exact in the
+ *              fp32 accumulator.  An fp32 map is normalised in fp32 and enters as a scaled fp16 (hi, lo) pair: two or three MFMA passes per K
+ *              step, lo x lo dropped.  The order of summation over C is the same for every pixel pair.
+ *   score      s[p1, p2] = (dot * r1[p1]) * r2[p2], evaluated once in fp32; both directions reduce these same bits, so nn21[nn12[p]] == p is a
+ *              consistent mutual-nearest-neighbour test.  Error bound on the cosine: (2 C + 16) 2^-24 for fp16 maps (tests/dense_match_ref.py
+ *              derives it, and the term of an fp32 map).
+ *   outputs    nn12 (B, P1) int32: the LOWEST p2 of maximal computed score (argmax's rule), sim12 (B, P1) fp32: the score there; nn21 (B, P2),
+ *              sim21 (B, P2) likewise for every pixel of f2 over the pixels of f1.  A pair (nn12, sim12) or (nn21, sim21) may be null: that
+ *              direction is not reduced and nothing of it is written.  Half a pair, or both pairs null: GDF_ERR_ARG.
+ *   zero norms a pixel whose computed norm is not positive and finite never wins; its own row (column), or one that no pixel answers, returns
+ *              index 0 and a NaN score, as gdf_op_nn_match does — the reference propagates NaN here.
+ *   workspace  gdf_op_dense_match_workspace(B, C, P1, P2, f32_1, f32_2) bytes, 16-byte aligned, caller-owned, contents undefined before and
+ *              after: the fp16 operand panels (2 bytes per element of an fp16 map, 4 of an fp32 map, pixels padded to 256 and C to 64), the
+ *              reciprocal norms and the tile partials.
+ * Stream-ordered, no allocation, no atomics, nothing read back; the same inputs give the same bits on any stream, on repeated calls and at any
+ * batch position.  A null map, C, H or W below 1, differing C, B < 0, a misaligned or too small workspace: GDF_ERR_ARG before any launch.
+ * B > 65535, a map of more than 2^30 pixels, or 2^31 tiles or more: GDF_ERR_UNSUPPORTED.  B == 0 is a successful no-op. */
+size_t gdf_op_dense_match_workspace(int B, int C, int P1, int P2, int f32_1, int f32_2);
+int gdf_op_dense_match(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, int* nn12 /* (B, P1) */, float* sim12 /* (B, P1) */,
+                       int* nn21 /* (B, P2) */, float* sim21 /* (B, P2) */, void* workspace, size_t workspace_bytes, void* stream);
 /* The correspondence evaluator's loss on two hyperfeature maps (correspondence/task-corres.py:70-80, compute_clip_loss, called per image pair from
  * validate() :103 and per step from train() :159) and its gradient with respect to both maps — computed WITHOUT either P x P similarity matrix
  * (csrc/cliploss.hip).  With a^_p = f1[:, p] / ||f1[:, p]|| and b^_p likewise for f2 (pixel p = y W + x):
