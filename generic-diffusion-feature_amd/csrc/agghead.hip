@@ -22,24 +22,15 @@
 // Workgroups are numbered so that the pixel tiles of one 256-row block follow one another ON ONE XCD (they share the block's packed rows through
 // that XCD's L2).  Every tile lies inside one image.  No atomics, no split-K, fixed summation order, stream-ordered, no allocation in a launch.
 #include <math.h>
-#include <string.h>
 
 #include <algorithm>
 #include <vector>
 
-#include "kernels.h"
+#include "feat_common.h"
 
 namespace gdf {
 
 namespace {
-
-typedef _Float16 ah_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 ah_f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 ah_f16x2 __attribute__((ext_vector_type(2)));
-typedef float ah_f32x16 __attribute__((ext_vector_type(16)));
-typedef float ah_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned ah_u32x4 __attribute__((ext_vector_type(4)));
-#define AH_LDS __attribute__((address_space(3)))
 
 enum {
   AH_PW = 32, AH_PH = 4,             // pixel patch of a workgroup: one MFMA column block per patch row
@@ -52,21 +43,13 @@ enum {
   AH_ROWS = 256,                     // output channels per workgroup
   AH_STEPS = 9 * AH_KT / 16,         // MFMA k-steps per tile: [tap][16-channel step]
   AH_NW = 3,                         // weight fragments in registers (the one in use and two ahead); divides AH_STEPS
-  AH_XCDS = 8,
 };
 
 struct AhArgs {
   const void* x; long sb, sc, sy, sx; int C, H, W;
-  const ah_u32x4* w; const float *inv_s, *bias; float* out;
+  const u32x4* w; const float *inv_s, *bias; float* out;
   int Cout, nkt, nrb, tx, ty; long ntile; unsigned chunk; long total;
 };
-
-template <typename T> struct AhVec;
-template <> struct AhVec<_Float16> { typedef ah_f16x8 type; enum { V = 8 }; };
-template <> struct AhVec<float> { typedef ah_f32x4 type; enum { V = 4 }; };
-
-// every wave's LDS writes have landed and every wave's LDS reads have returned; global loads stay in flight (a __syncthreads() would drain them)
-__device__ __forceinline__ void ah_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // T: the map's element type.  CL: channels-last map (sc == 1, C a multiple of the 16-byte vector, aligned pixels): 16-byte loads along C; otherwise
 // two elements per thread and load with the map's own strides, lanes along the patch row (coalesced where sx == 1).
@@ -75,14 +58,14 @@ __global__ __launch_bounds__(AH_NT) void ah_conv_kernel(const AhArgs a) {
   constexpr bool F32 = sizeof(T) == 4;
   constexpr int NIMG = F32 ? 2 : 1;              // x images of a tile: hi (and lo)
   constexpr int BUF = NIMG * AH_IMG;             // bytes of one of the two staging buffers
-  constexpr int V = AhVec<T>::V;
+  constexpr int V = MapVec<T>::V;
   constexpr int NCHP = AH_KT / V;                // CL: 16-byte chunks per pixel and tile
   constexpr int NIT = CL ? (AH_NPX * NCHP + AH_NT - 1) / AH_NT : AH_KT / 4;   // staging items per thread
-  typedef typename AhVec<T>::type vt;
+  typedef typename MapVec<T>::type vt;
   extern __shared__ __attribute__((aligned(16))) char ah_smem[];
 
-  // (row block, pixel tile) of this workgroup: consecutive numbers on one XCD (workgroups go round-robin over the XCDs)
-  const long L = (long)(blockIdx.x % AH_XCDS) * a.chunk + blockIdx.x / AH_XCDS;
+  // (row block, pixel tile) of this workgroup: consecutive numbers on one XCD
+  const long L = xcd_slot(blockIdx.x, a.chunk);
   if (L >= a.total) return;                      // (whole workgroups, before any barrier)
   const int cb = (int)(L / a.ntile);
   const long tile = L % a.ntile;
@@ -135,46 +118,46 @@ __global__ __launch_bounds__(AH_NT) void ah_conv_kernel(const AhArgs a) {
       if (loff[CL ? i : 0] < 0) continue;
       char* d = buf + loff[CL ? i : 0] + (CL ? 0 : 8 * i);
       if constexpr (CL && !F32) {
-        *(ah_f16x8*)d = xv[i];
+        *(f16x8*)d = xv[i];
       } else if constexpr (CL) {
-        ah_f16x4 hi, lo;
+        f16x4 hi, lo;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           hi[j] = f32_to_f16_sat(xv[i][j]);
           lo[j] = f32_to_f16_sat(xv[i][j] - (float)hi[j]);
         }
-        *(ah_f16x4*)d = hi;
-        *(ah_f16x4*)(d + AH_IMG) = lo;
+        *(f16x4*)d = hi;
+        *(f16x4*)(d + AH_IMG) = lo;
       } else if constexpr (F32) {
-        ah_f16x2 hi, lo;
+        f16x2 hi, lo;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           hi[j] = f32_to_f16_sat(xe[i][j]);
           lo[j] = f32_to_f16_sat(xe[i][j] - (float)hi[j]);
         }
-        *(ah_f16x2*)d = hi;
-        *(ah_f16x2*)(d + AH_IMG) = lo;
+        *(f16x2*)d = hi;
+        *(f16x2*)(d + AH_IMG) = lo;
       } else {
-        ah_f16x2 v;
+        f16x2 v;
         v[0] = xe[i][0];
         v[1] = xe[i][1];
-        *(ah_f16x2*)d = v;
+        *(f16x2*)d = v;
       }
     }
   };
 
   // ---- weights: fragment g of this wave's row block is step g % 18 of tile g / 18; [hi, lo] x 64 lanes x 16 bytes each ----
   const long gend = (long)a.nkt * AH_STEPS;
-  const ah_u32x4* wp = a.w + (size_t)(active ? rb : 0) * (size_t)gend * 2 * 64 + lane;
-  ah_u32x4 whi[AH_NW], wlo[AH_NW];
+  const u32x4* wp = a.w + (size_t)(active ? rb : 0) * (size_t)gend * 2 * 64 + lane;
+  u32x4 whi[AH_NW], wlo[AH_NW];
   auto load_w = [&](int slot, long g) {
     if (!active) return;
-    const ah_u32x4* p = wp + (size_t)(g < gend ? g : gend - 1) * 2 * 64;   // (past the end: the last fragment again, unused)
+    const u32x4* p = wp + (size_t)(g < gend ? g : gend - 1) * 2 * 64;   // (past the end: the last fragment again, unused)
     whi[slot] = p[0];
     wlo[slot] = p[64];
   };
 
-  ah_f32x16 acc[AH_PH], tot[AH_PH];
+  f32x16 acc[AH_PH], tot[AH_PH];
 #pragma unroll
   for (int j = 0; j < AH_PH; ++j)
 #pragma unroll
@@ -188,9 +171,9 @@ __global__ __launch_bounds__(AH_NT) void ah_conv_kernel(const AhArgs a) {
   load_w(1, 1);
   store_x(ah_smem);
   if (a.nkt > 1) load_x(1);
-  ah_barrier();
+  lds_barrier();
   for (int kt = 0; kt < a.nkt; ++kt) {
-    AH_LDS const char* cur = (AH_LDS const char*)(ah_smem + (kt & 1) * BUF) + xl;
+    GDF_LDS const char* cur = (GDF_LDS const char*)(ah_smem + (kt & 1) * BUF) + xl;
     // the other buffer was last read in tile kt - 1, which every wave has left: tile kt + 1 goes there now, and tile kt + 2 sets out
     if (kt + 1 < a.nkt) store_x(ah_smem + ((kt + 1) & 1) * BUF);
     if (kt + 2 < a.nkt) load_x(kt + 2);
@@ -200,13 +183,13 @@ __global__ __launch_bounds__(AH_NT) void ah_conv_kernel(const AhArgs a) {
         constexpr int NS = AH_KT / 16;
         const int tap = st / NS, s = st % NS, dy = tap / 3, dx = tap % 3;
         load_w((st + 2) % AH_NW, (long)kt * AH_STEPS + st + 2);
-        const ah_f16x8 ahi = __builtin_bit_cast(ah_f16x8, whi[st % AH_NW]), alo = __builtin_bit_cast(ah_f16x8, wlo[st % AH_NW]);
-        ah_f16x8 xf[NIMG][AH_PH];
+        const f16x8 ahi = __builtin_bit_cast(f16x8, whi[st % AH_NW]), alo = __builtin_bit_cast(f16x8, wlo[st % AH_NW]);
+        f16x8 xf[NIMG][AH_PH];
 #pragma unroll
         for (int im = 0; im < NIMG; ++im)
 #pragma unroll
           for (int j = 0; j < AH_PH; ++j)
-            xf[im][j] = *(AH_LDS const ah_f16x8*)(cur + im * AH_IMG + ((j + dy) * AH_LW + dx) * AH_PST + s * 32);
+            xf[im][j] = *(GDF_LDS const f16x8*)(cur + im * AH_IMG + ((j + dy) * AH_LW + dx) * AH_PST + s * 32);
 #pragma unroll
         for (int j = 0; j < AH_PH; ++j) {
           acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(alo, xf[0][j], acc[j], 0, 0, 0);
@@ -222,7 +205,7 @@ __global__ __launch_bounds__(AH_NT) void ah_conv_kernel(const AhArgs a) {
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
       }
     }
-    ah_barrier();
+    lds_barrier();
   }
 
   // accumulator register r of lane (q, lh) is row 8 (r / 4) + 4 lh + r % 4 (the output channel), column q (the pixel of patch row j): the lanes
@@ -248,32 +231,23 @@ hipError_t ah_launch(const AhArgs& a, unsigned grid, hipStream_t s) {
   return hipGetLastError();
 }
 
-size_t ah_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-uint16_t ah_half_bits(float v) {                 // round to nearest even, subnormals included (|v| < 2^14 here)
-  const _Float16 h = (_Float16)v;
-  uint16_t u;
-  memcpy(&u, &h, 2);
-  return u;
-}
-
-// the device image of a head: [packed fragments][1 / scale][bias]
-struct AhLayout { int nkt, nrb; size_t blk, o_is, o_b, bytes; };
-AhLayout ah_layout(int Cin, int Cout) {
+// the device image of a head at `base` (null: the sizes alone): [packed fragments][1 / scale][bias]
+struct AhLayout { int nkt, nrb; size_t blk; char* w; float *inv_s, *bias; size_t bytes; };
+AhLayout ah_layout(int Cin, int Cout, void* base) {
   AhLayout l;
   l.nkt = (Cin + AH_KT - 1) / AH_KT;
   l.nrb = (Cout + 31) / 32;
   l.blk = (size_t)l.nkt * AH_STEPS * 2 * 64 * 8;                            // halves of one 32-row block
-  l.o_is = ah_up256((size_t)l.nrb * l.blk * 2);
-  l.o_b = l.o_is + ah_up256((size_t)l.nrb * 32 * 4);
-  l.bytes = l.o_b + ah_up256((size_t)l.nrb * 32 * 4);
+  Carver c(base);
+  l.w = c.take<char>((size_t)l.nrb * l.blk * 2);
+  l.inv_s = c.take<float>((size_t)l.nrb * 32 * 4);
+  l.bias = c.take<float>((size_t)l.nrb * 32 * 4);
+  l.bytes = c.bytes();
   return l;
 }
 
-__device__ __forceinline__ int ah_shift_of(float m) { return (m > 0.f && m < INFINITY) ? 13 - ilogbf(m) : 0; }
-
-// agghead_create's rule for one row on the device: the row's largest magnitude, sh = 13 - ilogb(max) (0 for a zero or non-finite maximum) and
-// 1 / scale = 2^-sh; rows from Cout up to the end of the last 32-row block get 1
+// agghead_create's rule for one row on the device: the row's largest magnitude, sh = split_shift(max) and 1 / scale = 2^-sh; rows from Cout up
+// to the end of the last 32-row block get 1
 __global__ __launch_bounds__(256) void ah_rowscale_kernel(const float* __restrict__ W, int Cout, long rowlen, float* inv_s) {
   __shared__ float red[256];
   const int co = blockIdx.x, t = threadIdx.x;
@@ -286,7 +260,7 @@ __global__ __launch_bounds__(256) void ah_rowscale_kernel(const float* __restric
     if (t < s) red[t] = fmaxf(red[t], red[t + s]);
     __syncthreads();
   }
-  if (t == 0) inv_s[co] = ldexpf(1.f, -ah_shift_of(red[0]));
+  if (t == 0) inv_s[co] = ldexpf(1.f, -split_shift(red[0]));
 }
 
 // One thread = one lane entry (32-row block, channel tile, 16-channel step, lane) of the fragment image: 8 channels x 9 taps of one row, 72
@@ -294,7 +268,7 @@ __global__ __launch_bounds__(256) void ah_rowscale_kernel(const float* __restric
 // row's shift is read back from 1 / scale = 2^-sh (an exact power of two, subnormals included), so the handle needs no scratch; only where 2^-sh
 // has underflowed to 0 (a row whose largest magnitude is below 2^-136) the thread finds the row's maximum again.
 __global__ __launch_bounds__(256) void ah_pack_kernel(const float* __restrict__ W, const float* __restrict__ inv_s, int Cin, int Cout, int nkt,
-                                                      long n, ah_u32x4* img) {
+                                                      long n, u32x4* img) {
   const long id = (long)blockIdx.x * 256 + threadIdx.x;
   if (id >= n) return;
   const int lane = (int)(id & 63), s = (int)((id >> 6) & 1), kt = (int)((id >> 7) % nkt);
@@ -308,34 +282,33 @@ __global__ __launch_bounds__(256) void ah_pack_kernel(const float* __restrict__ 
     } else {
       float m = 0.f;
       for (long i = 0; i < (long)Cin * 9; ++i) m = fmaxf(m, fabsf(W[(long)co * Cin * 9 + i]));
-      shv = ah_shift_of(m);
+      shv = split_shift(m);
     }
   }
-  ah_u32x4* o = img + ((rb * nkt + kt) * 9 * (AH_KT / 16) + s) * 2 * 64 + lane;
+  u32x4* o = img + ((rb * nkt + kt) * 9 * (AH_KT / 16) + s) * 2 * 64 + lane;
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
-    ah_f16x8 hi, lo;
+    f16x8 hi, lo;
 #pragma unroll
     for (int el = 0; el < 8; ++el) {
       const float v = (co < Cout && ci0 + el < Cin) ? ldexpf(W[((long)co * Cin + ci0 + el) * 9 + tap], shv) : 0.f;
       hi[el] = (_Float16)v;
       lo[el] = (_Float16)(v - (float)hi[el]);
     }
-    o[(long)tap * (AH_KT / 16) * 2 * 64] = __builtin_bit_cast(ah_u32x4, hi);
-    o[(long)tap * (AH_KT / 16) * 2 * 64 + 64] = __builtin_bit_cast(ah_u32x4, lo);
+    o[(long)tap * (AH_KT / 16) * 2 * 64] = __builtin_bit_cast(u32x4, hi);
+    o[(long)tap * (AH_KT / 16) * 2 * 64 + 64] = __builtin_bit_cast(u32x4, lo);
   }
 }
 
 }  // namespace
 
 hipError_t agghead_create(int Cin, int Cout, const float* W, const float* bias, AggHead** out) {
-  const AhLayout l = ah_layout(Cin, Cout);
-  const int nkt = l.nkt, nrb = l.nrb;
-  const size_t blk = l.blk, o_is = l.o_is, o_b = l.o_b;
   void* dev = nullptr;
-  hipError_t e = hipMalloc(&dev, l.bytes);
+  hipError_t e = hipMalloc(&dev, ah_layout(Cin, Cout, nullptr).bytes);
   if (e != hipSuccess) return e;
-  char* d = (char*)dev;
+  const AhLayout l = ah_layout(Cin, Cout, dev);
+  const int nkt = l.nkt, nrb = l.nrb;
+  const size_t blk = l.blk;
   // one 32-row block at a time (the packed image of the largest head is close to 1 GB: it is never held on the host as a whole)
   std::vector<uint16_t> img(blk);
   std::vector<float> inv((size_t)nrb * 32, 1.f), bs((size_t)nrb * 32, 0.f);
@@ -348,8 +321,7 @@ hipError_t agghead_create(int Cin, int Cout, const float* W, const float* bias, 
       const float* row = W + (size_t)co * rowlen;
       float mx = 0.f;
       for (size_t i = 0; i < rowlen; ++i) mx = std::max(mx, fabsf(row[i]));
-      // the power of two that puts the row's largest magnitude into [2^13, 2^14): the low half stays clear of the fp16 subnormals
-      const int sh = (mx > 0.f && std::isfinite(mx)) ? 13 - ilogbf(mx) : 0;
+      const int sh = split_shift(mx);
       inv[co] = ldexpf(1.f, -sh);
       if (bias) bs[co] = bias[co];
       for (int ci = 0; ci < Cin; ++ci) {
@@ -358,17 +330,17 @@ hipError_t agghead_create(int Cin, int Cout, const float* W, const float* bias, 
           const float v = ldexpf(row[(size_t)ci * 9 + tap], sh);
           const _Float16 hi = (_Float16)v;
           uint16_t* dh = img.data() + (((((size_t)kt * 9 + tap) * (AH_KT / 16) + s) * 2 + 0) * 64 + lh * 32 + n) * 8 + el;
-          dh[0] = ah_half_bits((float)hi);
-          dh[64 * 8] = ah_half_bits(v - (float)hi);
+          dh[0] = half_bits((float)hi);
+          dh[64 * 8] = half_bits(v - (float)hi);
         }
       }
     }
-    e = hipMemcpy(d + (size_t)rb * blk * 2, img.data(), blk * 2, hipMemcpyHostToDevice);
+    e = hipMemcpy(l.w + (size_t)rb * blk * 2, img.data(), blk * 2, hipMemcpyHostToDevice);
   }
-  if (e == hipSuccess) e = hipMemcpy(d + o_is, inv.data(), inv.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + o_b, bs.data(), bs.size() * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(l.inv_s, inv.data(), inv.size() * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(l.bias, bs.data(), bs.size() * 4, hipMemcpyHostToDevice);
   if (e != hipSuccess) { (void)hipFree(dev); return e; }
-  *out = new AggHead{Cin, Cout, nkt, nrb, dev, (const void*)d, (const float*)(d + o_is), (const float*)(d + o_b)};
+  *out = new AggHead{Cin, Cout, nkt, nrb, dev, l.w, l.inv_s, l.bias};
   return hipSuccess;
 }
 
@@ -380,19 +352,18 @@ hipError_t agghead_update(AggHead* h, const float* W_dev, hipStream_t s) {
   if (e != hipSuccess) return e;
   const long n = (long)h->nrb * h->nkt * 2 * 64;
   hipLaunchKernelGGL(ah_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W_dev, h->inv_s, h->Cin, h->Cout, h->nkt, n,
-                     (ah_u32x4*)h->w);
+                     (u32x4*)h->w);
   return hipGetLastError();
 }
 
 hipError_t agghead_create_device(int Cin, int Cout, const float* W_dev, const float* bias_dev, hipStream_t s, AggHead** out) {
-  const AhLayout l = ah_layout(Cin, Cout);
   void* dev = nullptr;
-  hipError_t e = hipMalloc(&dev, l.bytes);
+  hipError_t e = hipMalloc(&dev, ah_layout(Cin, Cout, nullptr).bytes);
   if (e != hipSuccess) return e;
-  char* d = (char*)dev;
-  AggHead* h = new AggHead{Cin, Cout, l.nkt, l.nrb, dev, (const void*)d, (const float*)(d + l.o_is), (const float*)(d + l.o_b)};
-  e = hipMemsetAsync(d + l.o_b, 0, (size_t)l.nrb * 32 * 4, s);
-  if (e == hipSuccess && bias_dev) e = hipMemcpyAsync(d + l.o_b, bias_dev, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s);
+  const AhLayout l = ah_layout(Cin, Cout, dev);
+  AggHead* h = new AggHead{Cin, Cout, l.nkt, l.nrb, dev, l.w, l.inv_s, l.bias};
+  e = hipMemsetAsync(l.bias, 0, (size_t)l.nrb * 32 * 4, s);
+  if (e == hipSuccess && bias_dev) e = hipMemcpyAsync(l.bias, bias_dev, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s);
   if (e == hipSuccess) e = agghead_update(h, W_dev, s);
   if (e != hipSuccess) { agghead_destroy(h); return e; }
   *out = h;
@@ -411,13 +382,12 @@ hipError_t launch_agghead(const AggHead* h, const AggSrc& x, int B, float* out, 
   if (B == 0) return hipSuccess;
   const int tx = (x.W + AH_PW - 1) / AH_PW, ty = (x.H + AH_PH - 1) / AH_PH;
   const long ntile = (long)B * tx * ty, total = ntile * ((h->Cout + AH_ROWS - 1) / AH_ROWS);
-  const long chunk = (total + AH_XCDS - 1) / AH_XCDS;
-  if (chunk * AH_XCDS >= (1l << 31)) return hipErrorInvalidValue;
-  const AhArgs a{x.ptr, x.sb, x.sc, x.sy, x.sx, x.C, x.H, x.W, (const ah_u32x4*)h->w, h->inv_s, h->bias, out,
+  const long chunk = xcd_chunk(total);
+  if (chunk * XCDS >= (1l << 31)) return hipErrorInvalidValue;
+  const AhArgs a{x.ptr, x.sb, x.sc, x.sy, x.sx, x.C, x.H, x.W, (const u32x4*)h->w, h->inv_s, h->bias, out,
                  h->Cout, h->nkt, h->nrb, tx, ty, ntile, (unsigned)chunk, total};
-  const long vl = x.f32 ? 4 : 8;                 // (launch_pixcls's rule)
-  const bool cl = x.sc == 1 && !(x.C % vl) && !((uintptr_t)x.ptr & 15) && !(x.sb % vl) && !(x.sy % vl) && !(x.sx % vl);
-  const unsigned grid = (unsigned)(chunk * AH_XCDS);
+  const bool cl = map_lanes_c(x);
+  const unsigned grid = (unsigned)(chunk * XCDS);
   if (x.f32) return cl ? ah_launch<float, true>(a, grid, s) : ah_launch<float, false>(a, grid, s);
   return cl ? ah_launch<_Float16, true>(a, grid, s) : ah_launch<_Float16, false>(a, grid, s);
 }

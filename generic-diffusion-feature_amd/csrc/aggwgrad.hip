@@ -26,17 +26,11 @@
 // that XCD's L2).  No atomics, no split-K, fixed summation order, stream-ordered, no allocation in a launch.
 #include <math.h>
 
-#include "kernels.h"
+#include "feat_common.h"
 
 namespace gdf {
 
 namespace {
-
-typedef _Float16 wg_f16x8 __attribute__((ext_vector_type(8)));
-typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
-typedef float wg_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned wg_u32x4 __attribute__((ext_vector_type(4)));
-#define WG_LDS __attribute__((address_space(3)))
 
 enum {
   WG_PW = 32, WG_PH = 4,             // pixel patch of one staging round: two k-steps per patch row
@@ -50,21 +44,17 @@ enum {
   WG_ROWS = 128,                     // output channels per workgroup
   WG_KS = WG_PH * WG_PW / 16,        // k-steps per patch
   WG_NG = 4,                         // G fragment pairs in registers (the one in use and three ahead); divides WG_KS
-  WG_XCDS = 8,
   WG_NPAIR = WG_CT * (WG_PW + 2),    // (channel, staged column) pairs of a patch
   WG_NSLOT = (WG_NPAIR + WG_NT - 1) / WG_NT,   // pairs per thread; each pair is WG_LH elements, one per staged row
 };
 
 struct WgArgs {
   const void* x; long sb, sc, sy, sx; int C, H, W;
-  const wg_u32x4* gs; const int* sh; float* dw;
+  const u32x4* gs; const int* sh; float* dw;
   int Cout, nct, nrb, accumulate; long ntile; unsigned chunk; long total;
 };
 
-// every wave's LDS writes have landed and every wave's LDS reads have returned; global loads stay in flight
-__device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// max |G| over (b, y, x) of one output channel -> mx[co], and the shift that puts it into [2^13, 2^14) -> sh[co] (0 for a zero or non-finite maximum)
+// max |G| over (b, y, x) of one output channel -> mx[co], and its split_shift -> sh[co]
 __global__ __launch_bounds__(256) void wg_rowmax_kernel(const float* __restrict__ g, int B, int Cout, long P, float* mx, int* sh) {
   __shared__ float red[256];
   const int co = blockIdx.x, t = threadIdx.x;
@@ -82,14 +72,14 @@ __global__ __launch_bounds__(256) void wg_rowmax_kernel(const float* __restrict_
   if (t == 0) {
     m = red[0];
     mx[co] = m;
-    sh[co] = (m > 0.f && m < INFINITY) ? 13 - ilogbf(m) : 0;
+    sh[co] = split_shift(m);
   }
 }
 
 // One thread = one lane entry of G's fragment image: (32-row block, k-step, lane (q, lh)) holds row 32 block + q, pixels 8 lh .. 8 lh + 7 of the
 // k-step; k-step 8 patch + st is patch row st / 2, pixels 16 (st % 2) .. + 15 of it; patches run along x, then y, then the images.
 __global__ __launch_bounds__(256) void wg_split_kernel(const float* __restrict__ g, const int* __restrict__ sh, int Cout, int H, int W, int tx,
-                                                       int ty, long nks, long n, wg_u32x4* gs) {
+                                                       int ty, long nks, long n, u32x4* gs) {
   const long id = (long)blockIdx.x * 256 + threadIdx.x;
   if (id >= n) return;
   const int lane = (int)(id & 63), q = lane & 31, lh = lane >> 5;
@@ -101,16 +91,16 @@ __global__ __launch_bounds__(256) void wg_split_kernel(const float* __restrict__
   const bool ok = co < Cout && y < H;
   const long off = ok ? (((long)b * Cout + co) * H + y) * W + xs : 0;
   const int shv = ok ? sh[co] : 0;
-  wg_f16x8 hi, lo;
+  f16x8 hi, lo;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const float v = (ok && xs + j < W) ? ldexpf(g[off + j], shv) : 0.f;
     hi[j] = f32_to_f16_sat(v);
     lo[j] = f32_to_f16_sat(v - (float)hi[j]);
   }
-  wg_u32x4* o = gs + (size_t)(id >> 6) * 128 + lane;
-  o[0] = __builtin_bit_cast(wg_u32x4, hi);
-  o[64] = __builtin_bit_cast(wg_u32x4, lo);
+  u32x4* o = gs + (size_t)(id >> 6) * 128 + lane;
+  o[0] = __builtin_bit_cast(u32x4, hi);
+  o[64] = __builtin_bit_cast(u32x4, lo);
 }
 
 // T: the map's element type.  The map is read with its own strides, lanes along the staged row (coalesced where sx == 1).
@@ -120,8 +110,8 @@ __global__ __launch_bounds__(WG_NT) void wg_kernel(const WgArgs a) {
   constexpr int NIMG = F32 ? 2 : 1;              // x images: hi (and lo)
   __shared__ __attribute__((aligned(16))) char wg_smem[NIMG * WG_IMG];
 
-  // (row block, channel tile) of this workgroup: consecutive numbers on one XCD (workgroups go round-robin over the XCDs)
-  const long L = (long)(blockIdx.x % WG_XCDS) * a.chunk + blockIdx.x / WG_XCDS;
+  // (row block, channel tile) of this workgroup: consecutive numbers on one XCD
+  const long L = xcd_slot(blockIdx.x, a.chunk);
   if (L >= a.total) return;                      // (whole workgroups, before any barrier)
   const int cb = (int)(L / a.nct), ct = (int)(L % a.nct);
 
@@ -130,7 +120,7 @@ __global__ __launch_bounds__(WG_NT) void wg_kernel(const WgArgs a) {
   const bool active = rb < a.nrb;                // (wave-uniform) a block past Cout: the wave stages and waits, nothing else
 
   // the margins and the pad are never staged: give them a value once (the halves beside the staged columns are read and shifted out)
-  for (int i = t * 16; i < NIMG * WG_IMG; i += WG_NT * 16) *(wg_u32x4*)(wg_smem + i) = (wg_u32x4)0u;
+  for (int i = t * 16; i < NIMG * WG_IMG; i += WG_NT * 16) *(u32x4*)(wg_smem + i) = (u32x4)0u;
   __syncthreads();
 
   // ---- staging.  Pair t + 256 j of a thread is channel pair / 34, staged column pair % 34 (global x = x0 + column - 1); its six elements are
@@ -175,23 +165,23 @@ __global__ __launch_bounds__(WG_NT) void wg_kernel(const WgArgs a) {
 
   // ---- G: fragment pair g of this wave's row block is k-step g % 8 of patch g / 8; [hi, lo] x 64 lanes x 16 bytes each ----
   const long gend = a.ntile * WG_KS;
-  const wg_u32x4* gp = a.gs + (size_t)(active ? rb : 0) * (size_t)gend * 2 * 64 + lane;
-  wg_u32x4 ghi[WG_NG], glo[WG_NG];
+  const u32x4* gp = a.gs + (size_t)(active ? rb : 0) * (size_t)gend * 2 * 64 + lane;
+  u32x4 ghi[WG_NG], glo[WG_NG];
   auto load_g = [&](int slot, long g) {
     if (!active) return;
-    const wg_u32x4* p = gp + (size_t)(g < gend ? g : gend - 1) * 2 * 64;     // (past the end: the last pair again, unused)
+    const u32x4* p = gp + (size_t)(g < gend ? g : gend - 1) * 2 * 64;     // (past the end: the last pair again, unused)
     ghi[slot] = p[0];
     glo[slot] = p[64];
   };
 
-  wg_f32x16 acc[9], tot[9];
+  f32x16 acc[9], tot[9];
 #pragma unroll
   for (int j = 0; j < 9; ++j)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[j][r] = tot[j][r] = 0.f;
 
   // B operand of lane (q, lh): channel q of the tile, pixels 8 lh .. 8 lh + 7 of a k-step (the A fragment holds the same pixels of row q)
-  WG_LDS const char* xb = (WG_LDS const char*)wg_smem + q * WG_CST + (WG_MARGIN + 8 * lh) * 2;
+  GDF_LDS const char* xb = (GDF_LDS const char*)wg_smem + q * WG_CST + (WG_MARGIN + 8 * lh) * 2;
 
   int b = 0, y0 = 0, x0 = 0;
   load_x(0, 0, 0);
@@ -199,7 +189,7 @@ __global__ __launch_bounds__(WG_NT) void wg_kernel(const WgArgs a) {
   for (int st = 0; st < WG_NG - 1; ++st) load_g(st, st);
   for (long k = 0; k < a.ntile; ++k) {
     store_x();
-    wg_barrier();
+    lds_barrier();
     int bn = b, yn = y0, xn = x0 + WG_PW;                  // the next patch: along x, then y, then the image
     if (xn >= a.W) { xn = 0; yn += WG_PH; }
     if (yn >= a.H) { yn = 0; ++bn; }
@@ -208,22 +198,22 @@ __global__ __launch_bounds__(WG_NT) void wg_kernel(const WgArgs a) {
 #pragma unroll
       for (int st = 0; st < WG_KS; ++st) {
         load_g((st + WG_NG - 1) % WG_NG, k * WG_KS + st + WG_NG - 1);
-        const wg_f16x8 ahi = __builtin_bit_cast(wg_f16x8, ghi[st % WG_NG]), alo = __builtin_bit_cast(wg_f16x8, glo[st % WG_NG]);
+        const f16x8 ahi = __builtin_bit_cast(f16x8, ghi[st % WG_NG]), alo = __builtin_bit_cast(f16x8, glo[st % WG_NG]);
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
-          WG_LDS const char* p = xb + ((st >> 1) + dy) * WG_PITCH + (st & 1) * 32;
-          wg_f16x8 xf[NIMG][3];
+          GDF_LDS const char* p = xb + ((st >> 1) + dy) * WG_PITCH + (st & 1) * 32;
+          f16x8 xf[NIMG][3];
 #pragma unroll
           for (int im = 0; im < NIMG; ++im) {
-            const wg_u32x4 c = *(WG_LDS const wg_u32x4*)(p + im * WG_IMG);
-            const unsigned pv = *(WG_LDS const unsigned*)(p + im * WG_IMG - 4), nx = *(WG_LDS const unsigned*)(p + im * WG_IMG + 16);
+            const u32x4 c = *(GDF_LDS const u32x4*)(p + im * WG_IMG);
+            const unsigned pv = *(GDF_LDS const unsigned*)(p + im * WG_IMG - 4), nx = *(GDF_LDS const unsigned*)(p + im * WG_IMG + 16);
             // pixel i - 1 / i + 1 in the place of pixel i: the 16-bit funnel shifts of neighbouring dwords
             const unsigned s0 = (pv >> 16) | (c[0] << 16), s1 = (c[0] >> 16) | (c[1] << 16), s2 = (c[1] >> 16) | (c[2] << 16),
                            s3 = (c[2] >> 16) | (c[3] << 16), s4 = (c[3] >> 16) | (nx << 16);
-            const wg_u32x4 lft = {s0, s1, s2, s3}, rgt = {s1, s2, s3, s4};
-            xf[im][0] = __builtin_bit_cast(wg_f16x8, lft);
-            xf[im][1] = __builtin_bit_cast(wg_f16x8, c);
-            xf[im][2] = __builtin_bit_cast(wg_f16x8, rgt);
+            const u32x4 lft = {s0, s1, s2, s3}, rgt = {s1, s2, s3, s4};
+            xf[im][0] = __builtin_bit_cast(f16x8, lft);
+            xf[im][1] = __builtin_bit_cast(f16x8, c);
+            xf[im][2] = __builtin_bit_cast(f16x8, rgt);
           }
 #pragma unroll
           for (int dx = 0; dx < 3; ++dx) acc[dy * 3 + dx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(alo, xf[0][dx], acc[dy * 3 + dx], 0, 0, 0);
@@ -246,7 +236,7 @@ __global__ __launch_bounds__(WG_NT) void wg_kernel(const WgArgs a) {
       }
     }
     b = bn; y0 = yn; x0 = xn;
-    wg_barrier();                                          // every wave has left the patch: the next one may be stored
+    lds_barrier();                                          // every wave has left the patch: the next one may be stored
   }
 
   // accumulator register r of lane (q, lh) is row 8 (r / 4) + 4 lh + r % 4 (the output channel), column q (the input channel); a lane's nine
@@ -268,37 +258,42 @@ __global__ __launch_bounds__(WG_NT) void wg_kernel(const WgArgs a) {
   }
 }
 
-size_t wg_up256(size_t v) { return (v + 255) & ~(size_t)255; }
+// [max |G| per output channel][shift per output channel][G's fragment image: 2 KB per 32-row block and k-step]
+struct WgWs { float* mx; int* sh; u32x4* gs; size_t bytes; };
+WgWs wg_carve(void* base, int B, int Cout, int H, int W) {
+  const size_t nks = (size_t)B * ((W + WG_PW - 1) / WG_PW) * ((H + WG_PH - 1) / WG_PH) * WG_KS;
+  Carver c(base);
+  WgWs ws;
+  ws.mx = c.take<float>((size_t)Cout * 4);
+  ws.sh = c.take<int>((size_t)Cout * 4);
+  ws.gs = c.take<u32x4>((size_t)((Cout + 31) / 32) * nks * 2 * 64 * 16);
+  ws.bytes = c.bytes();
+  return ws;
+}
 
 }  // namespace
 
-// [max |G| per output channel][shift per output channel][G's fragment image: 2 KB per 32-row block and k-step]
-size_t agghead_wgrad_workspace(int B, int Cout, int H, int W) {
-  const size_t nks = (size_t)B * ((W + WG_PW - 1) / WG_PW) * ((H + WG_PH - 1) / WG_PH) * WG_KS;
-  return 2 * wg_up256((size_t)Cout * 4) + (size_t)((Cout + 31) / 32) * nks * 2 * 64 * 16;
-}
+size_t agghead_wgrad_workspace(int B, int Cout, int H, int W) { return wg_carve(nullptr, B, Cout, H, W).bytes; }
 
 hipError_t launch_agghead_wgrad(const AggSrc& x, int B, const float* g, int Cout, float* dw, int accumulate, void* workspace, hipStream_t s) {
   if (!x.ptr || !g || !dw || !workspace || x.C < 1 || x.H < 1 || x.W < 1 || Cout < 1 || B < 0) return hipErrorInvalidValue;
   if ((long)B * x.H * x.W >= (1l << 31)) return hipErrorInvalidValue;
   if (B == 0) return hipSuccess;
-  float* mx = (float*)workspace;
-  int* sh = (int*)((char*)workspace + wg_up256((size_t)Cout * 4));
-  wg_u32x4* gs = (wg_u32x4*)((char*)workspace + 2 * wg_up256((size_t)Cout * 4));
+  const WgWs ws = wg_carve(workspace, B, Cout, x.H, x.W);
   const int nct = (x.C + WG_CT - 1) / WG_CT, ncb = (Cout + WG_ROWS - 1) / WG_ROWS, nrb = (Cout + 31) / 32;
   const int tx = (x.W + WG_PW - 1) / WG_PW, ty = (x.H + WG_PH - 1) / WG_PH;
   const long ntile = (long)B * tx * ty, nks = ntile * WG_KS, nsplit = (long)nrb * nks * 64;
   if ((nsplit + 255) / 256 >= (1l << 31)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(wg_rowmax_kernel, dim3(Cout), dim3(256), 0, s, g, B, Cout, (long)x.H * x.W, mx, sh);
+  hipLaunchKernelGGL(wg_rowmax_kernel, dim3(Cout), dim3(256), 0, s, g, B, Cout, (long)x.H * x.W, ws.mx, ws.sh);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(wg_split_kernel, dim3((unsigned)((nsplit + 255) / 256)), dim3(256), 0, s, g, (const int*)sh, Cout, x.H, x.W, tx, ty, nks,
-                     nsplit, gs);
+  hipLaunchKernelGGL(wg_split_kernel, dim3((unsigned)((nsplit + 255) / 256)), dim3(256), 0, s, g, (const int*)ws.sh, Cout, x.H, x.W, tx, ty, nks,
+                     nsplit, ws.gs);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const long total = (long)ncb * nct, chunk = (total + WG_XCDS - 1) / WG_XCDS;
-  const WgArgs a{x.ptr, x.sb, x.sc, x.sy, x.sx, x.C, x.H, x.W, gs, sh, dw, Cout, nct, nrb, accumulate ? 1 : 0, ntile, (unsigned)chunk, total};
-  const unsigned grid = (unsigned)(chunk * WG_XCDS);
+  const long total = (long)ncb * nct, chunk = xcd_chunk(total);
+  const WgArgs a{x.ptr, x.sb, x.sc, x.sy, x.sx, x.C, x.H, x.W, ws.gs, ws.sh, dw, Cout, nct, nrb, accumulate ? 1 : 0, ntile, (unsigned)chunk, total};
+  const unsigned grid = (unsigned)(chunk * XCDS);
   if (x.f32) hipLaunchKernelGGL(wg_kernel<float>, dim3(grid), dim3(WG_NT), 0, s, a);
   else hipLaunchKernelGGL(wg_kernel<_Float16>, dim3(grid), dim3(WG_NT), 0, s, a);
   return hipGetLastError();

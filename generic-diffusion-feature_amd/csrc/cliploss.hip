@@ -22,7 +22,7 @@
 
 #include <algorithm>
 
-#include "kernels.h"
+#include "feat_common.h"
 
 namespace gdf {
 
@@ -46,33 +46,6 @@ __device__ __forceinline__ float cl_z(float scale, float c) {
   return scale * c;
 }
 
-template <typename T>
-__device__ __forceinline__ float cl_ld(const void* p, long o) { return (float)((const T*)p)[o]; }
-
-// the sum of 256 threads' values in a fixed tree; every thread receives it.  red: 256 floats
-__device__ __forceinline__ float cl_block_sum(float v, float* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int half = 128; half >= 1; half >>= 1) {
-    if ((int)threadIdx.x < half) red[threadIdx.x] += red[threadIdx.x + half];
-    __syncthreads();
-  }
-  return red[0];
-}
-__device__ __forceinline__ float cl_block_max(float v, float* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int half = 128; half >= 1; half >>= 1) {
-    if ((int)threadIdx.x < half) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + half]);
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // One workgroup = one (pair b, query slot n < Npad).  idx: (B, N) flat pixel indices of this map.  An index outside the map is clamped for the read
 // and flagged; so is a norm that is not positive and finite.  Slots n >= N are zero-filled.
 __global__ __launch_bounds__(256) void cl_gather_kernel(const void* f, int f32, long sb, long sc, long sy, long sx, int C, int W, int P,
@@ -90,12 +63,12 @@ __global__ __launch_bounds__(256) void cl_gather_kernel(const void* f, int f32, 
   const long o = (long)b * sb + (long)(p / W) * sy + (long)(p % W) * sx;
   float ss = 0.f;
   for (int c = threadIdx.x; c < C; c += 256) {
-    const float v = f32 ? cl_ld<float>(f, o + (long)c * sc) : cl_ld<_Float16>(f, o + (long)c * sc);
+    const float v = f32 ? ld<float>(f, o + (long)c * sc) : ld<_Float16>(f, o + (long)c * sc);
     ss = fmaf(v, v, ss);
   }
-  const float inv = 1.f / sqrtf(cl_block_sum(ss, red));
+  const float inv = 1.f / sqrtf(block_sum256(ss, red));
   for (int c = threadIdx.x; c < C; c += 256) {
-    const float v = f32 ? cl_ld<float>(f, o + (long)c * sc) : cl_ld<_Float16>(f, o + (long)c * sc);
+    const float v = f32 ? ld<float>(f, o + (long)c * sc) : ld<_Float16>(f, o + (long)c * sc);
     qb[cl_qoff(n, c, C, N)] = v * inv;
   }
   if (threadIdx.x == 0) {
@@ -233,12 +206,12 @@ __global__ __launch_bounds__(256) void cl_lse_kernel(const float* cos_, const fl
     if (!(ki > 0.f && ki < INFINITY)) nb = 1.f;
     m = fmaxf(m, cl_z(scale, cb[(long)p * Npad]));
   }
-  m = cl_block_max(m, red);
-  nb = cl_block_max(nb, red);
+  m = block_max256(m, red);
+  nb = block_max256(nb, red);
   float se = 0.f;
 #pragma unroll 4
   for (int p = threadIdx.x; p < P; p += 256) se += expf(cl_z(scale, cb[(long)p * Npad]) - m);
-  se = cl_block_sum(se, red);
+  se = block_sum256(se, red);
   if (threadIdx.x == 0) {
     const long long l = label[(long)b * N + n];
     const int lp = cl_clamp(l, P);
@@ -413,7 +386,7 @@ __global__ __launch_bounds__(256) void cl_rowsum_kernel(const float* cos_, const
     const float cv = cb[(long)p * Npad];
     t = fmaf(coef * (expf(cl_z(scale, cv) - ls) - ((long long)p == lab ? 1.f : 0.f)), cv, t);
   }
-  t = cl_block_sum(t, red);
+  t = block_sum256(t, red);
   if (threadIdx.x == 0) T[(long)b * Npad + n] = t;
 }
 
@@ -442,8 +415,6 @@ __global__ __launch_bounds__(256) void cl_rows_kernel(const float* part, int R, 
   *g = v;
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // pixels per backward workgroup: at most CL_RANGES ranges per map, whole tiles
 int cl_pr(int P) { return (int)std::max<long>(CL_TILE, (((long)P + CL_RANGES - 1) / CL_RANGES + CL_TILE - 1) / CL_TILE * CL_TILE); }
 
@@ -453,37 +424,30 @@ struct ClWs { ClDir d[2]; int* valid; size_t bytes; };
 ClWs cl_carve(void* base, int B, int N, int C, int P1, int P2) {
   const size_t npad = (size_t)cl_npad(N);
   const int P[2] = {P1, P2};
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = p + off; off += up256(bytes); return r; };
+  Carver c(base);
   ClWs ws;
   for (int d = 0; d < 2; ++d) {
     const size_t pk = (size_t)P[1 - d], R = (size_t)((pk + cl_pr((int)pk) - 1) / cl_pr((int)pk));
     ClDir& e = ws.d[d];
-    e.q = (float*)take((size_t)B * C * npad * 4);
-    e.qinv = (float*)take((size_t)B * npad * 4);
-    e.qbad = (int*)take((size_t)B * npad * 4);
-    e.cos_ = (float*)take((size_t)B * pk * npad * 4);
-    e.kinv = (float*)take((size_t)B * pk * 4);
-    e.lse = (float*)take((size_t)B * npad * 4);
-    e.term = (float*)take((size_t)B * npad * 4);
-    e.bad = (int*)take((size_t)B * npad * 4);
-    e.T = (float*)take((size_t)B * npad * 4);
-    e.part = (float*)take((size_t)B * R * npad * C * 4);
+    e.q = c.take<float>((size_t)B * C * npad * 4);
+    e.qinv = c.take<float>((size_t)B * npad * 4);
+    e.qbad = c.take<int>((size_t)B * npad * 4);
+    e.cos_ = c.take<float>((size_t)B * pk * npad * 4);
+    e.kinv = c.take<float>((size_t)B * pk * 4);
+    e.lse = c.take<float>((size_t)B * npad * 4);
+    e.term = c.take<float>((size_t)B * npad * 4);
+    e.bad = c.take<int>((size_t)B * npad * 4);
+    e.T = c.take<float>((size_t)B * npad * 4);
+    e.part = c.take<float>((size_t)B * R * npad * C * 4);
   }
-  ws.valid = (int*)take((size_t)B * 4);
-  ws.bytes = off;
+  ws.valid = c.take<int>((size_t)B * 4);
+  ws.bytes = c.bytes();
   return ws;
-}
-
-bool cl_lanes_c(const AggSrc& f) {
-  const long vl = f.f32 ? 4 : 8;
-  return f.sc == 1 && !(f.C % vl) && !((uintptr_t)f.ptr & 15) && !(f.sb % vl) && !(f.sy % vl) && !(f.sx % vl);
 }
 
 template <typename T, int NQ>
 void cl_fwd(const AggSrc& k, int B, int P, const float* q, long qstride, int Npad, int n0, float* cos_, float* kinv, hipStream_t s) {
-  if (cl_lanes_c(k)) {
+  if (map_lanes_c(k)) {
     hipLaunchKernelGGL((cl_fwd_c_kernel<T, NQ>), dim3((unsigned)((P + 4 * CL_P - 1) / (4 * CL_P)), (unsigned)B), dim3(256), 0, s, (const T*)k.ptr,
                        k.sb, k.sy, k.sx, k.C, k.W, P, q, qstride, Npad, n0, cos_, kinv);
   } else {
@@ -498,19 +462,9 @@ template <typename T, int NQ>
 void cl_bwd(const AggSrc& k, int B, int P, const float* q, long qstride, int n0, const ClBwd& a, hipStream_t s) {
   const int PR = cl_pr(P), R = (P + PR - 1) / PR;
   hipLaunchKernelGGL((cl_bwd_kernel<T, NQ>), dim3((unsigned)R, (unsigned)((k.C + CL_TILE - 1) / CL_TILE), (unsigned)B), dim3(256), 0, s,
-                     (const T*)k.ptr, k.sb, k.sc, k.sy, k.sx, cl_lanes_c(k) ? 1 : 0, k.C, k.W, P, q, qstride, a.Npad, n0, a.N, a.cos_, a.kinv, a.lse,
+                     (const T*)k.ptr, k.sb, k.sc, k.sy, k.sx, map_lanes_c(k) ? 1 : 0, k.C, k.W, P, q, qstride, a.Npad, n0, a.N, a.cos_, a.kinv, a.lse,
                      a.label, a.scale, a.grad_loss, a.valid, a.grad, n0 > 0 ? 1 : 0, a.part, PR);
 }
-
-#define CL_BY_NQ(FN, NQ, ...)                                                     \
-  switch (NQ) {                                                                    \
-    case 4: if (k.f32) FN<float, 4>(__VA_ARGS__); else FN<_Float16, 4>(__VA_ARGS__); break;       \
-    case 8: if (k.f32) FN<float, 8>(__VA_ARGS__); else FN<_Float16, 8>(__VA_ARGS__); break;       \
-    case 12: if (k.f32) FN<float, 12>(__VA_ARGS__); else FN<_Float16, 12>(__VA_ARGS__); break;    \
-    case 16: if (k.f32) FN<float, 16>(__VA_ARGS__); else FN<_Float16, 16>(__VA_ARGS__); break;    \
-    case 20: if (k.f32) FN<float, 20>(__VA_ARGS__); else FN<_Float16, 20>(__VA_ARGS__); break;    \
-    default: if (k.f32) FN<float, CL_MAXQ>(__VA_ARGS__); else FN<_Float16, CL_MAXQ>(__VA_ARGS__); break; \
-  }
 
 bool cl_args_ok(const AggSrc& f1, const AggSrc& f2, int B, int N, const void* workspace) {
   if (!f1.ptr || !f2.ptr || !workspace || ((uintptr_t)workspace & 15)) return false;
@@ -538,8 +492,11 @@ hipError_t launch_clip_loss(const AggSrc& f1, const AggSrc& f2, int B, const lon
     hipLaunchKernelGGL(cl_gather_kernel, dim3((unsigned)Npad, (unsigned)B), dim3(256), 0, s, qm.ptr, qm.f32, qm.sb, qm.sc, qm.sy, qm.sx, C, qm.W,
                        P[d], idx[d], N, Npad, e.q, e.qinv, e.qbad);
     for (int n0 = 0; n0 < N; n0 += CL_MAXQ) {
-      const int NQ = cl_nq(N - n0);
-      CL_BY_NQ(cl_fwd, NQ, k, B, Pk, e.q + (long)C * n0, (long)C * Npad, Npad, n0, e.cos_, e.kinv, s)
+      by_nq<CL_MAXQ>(cl_nq(N - n0), [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        if (k.f32) cl_fwd<float, NQ>(k, B, Pk, e.q + (long)C * n0, (long)C * Npad, Npad, n0, e.cos_, e.kinv, s);
+        else cl_fwd<_Float16, NQ>(k, B, Pk, e.q + (long)C * n0, (long)C * Npad, Npad, n0, e.cos_, e.kinv, s);
+      });
     }
     hipLaunchKernelGGL(cl_lse_kernel, dim3((unsigned)N, (unsigned)B), dim3(256), 0, s, e.cos_, e.kinv, e.qbad, idx[1 - d], Pk, N, Npad, scale, e.lse,
                        e.term, e.bad);
@@ -566,8 +523,11 @@ hipError_t launch_clip_loss_backward(const AggSrc& f1, const AggSrc& f2, int B, 
     if (!grads[1 - d] && !grads[d]) continue;
     const ClBwd a{e.cos_, e.kinv, e.lse, grad_loss, idx[1 - d], ws.valid, grads[1 - d], grads[d] ? e.part : nullptr, scale, N, Npad};
     for (int n0 = 0; n0 < N; n0 += CL_MAXQ) {
-      const int NQ = cl_nq(N - n0);
-      CL_BY_NQ(cl_bwd, NQ, k, B, Pk, e.q + (long)C * n0, (long)C * Npad, n0, a, s)
+      by_nq<CL_MAXQ>(cl_nq(N - n0), [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        if (k.f32) cl_bwd<float, NQ>(k, B, Pk, e.q + (long)C * n0, (long)C * Npad, n0, a, s);
+        else cl_bwd<_Float16, NQ>(k, B, Pk, e.q + (long)C * n0, (long)C * Npad, n0, a, s);
+      });
     }
   }
   // then the N rows of each query map, in n order, on top of its dense gradient

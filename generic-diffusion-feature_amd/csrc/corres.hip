@@ -19,7 +19,7 @@
 
 #include <algorithm>
 
-#include "kernels.h"
+#include "feat_common.h"
 
 namespace gdf {
 
@@ -27,31 +27,12 @@ namespace {
 
 enum { NN_NG = 5 };                                   // <T,T> <T,T_right> <T,T_down> <T,T_diag> <T_right,T_down>; neighbours clamp at the border
 
-// ATen's area_pixel_compute_source_index (align_corners = false) in separately rounded fp32 operations, as bilinear_src of post.hip.  Where the
-// second tap clamps onto the first the weight is irrelevant and is returned as 0: every fine row (column) of such a run computes the same bits.
+// bilinear_src, except that where the second tap clamps onto the first the weight is irrelevant and is returned as 0: every fine row (column)
+// of such a run computes the same bits.
 __device__ __forceinline__ void nn_src(int dst, float scale, int in, int& i0, int& i1, float& l1) {
-#pragma clang fp contract(off)
-  const float s = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-  i0 = min((int)s, in - 1);
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = i1 > i0 ? s - (float)i0 : 0.f;
+  bilinear_src(dst, scale, in, i0, i1, l1);
+  if (i1 == i0) l1 = 0.f;
 }
-
-// (score, index) candidates: the higher score wins, then the lower index.  A NaN never wins (scores enter only through `>`).
-__device__ __forceinline__ void nn_take(float& s, unsigned& i, float os, unsigned oi) {
-  if (os > s || (os == s && oi < i)) { s = os; i = oi; }
-}
-__device__ __forceinline__ void nn_wave_best(float& s, unsigned& i) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const float os = __shfl_xor(s, off);
-    const unsigned oi = (unsigned)__shfl_xor((int)i, off);
-    nn_take(s, i, os, oi);
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ float nn_ld(const void* p, long o) { return (float)((const T*)p)[o]; }
 
 // One workgroup = one (sample b, query slot n of the chunk).  points: (B, N, 2) fp32 (y, x) in load-size coordinates; the source index is
 // round_half_even(clip(.)) as np.round does.  q: (B, C, NQ) fp32, not normalised; qi: (B, NQ) = 1 / ||q||; slots n >= nc are zero-filled.
@@ -78,8 +59,8 @@ __global__ __launch_bounds__(1024) void nn_query_kernel(const void* f, int f32, 
   for (int c = threadIdx.x; c < C; c += 1024) {
     const long oc = (long)c * sc;
     float t00, t01, t10, t11;
-    if (f32) { t00 = nn_ld<float>(f, o00 + oc); t01 = nn_ld<float>(f, o01 + oc); t10 = nn_ld<float>(f, o10 + oc); t11 = nn_ld<float>(f, o11 + oc); }
-    else { t00 = nn_ld<_Float16>(f, o00 + oc); t01 = nn_ld<_Float16>(f, o01 + oc); t10 = nn_ld<_Float16>(f, o10 + oc); t11 = nn_ld<_Float16>(f, o11 + oc); }
+    if (f32) { t00 = ld<float>(f, o00 + oc); t01 = ld<float>(f, o01 + oc); t10 = ld<float>(f, o10 + oc); t11 = ld<float>(f, o11 + oc); }
+    else { t00 = ld<_Float16>(f, o00 + oc); t01 = ld<_Float16>(f, o01 + oc); t10 = ld<_Float16>(f, o10 + oc); t11 = ld<_Float16>(f, o11 + oc); }
     const float v = ly0 * (lx0 * t00 + lx1 * t01) + ly1 * (lx0 * t10 + lx1 * t11);
     qn[(long)c * NQ] = v;
     ss += v * v;
@@ -272,7 +253,7 @@ __global__ __launch_bounds__(16 * NQ) void nn_fine_kernel(const float* D, const 
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    nn_wave_best(bs[k], bi[k]);
+    wave_best(bs[k], bi[k]);
     if (lane == 0 && n4 + k < nc) {
       const long o = ((long)b * NQ + n4 + k) * gridDim.x + blockIdx.x;
       ps[o] = bs[k];
@@ -289,8 +270,8 @@ __global__ __launch_bounds__(64) void nn_final_kernel(const float* ps, const uns
   const long o = ((long)b * NQ + n) * nblk;
   float s = -INFINITY;
   unsigned i = 0u;
-  for (int k = threadIdx.x; k < nblk; k += 64) nn_take(s, i, ps[o + k], pi[o + k]);
-  nn_wave_best(s, i);
+  for (int k = threadIdx.x; k < nblk; k += 64) best_take(s, i, ps[o + k], pi[o + k]);
+  wave_best(s, i);
   if (threadIdx.x == 0) {
     const long r = (long)b * N + n0 + n;
     out_yx[r * 2] = (long long)(i / (unsigned)LW);
@@ -299,17 +280,21 @@ __global__ __launch_bounds__(64) void nn_final_kernel(const float* ps, const uns
   }
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 int nq_of(int n) { return std::min((n + 3) / 4 * 4, (int)NN_MAXQ); }     // the instantiation of a chunk of n queries: 4, 8, .. NN_MAXQ
 
 struct NnWs { float *q, *qi, *D, *G, *ps; unsigned* pi; size_t bytes; };
 NnWs nn_carve(void* base, int B, int N, int C, int h2, int w2) {
   const size_t nq = (size_t)nq_of(N), hw = (size_t)h2 * w2;
-  const size_t q = up256((size_t)B * C * nq * 4), qi = up256((size_t)B * nq * 4), D = up256((size_t)B * hw * nq * 4);
-  const size_t G = up256((size_t)B * hw * 8 * 4), pp = up256((size_t)B * nq * NN_FINE_BLOCKS * 4);
-  char* p = (char*)base;
-  return NnWs{(float*)p, (float*)(p + q), (float*)(p + q + qi), (float*)(p + q + qi + D), (float*)(p + q + qi + D + G),
-              (unsigned*)(p + q + qi + D + G + pp), q + qi + D + G + 2 * pp};
+  Carver c(base);
+  NnWs ws;
+  ws.q = c.take<float>((size_t)B * C * nq * 4);
+  ws.qi = c.take<float>((size_t)B * nq * 4);
+  ws.D = c.take<float>((size_t)B * hw * nq * 4);
+  ws.G = c.take<float>((size_t)B * hw * 8 * 4);
+  ws.ps = c.take<float>((size_t)B * nq * NN_FINE_BLOCKS * 4);
+  ws.pi = c.take<unsigned>((size_t)B * nq * NN_FINE_BLOCKS * 4);
+  ws.bytes = c.bytes();
+  return ws;
 }
 
 template <typename T, int NQ>
@@ -344,21 +329,13 @@ hipError_t launch_nn_match(const AggSrc& f1, const AggSrc& f2, int B, const floa
   if ((long)LH * LW >= (1l << 30) || (long)B * f2.H * f2.W >= (1l << 31)) return hipErrorInvalidValue;
   if (B == 0) return hipSuccess;
   const NnWs ws = nn_carve(workspace, B, N, f2.C, f2.H, f2.W);
-  const long vl = f2.f32 ? 4 : 8;
-  const bool lanes_c = f2.sc == 1 && !(f2.C % vl) && !((uintptr_t)f2.ptr & 15) && !(f2.sb % vl) && !(f2.sy % vl) && !(f2.sx % vl);
+  const bool lanes_c = map_lanes_c(f2);
   const int nblk = (int)std::min<long>(((long)LH * LW + 63) / 64, (long)NN_FINE_BLOCKS);
   for (int n0 = 0; n0 < N; n0 += NN_MAXQ) {
     const int nc = std::min(N - n0, (int)NN_MAXQ), NQ = nq_of(nc);
     hipLaunchKernelGGL(nn_query_kernel, dim3((unsigned)(B * NQ)), dim3(1024), 0, s, f1.ptr, f1.f32, f1.sb, f1.sc, f1.sy, f1.sx, f1.C, f1.H, f1.W,
                        points, N, n0, nc, NQ, LH, LW, ws.q, ws.qi);
-    switch (NQ) {
-      case 4: nn_chunk<4>(f2, lanes_c, B, nc, LH, LW, nblk, ws, s); break;
-      case 8: nn_chunk<8>(f2, lanes_c, B, nc, LH, LW, nblk, ws, s); break;
-      case 12: nn_chunk<12>(f2, lanes_c, B, nc, LH, LW, nblk, ws, s); break;
-      case 16: nn_chunk<16>(f2, lanes_c, B, nc, LH, LW, nblk, ws, s); break;
-      case 20: nn_chunk<20>(f2, lanes_c, B, nc, LH, LW, nblk, ws, s); break;
-      default: nn_chunk<NN_MAXQ>(f2, lanes_c, B, nc, LH, LW, nblk, ws, s); break;
-    }
+    by_nq<NN_MAXQ>(NQ, [&](auto nq) { nn_chunk<decltype(nq)::value>(f2, lanes_c, B, nc, LH, LW, nblk, ws, s); });
     hipLaunchKernelGGL(nn_final_kernel, dim3((unsigned)(B * nc)), dim3(64), 0, s, ws.ps, ws.pi, nblk, NQ, nc, N, n0, LW, out_yx, out_score);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

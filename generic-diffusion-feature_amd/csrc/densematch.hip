@@ -26,7 +26,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "kernels.h"
+#include "feat_common.h"
 
 namespace gdf {
 
@@ -36,14 +36,7 @@ enum { DM_PACK_P = 64 };                               // pixels of one pack wor
 #define DM_SCALE 4096.f                                // an fp32 map's unit vectors are stored as fp16 pairs of DM_SCALE * v: lo stays clear of
                                                        // the fp16 subnormals down to |v| ~ 2^-25, hi <= 4096
 
-typedef _Float16 dm_f16x8 __attribute__((ext_vector_type(8)));
-typedef float dm_f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned dm_u32x4 __attribute__((ext_vector_type(4)));
-
-// (score, index) candidates: the higher score wins, then the lower index.  Scores are never NaN here (the epilogue replaces them by -inf).
-__device__ __forceinline__ void dm_take(float& s, int& i, float os, int oi) {
-  if (os > s || (os == s && oi < i)) { s = os; i = oi; }
-}
+// (best_take's scores are never NaN here: the epilogue replaces them by -inf)
 
 // One workgroup = DM_PACK_P consecutive pixels (flattened y * W + x) of one sample, all channels in chunks of 64 through an LDS tile.  The tile is
 // loaded with lanes along the channels where sc == 1 and along the pixels otherwise, and written out with lanes along the channels, 16 bytes each.
@@ -93,7 +86,7 @@ __global__ __launch_bounds__(256) void dm_pack_kernel(const T* __restrict__ f, l
         }
         if (write) {
           const long o = (long)(p0 + pl) * Kp + c0 + sc8;
-          dm_f16x8 h, l;
+          f16x8 h, l;
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             if (F32) {
@@ -104,8 +97,8 @@ __global__ __launch_bounds__(256) void dm_pack_kernel(const T* __restrict__ f, l
               h[e] = (_Float16)v[e];
             }
           }
-          *(dm_f16x8*)(hi + o) = h;
-          if (F32) *(dm_f16x8*)(lo + o) = l;
+          *(f16x8*)(hi + o) = h;
+          if (F32) *(f16x8*)(lo + o) = l;
         }
       }
     }
@@ -139,7 +132,7 @@ __global__ __launch_bounds__(256) void dm_match_kernel(const _Float16* __restric
   constexpr int NP = N1 + N2;                         // staged panels: [A hi, A lo][B hi, B lo]
   constexpr int PT = DM_TILE * CH;                    // chunks of one staged panel tile
   constexpr int LD = PT / 256;                        // chunks a thread moves per panel
-  __shared__ dm_u32x4 lds[NP * PT];
+  __shared__ u32x4 lds[NP * PT];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6, wm = wv >> 1, wn = wv & 1;
   const int r = lane & 31, h = lane >> 5, b = blockIdx.y;
   const int nt = ntx * nty;
@@ -150,7 +143,7 @@ __global__ __launch_bounds__(256) void dm_match_kernel(const _Float16* __restric
   const _Float16* pa = A + ((long)b * N1 * P1p + row0) * Kp;
   const _Float16* pb = Bm + ((long)b * N2 * P2p + col0) * Kp;
 
-  dm_u32x4 stage[NP][LD];
+  u32x4 stage[NP][LD];
   auto load_global = [&](int k0) {
 #pragma unroll
     for (int n = 0; n < NP; ++n) {
@@ -158,7 +151,7 @@ __global__ __launch_bounds__(256) void dm_match_kernel(const _Float16* __restric
 #pragma unroll
       for (int i = 0; i < LD; ++i) {
         const int q = t + 256 * i, row = q / CH, ch = q % CH;
-        stage[n][i] = *(const dm_u32x4*)(src + (long)row * Kp + k0 + ch * 8);
+        stage[n][i] = *(const u32x4*)(src + (long)row * Kp + k0 + ch * 8);
       }
     }
   };
@@ -172,7 +165,7 @@ __global__ __launch_bounds__(256) void dm_match_kernel(const _Float16* __restric
       }
   };
 
-  dm_f32x16 acc[4][4];
+  f32x16 acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -190,20 +183,20 @@ __global__ __launch_bounds__(256) void dm_match_kernel(const _Float16* __restric
 #pragma unroll
     for (int kk = 0; kk < BK / 16; ++kk) {
       const int ch = kk * 2 + h;
-      dm_f16x8 fa[N1][4], fb[N2][4];
+      f16x8 fa[N1][4], fb[N2][4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int row = wm * 128 + i * 32 + r;
         const int o = row * CH + (ch ^ ((row / RP) & (CH - 1)));
 #pragma unroll
-        for (int n = 0; n < N1; ++n) fa[n][i] = __builtin_bit_cast(dm_f16x8, lds[n * PT + o]);
+        for (int n = 0; n < N1; ++n) fa[n][i] = __builtin_bit_cast(f16x8, lds[n * PT + o]);
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int row = wn * 128 + j * 32 + r;
         const int o = row * CH + (ch ^ ((row / RP) & (CH - 1)));
 #pragma unroll
-        for (int n = 0; n < N2; ++n) fb[n][j] = __builtin_bit_cast(dm_f16x8, lds[(N1 + n) * PT + o]);
+        for (int n = 0; n < N2; ++n) fb[n][j] = __builtin_bit_cast(f16x8, lds[(N1 + n) * PT + o]);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -246,16 +239,16 @@ __global__ __launch_bounds__(256) void dm_match_kernel(const _Float16* __restric
       for (int j = 0; j < 4; ++j) {
         float v = (acc[i][j][reg] * ra) * c2[j];
         v = (ra > 0.f && c2[j] > 0.f && v == v) ? v : -INFINITY;
-        if (do_cols) dm_take(cs[j], ci[j], v, gr);
+        if (do_cols) best_take(cs[j], ci[j], v, gr);
         if (j == 0) { s = v; ix = gc[0]; }
-        else dm_take(s, ix, v, gc[j]);
+        else best_take(s, ix, v, gc[j]);
       }
       if (do_rows) {
 #pragma unroll
         for (int off = 16; off >= 1; off >>= 1) {
           const float ts = __shfl_xor(s, off);
           const int ti = __shfl_xor(ix, off);
-          dm_take(s, ix, ts, ti);
+          best_take(s, ix, ts, ti);
         }
         if (r == (i & 1) * 16 + reg) { os[i >> 1] = s; oi[i >> 1] = ix; }
       }
@@ -279,7 +272,7 @@ __global__ __launch_bounds__(256) void dm_match_kernel(const _Float16* __restric
     for (int j = 0; j < 4; ++j) {
       const float ts = __shfl_xor(cs[j], 32);
       const int ti = __shfl_xor(ci[j], 32);
-      dm_take(cs[j], ci[j], ts, ti);
+      best_take(cs[j], ci[j], ts, ti);
     }
     const long o = ((long)b * 2 * nty + 2 * ty + wm) * P2p + col0 + wn * 128;
     if (h == 0) {                                     // (both halves hold the same four results; static indices keep them in registers)
@@ -301,34 +294,30 @@ __global__ __launch_bounds__(256) void dm_fold_kernel(const float* __restrict__ 
   int i = 0;
   for (int k = 0; k < nparts; ++k) {
     const long o = ((long)b * nparts + k) * Pp + p;
-    dm_take(s, i, ps[o], pi[o]);
+    best_take(s, i, ps[o], pi[o]);
   }
   const bool none = s == -INFINITY;
   nn[(long)b * P + p] = none ? 0 : i;
   sim[(long)b * P + p] = none ? NAN : s;
 }
 
-size_t dm_up256(size_t v) { return (v + 255) & ~(size_t)255; }
 long dm_pad(long v, long m) { return (v + m - 1) / m * m; }
 
 struct DmWs { _Float16 *a, *b; float *r1, *r2, *prs; int* pri; float* pcs; int* pci; size_t bytes; };
 DmWs dm_carve(void* base, int B, int C, long P1, long P2, int f32_1, int f32_2) {
   const size_t P1p = (size_t)dm_pad(P1, DM_TILE), P2p = (size_t)dm_pad(P2, DM_TILE), Kp = (size_t)dm_pad(C, DM_KPAD), nb = (size_t)B;
   const size_t ntx = P2p / DM_TILE, nty = P1p / DM_TILE;
-  const size_t a = dm_up256(nb * (f32_1 ? 2 : 1) * P1p * Kp * 2), b = dm_up256(nb * (f32_2 ? 2 : 1) * P2p * Kp * 2);
-  const size_t r1 = dm_up256(nb * P1p * 4), r2 = dm_up256(nb * P2p * 4);
-  const size_t pr = dm_up256(nb * 2 * ntx * P1p * 4), pc = dm_up256(nb * 2 * nty * P2p * 4);
-  char* p = (char*)base;
+  Carver c(base);
   DmWs w;
-  w.a = (_Float16*)p; p += a;
-  w.b = (_Float16*)p; p += b;
-  w.r1 = (float*)p; p += r1;
-  w.r2 = (float*)p; p += r2;
-  w.prs = (float*)p; p += pr;
-  w.pri = (int*)p; p += pr;
-  w.pcs = (float*)p; p += pc;
-  w.pci = (int*)p; p += pc;
-  w.bytes = a + b + r1 + r2 + 2 * pr + 2 * pc;
+  w.a = c.take<_Float16>(nb * (f32_1 ? 2 : 1) * P1p * Kp * 2);
+  w.b = c.take<_Float16>(nb * (f32_2 ? 2 : 1) * P2p * Kp * 2);
+  w.r1 = c.take<float>(nb * P1p * 4);
+  w.r2 = c.take<float>(nb * P2p * 4);
+  w.prs = c.take<float>(nb * 2 * ntx * P1p * 4);
+  w.pri = c.take<int>(nb * 2 * ntx * P1p * 4);
+  w.pcs = c.take<float>(nb * 2 * nty * P2p * 4);
+  w.pci = c.take<int>(nb * 2 * nty * P2p * 4);
+  w.bytes = c.bytes();
   return w;
 }
 

@@ -453,24 +453,44 @@ int gdf_op_resize_concat(const void* src, int src_f32, long sb, long sc, long sy
   return fin(launch_resize_concat(src_f32 ? nullptr : (const half_t*)src, src_f32 ? (const float*)src : nullptr, sb, sc, sy, sx, B, C, H, W,
                                   (half_t*)out, Ctot, coff, S, (hipStream_t)stream), "resize_concat");
 }
+// ---- the feature-map ops: one map descriptor conversion and one checker per entry point ----
+static AggSrc to_src(const gdf_agg_src& e) { return AggSrc{e.ptr, e.f32, e.sb, e.sc, e.sy, e.sx, e.C, e.H, e.W, e.coff}; }
+
+// The refusals of entry point `op`.  Every check returns 0 where it passes and otherwise the code to return, with the error text set; the entry
+// points call them in the order in which their refusals are documented to fire.
+struct OpCheck {
+  const char* op;
+  int fail(int rc, const std::string& msg) const { set_error(std::string(op) + ": " + msg); return rc; }
+  int bad(const std::string& msg) const { return fail(GDF_ERR_ARG, msg); }
+  int big(const std::string& msg) const { return fail(GDF_ERR_UNSUPPORTED, msg); }
+  int feat(const gdf_agg_src* a, const gdf_agg_src* b = nullptr) const { return (!a->ptr || (b && !b->ptr)) ? bad("null feature pointer") : 0; }
+  int dims(const gdf_agg_src* a, const gdf_agg_src* b = nullptr) const {
+    if (a->C < 1 || a->H < 1 || a->W < 1 || (b && (b->C < 1 || b->H < 1 || b->W < 1))) return bad("C, H and W >= 1");
+    return (b && a->C != b->C) ? bad("the two maps differ in C") : 0;
+  }
+  int aligned(const void* ws) const { return ((uintptr_t)ws & 15) ? bad("the workspace must be 16-byte aligned") : 0; }
+  int batch(int B) const { return B > 65535 ? big("B > 65535; split the batch") : 0; }
+  int room(size_t have, size_t need, const char* fn) const { return have < need ? bad(std::string("workspace smaller than ") + fn + " says") : 0; }
+};
+
 int gdf_op_aggregate(const gdf_agg_src* srcs, int n, int B, void* out, int out_f32, int Ctot, int OH, int OW, int mode, void* stream) {
-  auto bad = [](const char* msg) { set_error(std::string("gdf_op_aggregate: ") + msg); return GDF_ERR_ARG; };
-  if (n < 1 || n > AGG_MAX) return bad("1 <= n <= 16 sources");
-  if (!srcs || !out) return bad("null pointer");
-  if (mode != 0 && mode != 1) return bad("mode is 0 (nearest) or 1 (bilinear)");
-  if (B < 0 || OH < 1 || OW < 1) return bad("B >= 0, OH and OW >= 1");
-  if (mode == 0 && (out_f32 || OH != OW)) return bad("nearest writes fp16 and a square grid (gdf_op_resize_concat's kernel)");
+  const OpCheck ck{"gdf_op_aggregate"};
+  if (n < 1 || n > AGG_MAX) return ck.bad("1 <= n <= 16 sources");
+  if (!srcs || !out) return ck.bad("null pointer");
+  if (mode != 0 && mode != 1) return ck.bad("mode is 0 (nearest) or 1 (bilinear)");
+  if (B < 0 || OH < 1 || OW < 1) return ck.bad("B >= 0, OH and OW >= 1");
+  if (mode == 0 && (out_f32 || OH != OW)) return ck.bad("nearest writes fp16 and a square grid (gdf_op_resize_concat's kernel)");
   size_t blocks = 0;
   AggSrc a[AGG_MAX];
   for (int k = 0; k < n; ++k) {
     const gdf_agg_src& e = srcs[k];
-    if (!e.ptr) return bad("null source pointer");
-    if (e.C < 1 || e.H < 1 || e.W < 1) return bad("C, H and W >= 1");
-    if (e.coff < 0 || (long)e.coff + e.C > Ctot) return bad("coff < 0 or coff + C > Ctot");
+    if (!e.ptr) return ck.bad("null source pointer");
+    if (e.C < 1 || e.H < 1 || e.W < 1) return ck.bad("C, H and W >= 1");
+    if (e.coff < 0 || (long)e.coff + e.C > Ctot) return ck.bad("coff < 0 or coff + C > Ctot");
     blocks += (size_t)B * OH * ((e.C + 63) / 64);
-    a[k] = AggSrc{e.ptr, e.f32, e.sb, e.sc, e.sy, e.sx, e.C, e.H, e.W, e.coff};
+    a[k] = to_src(e);
   }
-  if (blocks >= (1ull << 31)) { set_error("gdf_op_aggregate: 2^31 workgroups or more; split the batch"); return GDF_ERR_UNSUPPORTED; }
+  if (blocks >= (1ull << 31)) return ck.big("2^31 workgroups or more; split the batch");
   if (B == 0) return GDF_OK;
   if (mode == 1) return fin(launch_aggregate(a, n, B, out, out_f32, Ctot, OH, OW, (hipStream_t)stream), "gdf_op_aggregate");
   for (int k = 0; k < n; ++k) {
@@ -486,22 +506,17 @@ size_t gdf_op_nn_match_workspace(int B, int N, int C, int h2, int w2) {
 }
 int gdf_op_nn_match(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const float* points, int N, int LH, int LW, long long* out_yx,
                     float* out_score, void* workspace, size_t workspace_bytes, void* stream) {
-  auto bad = [](const char* msg) { set_error(std::string("gdf_op_nn_match: ") + msg); return GDF_ERR_ARG; };
-  auto big = [](const char* msg) { set_error(std::string("gdf_op_nn_match: ") + msg); return GDF_ERR_UNSUPPORTED; };
-  if (!f1 || !f2 || !points || !out_yx || !out_score || !workspace) return bad("null pointer");
-  if (!f1->ptr || !f2->ptr) return bad("null feature pointer");
-  if (B < 0 || N < 1 || LH < 1 || LW < 1) return bad("B >= 0, N, LH and LW >= 1");
-  if (f1->C < 1 || f1->H < 1 || f1->W < 1 || f2->C < 1 || f2->H < 1 || f2->W < 1) return bad("C, H and W >= 1");
-  if (f1->C != f2->C) return bad("the two maps differ in C");
-  if ((uintptr_t)workspace & 15) return bad("the workspace must be 16-byte aligned");
-  if (B > 65535) return big("B > 65535; split the batch");
-  if ((long long)LH * LW >= (1ll << 30)) return big("LH * LW >= 2^30 pixels (32-bit flat indices)");
-  if ((long long)std::max(B, 1) * f2->H * f2->W >= (1ll << 31)) return big("B * h2 * w2 >= 2^31; split the batch");
-  if (workspace_bytes < gdf_op_nn_match_workspace(B, N, f2->C, f2->H, f2->W)) return bad("workspace smaller than gdf_op_nn_match_workspace says");
+  const OpCheck ck{"gdf_op_nn_match"};
+  int rc;
+  if (!f1 || !f2 || !points || !out_yx || !out_score || !workspace) return ck.bad("null pointer");
+  if ((rc = ck.feat(f1, f2))) return rc;
+  if (B < 0 || N < 1 || LH < 1 || LW < 1) return ck.bad("B >= 0, N, LH and LW >= 1");
+  if ((rc = ck.dims(f1, f2)) || (rc = ck.aligned(workspace)) || (rc = ck.batch(B))) return rc;
+  if ((long long)LH * LW >= (1ll << 30)) return ck.big("LH * LW >= 2^30 pixels (32-bit flat indices)");
+  if ((long long)std::max(B, 1) * f2->H * f2->W >= (1ll << 31)) return ck.big("B * h2 * w2 >= 2^31; split the batch");
+  if ((rc = ck.room(workspace_bytes, gdf_op_nn_match_workspace(B, N, f2->C, f2->H, f2->W), "gdf_op_nn_match_workspace"))) return rc;
   if (B == 0) return GDF_OK;
-  const AggSrc a{f1->ptr, f1->f32, f1->sb, f1->sc, f1->sy, f1->sx, f1->C, f1->H, f1->W, 0};
-  const AggSrc b{f2->ptr, f2->f32, f2->sb, f2->sc, f2->sy, f2->sx, f2->C, f2->H, f2->W, 0};
-  return fin(launch_nn_match(a, b, B, points, N, LH, LW, out_yx, out_score, workspace, (hipStream_t)stream), "gdf_op_nn_match");
+  return fin(launch_nn_match(to_src(*f1), to_src(*f2), B, points, N, LH, LW, out_yx, out_score, workspace, (hipStream_t)stream), "gdf_op_nn_match");
 }
 size_t gdf_op_dense_match_workspace(int B, int C, int P1, int P2, int f32_1, int f32_2) {
   return dense_match_workspace(std::max(B, 1), std::max(C, 1), std::min(std::max(P1, 1), (int)DM_MAXP), std::min(std::max(P2, 1), (int)DM_MAXP),
@@ -509,26 +524,21 @@ size_t gdf_op_dense_match_workspace(int B, int C, int P1, int P2, int f32_1, int
 }
 int gdf_op_dense_match(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, int* nn12, float* sim12, int* nn21, float* sim21, void* workspace,
                        size_t workspace_bytes, void* stream) {
-  auto bad = [](const char* msg) { set_error(std::string("gdf_op_dense_match: ") + msg); return GDF_ERR_ARG; };
-  auto big = [](const char* msg) { set_error(std::string("gdf_op_dense_match: ") + msg); return GDF_ERR_UNSUPPORTED; };
-  if (!f1 || !f2 || !workspace) return bad("null pointer");
-  if (!f1->ptr || !f2->ptr) return bad("null feature pointer");
-  if ((!nn12) != (!sim12) || (!nn21) != (!sim21)) return bad("an output pair is given whole or not at all");
-  if (!nn12 && !nn21) return bad("both output pairs are null");
-  if (B < 0) return bad("B >= 0");
-  if (f1->C < 1 || f1->H < 1 || f1->W < 1 || f2->C < 1 || f2->H < 1 || f2->W < 1) return bad("C, H and W >= 1");
-  if (f1->C != f2->C) return bad("the two maps differ in C");
-  if ((uintptr_t)workspace & 15) return bad("the workspace must be 16-byte aligned");
+  const OpCheck ck{"gdf_op_dense_match"};
+  int rc;
+  if (!f1 || !f2 || !workspace) return ck.bad("null pointer");
+  if ((rc = ck.feat(f1, f2))) return rc;
+  if ((!nn12) != (!sim12) || (!nn21) != (!sim21)) return ck.bad("an output pair is given whole or not at all");
+  if (!nn12 && !nn21) return ck.bad("both output pairs are null");
+  if (B < 0) return ck.bad("B >= 0");
+  if ((rc = ck.dims(f1, f2)) || (rc = ck.aligned(workspace)) || (rc = ck.batch(B))) return rc;
   const long long P1 = (long long)f1->H * f1->W, P2 = (long long)f2->H * f2->W;
-  if (B > 65535) return big("B > 65535; split the batch");
-  if (P1 > DM_MAXP || P2 > DM_MAXP) return big("more than 2^30 pixels in a map (32-bit indices)");
-  if (((P1 + DM_TILE - 1) / DM_TILE) * ((P2 + DM_TILE - 1) / DM_TILE) >= (1ll << 31)) return big("2^31 tiles or more; split a map");
-  if (workspace_bytes < gdf_op_dense_match_workspace(B, f1->C, (int)P1, (int)P2, f1->f32, f2->f32))
-    return bad("workspace smaller than gdf_op_dense_match_workspace says");
+  if (P1 > DM_MAXP || P2 > DM_MAXP) return ck.big("more than 2^30 pixels in a map (32-bit indices)");
+  if (((P1 + DM_TILE - 1) / DM_TILE) * ((P2 + DM_TILE - 1) / DM_TILE) >= (1ll << 31)) return ck.big("2^31 tiles or more; split a map");
+  if ((rc = ck.room(workspace_bytes, gdf_op_dense_match_workspace(B, f1->C, (int)P1, (int)P2, f1->f32, f2->f32), "gdf_op_dense_match_workspace")))
+    return rc;
   if (B == 0) return GDF_OK;
-  const AggSrc a{f1->ptr, f1->f32, f1->sb, f1->sc, f1->sy, f1->sx, f1->C, f1->H, f1->W, 0};
-  const AggSrc b{f2->ptr, f2->f32, f2->sb, f2->sc, f2->sy, f2->sx, f2->C, f2->H, f2->W, 0};
-  return fin(launch_dense_match(a, b, B, nn12, sim12, nn21, sim21, workspace, (hipStream_t)stream), "gdf_op_dense_match");
+  return fin(launch_dense_match(to_src(*f1), to_src(*f2), B, nn12, sim12, nn21, sim21, workspace, (hipStream_t)stream), "gdf_op_dense_match");
 }
 size_t gdf_op_clip_loss_workspace(int B, int N, int C, int P1, int P2) {
   return clip_loss_workspace(std::max(B, 1), std::max(N, 1), std::max(C, 1), std::max(P1, 1), std::max(P2, 1));
@@ -536,39 +546,32 @@ size_t gdf_op_clip_loss_workspace(int B, int N, int C, int P1, int P2) {
 // the checks the forward and the backward share; 0 = go on, -1 = B == 0 (a successful no-op)
 static int clip_loss_args(const char* what, const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const void* src_idx, const void* tgt_idx, int N,
                           float scale, const void* workspace, size_t workspace_bytes) {
-  auto bad = [&](const char* msg) { set_error(std::string(what) + ": " + msg); return GDF_ERR_ARG; };
-  auto big = [&](const char* msg) { set_error(std::string(what) + ": " + msg); return GDF_ERR_UNSUPPORTED; };
-  if (!f1 || !f2 || !src_idx || !tgt_idx || !workspace) return bad("null pointer");
-  if (!f1->ptr || !f2->ptr) return bad("null feature pointer");
-  if (B < 0 || N < 1) return bad("B >= 0 and N >= 1");
-  if (f1->C < 1 || f1->H < 1 || f1->W < 1 || f2->C < 1 || f2->H < 1 || f2->W < 1) return bad("C, H and W >= 1");
-  if (f1->C != f2->C) return bad("the two maps differ in C");
-  if (!(scale > 0.f) || !std::isfinite(scale)) return bad("the scale must be positive and finite");
-  if ((uintptr_t)workspace & 15) return bad("the workspace must be 16-byte aligned");
-  if (B > 65535) return big("B > 65535; split the batch");
-  if ((long long)f1->H * f1->W >= (1ll << 30) || (long long)f2->H * f2->W >= (1ll << 30)) return big("H * W >= 2^30 pixels (32-bit flat indices)");
-  if (workspace_bytes < gdf_op_clip_loss_workspace(B, N, f1->C, f1->H * f1->W, f2->H * f2->W))
-    return bad("workspace smaller than gdf_op_clip_loss_workspace says");
+  const OpCheck ck{what};
+  int rc;
+  if (!f1 || !f2 || !src_idx || !tgt_idx || !workspace) return ck.bad("null pointer");
+  if ((rc = ck.feat(f1, f2))) return rc;
+  if (B < 0 || N < 1) return ck.bad("B >= 0 and N >= 1");
+  if ((rc = ck.dims(f1, f2))) return rc;
+  if (!(scale > 0.f) || !std::isfinite(scale)) return ck.bad("the scale must be positive and finite");
+  if ((rc = ck.aligned(workspace)) || (rc = ck.batch(B))) return rc;
+  if ((long long)f1->H * f1->W >= (1ll << 30) || (long long)f2->H * f2->W >= (1ll << 30)) return ck.big("H * W >= 2^30 pixels (32-bit flat indices)");
+  if ((rc = ck.room(workspace_bytes, gdf_op_clip_loss_workspace(B, N, f1->C, f1->H * f1->W, f2->H * f2->W), "gdf_op_clip_loss_workspace"))) return rc;
   return B == 0 ? -1 : 0;
 }
 int gdf_op_clip_loss(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const long long* src_idx, const long long* tgt_idx, int N, float scale,
                      float* loss, float* terms, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!loss) { set_error("gdf_op_clip_loss: null pointer"); return GDF_ERR_ARG; }
+  if (!loss) return OpCheck{"gdf_op_clip_loss"}.bad("null pointer");
   const int rc = clip_loss_args("gdf_op_clip_loss", f1, f2, B, src_idx, tgt_idx, N, scale, workspace, workspace_bytes);
   if (rc) return rc < 0 ? GDF_OK : rc;
-  const AggSrc a{f1->ptr, f1->f32, f1->sb, f1->sc, f1->sy, f1->sx, f1->C, f1->H, f1->W, 0};
-  const AggSrc b{f2->ptr, f2->f32, f2->sb, f2->sc, f2->sy, f2->sx, f2->C, f2->H, f2->W, 0};
-  return fin(launch_clip_loss(a, b, B, src_idx, tgt_idx, N, scale, loss, terms, workspace, (hipStream_t)stream), "gdf_op_clip_loss");
+  return fin(launch_clip_loss(to_src(*f1), to_src(*f2), B, src_idx, tgt_idx, N, scale, loss, terms, workspace, (hipStream_t)stream), "gdf_op_clip_loss");
 }
 int gdf_op_clip_loss_backward(const gdf_agg_src* f1, const gdf_agg_src* f2, int B, const long long* src_idx, const long long* tgt_idx, int N,
                               float scale, const float* grad_loss, float* grad_f1, float* grad_f2, void* workspace, size_t workspace_bytes,
                               void* stream) {
-  if (!grad_loss) { set_error("gdf_op_clip_loss_backward: null pointer"); return GDF_ERR_ARG; }
+  if (!grad_loss) return OpCheck{"gdf_op_clip_loss_backward"}.bad("null pointer");
   const int rc = clip_loss_args("gdf_op_clip_loss_backward", f1, f2, B, src_idx, tgt_idx, N, scale, workspace, workspace_bytes);
   if (rc) return rc < 0 ? GDF_OK : rc;
-  const AggSrc a{f1->ptr, f1->f32, f1->sb, f1->sc, f1->sy, f1->sx, f1->C, f1->H, f1->W, 0};
-  const AggSrc b{f2->ptr, f2->f32, f2->sb, f2->sc, f2->sy, f2->sx, f2->C, f2->H, f2->W, 0};
-  return fin(launch_clip_loss_backward(a, b, B, src_idx, tgt_idx, N, scale, grad_loss, grad_f1, grad_f2, workspace, (hipStream_t)stream),
+  return fin(launch_clip_loss_backward(to_src(*f1), to_src(*f2), B, src_idx, tgt_idx, N, scale, grad_loss, grad_f1, grad_f2, workspace, (hipStream_t)stream),
              "gdf_op_clip_loss_backward");
 }
 size_t gdf_op_pca_workspace(int B, int C, int H, int W, int k, int joint) {
@@ -577,50 +580,45 @@ size_t gdf_op_pca_workspace(int B, int C, int H, int W, int k, int joint) {
 }
 int gdf_op_pca(const gdf_agg_src* src, int B, int k, int joint, int max_iter, float tol, float* mean, float* components, float* variance,
                float* total_variance, float* projection, int* info, void* workspace, size_t workspace_bytes, void* stream) {
-  auto bad = [](const char* msg) { set_error(std::string("gdf_op_pca: ") + msg); return GDF_ERR_ARG; };
-  auto big = [](const char* msg) { set_error(std::string("gdf_op_pca: ") + msg); return GDF_ERR_UNSUPPORTED; };
-  if (!src || !mean || !components || !variance || !total_variance || !info || !workspace) return bad("null pointer");
-  if (!src->ptr) return bad("null feature pointer");
-  if (B < 0) return bad("B >= 0");
-  if (src->C < 1 || src->H < 1 || src->W < 1) return bad("C, H and W >= 1");
-  if (joint != 0 && joint != 1) return bad("joint is 0 or 1");
-  if (k < 1 || k > 8) return bad("1 <= k <= 8");
-  if (max_iter < 1 || max_iter > PCA_MAXITER) return bad("1 <= max_iter <= 1024");
-  if (!(tol >= 0.f) || !std::isfinite(tol)) return bad("tol is finite and not negative");
-  if ((uintptr_t)workspace & 15) return bad("the workspace must be 16-byte aligned");
+  const OpCheck ck{"gdf_op_pca"};
+  int rc;
+  if (!src || !mean || !components || !variance || !total_variance || !info || !workspace) return ck.bad("null pointer");
+  if ((rc = ck.feat(src))) return rc;
+  if (B < 0) return ck.bad("B >= 0");
+  if ((rc = ck.dims(src))) return rc;
+  if (joint != 0 && joint != 1) return ck.bad("joint is 0 or 1");
+  if (k < 1 || k > 8) return ck.bad("1 <= k <= 8");
+  if (max_iter < 1 || max_iter > PCA_MAXITER) return ck.bad("1 <= max_iter <= 1024");
+  if (!(tol >= 0.f) || !std::isfinite(tol)) return ck.bad("tol is finite and not negative");
+  if ((rc = ck.aligned(workspace))) return rc;
   const long long samples = (long long)(joint ? std::max(B, 1) : 1) * src->H * src->W;
-  if (k > src->C || k > samples - 1) return bad("k <= min(C, samples - 1)");
-  if (src->C > PCA_MAXC) return big("C > 4096");
-  if (B > 65535) return big("B > 65535; split the batch");
-  if ((long long)std::max(B, 1) * src->H * src->W >= (1ll << 31)) return big("B * H * W >= 2^31; split the batch");
-  if (workspace_bytes < gdf_op_pca_workspace(B, src->C, src->H, src->W, k, joint)) return bad("workspace smaller than gdf_op_pca_workspace says");
+  if (k > src->C || k > samples - 1) return ck.bad("k <= min(C, samples - 1)");
+  if (src->C > PCA_MAXC) return ck.big("C > 4096");
+  if ((rc = ck.batch(B))) return rc;
+  if ((long long)std::max(B, 1) * src->H * src->W >= (1ll << 31)) return ck.big("B * H * W >= 2^31; split the batch");
+  if ((rc = ck.room(workspace_bytes, gdf_op_pca_workspace(B, src->C, src->H, src->W, k, joint), "gdf_op_pca_workspace"))) return rc;
   if (B == 0) return GDF_OK;
-  const AggSrc a{src->ptr, src->f32, src->sb, src->sc, src->sy, src->sx, src->C, src->H, src->W, 0};
-  return fin(launch_pca(a, B, k, joint, max_iter, tol, mean, components, variance, total_variance, projection, info, workspace,
+  return fin(launch_pca(to_src(*src), B, k, joint, max_iter, tol, mean, components, variance, total_variance, projection, info, workspace,
                         (hipStream_t)stream), "gdf_op_pca");
 }
 int gdf_op_pca_rgb(const float* projection, int B, int H, int W, int joint, unsigned char* out, int OH, int OW, void* stream) {
-  auto bad = [](const char* msg) { set_error(std::string("gdf_op_pca_rgb: ") + msg); return GDF_ERR_ARG; };
-  if (!projection || !out) return bad("null pointer");
-  if (B < 0 || H < 1 || W < 1 || OH < 1 || OW < 1) return bad("B >= 0, H, W, OH and OW >= 1");
-  if (joint != 0 && joint != 1) return bad("joint is 0 or 1");
-  if (B > 65535 || (long long)std::max(B, 1) * H * W >= (1ll << 31) || (long long)std::max(B, 1) * OH * OW >= (1ll << 31)) {
-    set_error("gdf_op_pca_rgb: B > 65535, B * H * W or B * OH * OW >= 2^31; split the batch");
-    return GDF_ERR_UNSUPPORTED;
-  }
+  const OpCheck ck{"gdf_op_pca_rgb"};
+  if (!projection || !out) return ck.bad("null pointer");
+  if (B < 0 || H < 1 || W < 1 || OH < 1 || OW < 1) return ck.bad("B >= 0, H, W, OH and OW >= 1");
+  if (joint != 0 && joint != 1) return ck.bad("joint is 0 or 1");
+  if (B > 65535 || (long long)std::max(B, 1) * H * W >= (1ll << 31) || (long long)std::max(B, 1) * OH * OW >= (1ll << 31))
+    return ck.big("B > 65535, B * H * W or B * OH * OW >= 2^31; split the batch");
   if (B == 0) return GDF_OK;
   return fin(launch_pca_rgb(projection, B, H, W, joint, out, OH, OW, (hipStream_t)stream), "gdf_op_pca_rgb");
 }
 int gdf_pixcls_create(int C, int M, int h1, int h2, int K, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
                       const float* b3, gdf_pixcls* out) {
-  auto bad = [](const char* msg) { set_error(std::string("gdf_pixcls_create: ") + msg); return GDF_ERR_ARG; };
+  const OpCheck ck{"gdf_pixcls_create"};
   if (out) *out = nullptr;
-  if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !out) return bad("null pointer");
-  if (C < 1 || M < 1 || h1 < 1 || h2 < 1 || K < 1) return bad("C, M, h1, h2 and K >= 1");
-  if (M > PC_MAXM || K > PC_MAXK || h1 > PC_MAXH || h2 > PC_MAXH || h1 % 32 || h2 % 32) {
-    set_error("gdf_pixcls_create: M <= 16, K <= 64, h1 and h2 multiples of 32 up to 256");
-    return GDF_ERR_UNSUPPORTED;
-  }
+  if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !out) return ck.bad("null pointer");
+  if (C < 1 || M < 1 || h1 < 1 || h2 < 1 || K < 1) return ck.bad("C, M, h1, h2 and K >= 1");
+  if (M > PC_MAXM || K > PC_MAXK || h1 > PC_MAXH || h2 > PC_MAXH || h1 % 32 || h2 % 32)
+    return ck.big("M <= 16, K <= 64, h1 and h2 multiples of 32 up to 256");
   PixCls* pc = nullptr;
   const int rc = fin(pixcls_create(C, M, h1, h2, K, W1, b1, W2, b2, W3, b3, &pc), "gdf_pixcls_create");
   if (rc == GDF_OK) *out = (gdf_pixcls)pc;
@@ -633,32 +631,29 @@ size_t gdf_pixcls_workspace(gdf_pixcls h, int B, int H, int W) {
 }
 int gdf_pixcls_predict(gdf_pixcls h, const gdf_agg_src* x, int B, long long* labels, float* js, uint8_t* model_labels, float* logits,
                        void* workspace, size_t workspace_bytes, void* stream) {
-  auto bad = [](const char* msg) { set_error(std::string("gdf_pixcls_predict: ") + msg); return GDF_ERR_ARG; };
-  if (!h || !x || !labels || !workspace) return bad("null pointer");
-  if (!x->ptr) return bad("null feature pointer");
+  const OpCheck ck{"gdf_pixcls_predict"};
+  int rc;
+  if (!h || !x || !labels || !workspace) return ck.bad("null pointer");
+  if ((rc = ck.feat(x))) return rc;
   const PixCls* pc = (const PixCls*)h;
-  if (B < 0 || x->H < 1 || x->W < 1) return bad("B >= 0, H and W >= 1");
-  if (x->C != pc->C) return bad("the map's C differs from the ensemble's");
-  if ((uintptr_t)workspace & 15) return bad("workspace not 16-byte aligned");
-  if ((long long)std::max(B, 1) * x->H * x->W >= (1ll << 31)) {
-    set_error("gdf_pixcls_predict: B * H * W >= 2^31; split the batch");
-    return GDF_ERR_UNSUPPORTED;
-  }
-  if (workspace_bytes < gdf_pixcls_workspace(h, B, x->H, x->W)) return bad("workspace smaller than gdf_pixcls_workspace says");
+  if (B < 0 || x->H < 1 || x->W < 1) return ck.bad("B >= 0, H and W >= 1");
+  if (x->C != pc->C) return ck.bad("the map's C differs from the ensemble's");
+  if ((uintptr_t)workspace & 15) return ck.bad("workspace not 16-byte aligned");      // (this entry point's own wording)
+  if ((long long)std::max(B, 1) * x->H * x->W >= (1ll << 31)) return ck.big("B * H * W >= 2^31; split the batch");
+  if ((rc = ck.room(workspace_bytes, gdf_pixcls_workspace(h, B, x->H, x->W), "gdf_pixcls_workspace"))) return rc;
   if (B == 0) return GDF_OK;
-  const AggSrc a{x->ptr, x->f32, x->sb, x->sc, x->sy, x->sx, x->C, x->H, x->W, 0};
-  return fin(launch_pixcls(pc, a, B, labels, js, model_labels, logits, workspace, (hipStream_t)stream), "gdf_pixcls_predict");
+  return fin(launch_pixcls(pc, to_src(*x), B, labels, js, model_labels, logits, workspace, (hipStream_t)stream), "gdf_pixcls_predict");
 }
 int gdf_agghead_create(int Cin, int Cout, const float* W, const float* bias, gdf_agghead* out) {
-  auto bad = [](const char* msg) { set_error(std::string("gdf_agghead_create: ") + msg); return GDF_ERR_ARG; };
+  const OpCheck ck{"gdf_agghead_create"};
   if (out) *out = nullptr;
-  if (!W || !out) return bad("null pointer");
-  if (Cin < 1 || Cout < 1) return bad("Cin and Cout >= 1");
+  if (!W || !out) return ck.bad("null pointer");
+  if (Cin < 1 || Cout < 1) return ck.bad("Cin and Cout >= 1");
   const size_t n = (size_t)Cout * Cin * 9;
   for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(W[i])) return bad("a weight is not finite");
+    if (!std::isfinite(W[i])) return ck.bad("a weight is not finite");
   for (int i = 0; bias && i < Cout; ++i)
-    if (!std::isfinite(bias[i])) return bad("a bias is not finite");
+    if (!std::isfinite(bias[i])) return ck.bad("a bias is not finite");
   AggHead* h = nullptr;
   const int rc = fin(agghead_create(Cin, Cout, W, bias, &h), "gdf_agghead_create");
   if (rc == GDF_OK) *out = (gdf_agghead)h;
@@ -666,29 +661,29 @@ int gdf_agghead_create(int Cin, int Cout, const float* W, const float* bias, gdf
 }
 void gdf_agghead_destroy(gdf_agghead h) { agghead_destroy((AggHead*)h); }
 int gdf_agghead_forward(gdf_agghead h, const gdf_agg_src* x, int B, float* out, void* stream) {
-  auto bad = [](const char* msg) { set_error(std::string("gdf_agghead_forward: ") + msg); return GDF_ERR_ARG; };
-  if (!h || !x || !out) return bad("null pointer");
-  if (!x->ptr) return bad("null feature pointer");
+  const OpCheck ck{"gdf_agghead_forward"};
+  int rc;
+  if (!h || !x || !out) return ck.bad("null pointer");
+  if ((rc = ck.feat(x))) return rc;
   const AggHead* ah = (const AggHead*)h;
-  if (B < 0 || x->H < 1 || x->W < 1) return bad("B >= 0, H and W >= 1");
-  if (x->C != ah->Cin) return bad("the map's C differs from the head's Cin");
-  if ((long long)std::max(B, 1) * x->H * x->W >= (1ll << 31)) return bad("B * H * W >= 2^31; split the batch");
+  if (B < 0 || x->H < 1 || x->W < 1) return ck.bad("B >= 0, H and W >= 1");
+  if (x->C != ah->Cin) return ck.bad("the map's C differs from the head's Cin");
+  if ((long long)std::max(B, 1) * x->H * x->W >= (1ll << 31)) return ck.bad("B * H * W >= 2^31; split the batch");
   if (B == 0) return GDF_OK;
-  const AggSrc a{x->ptr, x->f32, x->sb, x->sc, x->sy, x->sx, x->C, x->H, x->W, 0};
-  return fin(launch_agghead(ah, a, B, out, (hipStream_t)stream), "gdf_agghead_forward");
+  return fin(launch_agghead(ah, to_src(*x), B, out, (hipStream_t)stream), "gdf_agghead_forward");
 }
 int gdf_agghead_create_device(int Cin, int Cout, const float* W_dev, const float* bias_dev, void* stream, gdf_agghead* out) {
-  auto bad = [](const char* msg) { set_error(std::string("gdf_agghead_create_device: ") + msg); return GDF_ERR_ARG; };
+  const OpCheck ck{"gdf_agghead_create_device"};
   if (out) *out = nullptr;
-  if (!W_dev || !out) return bad("null pointer");
-  if (Cin < 1 || Cout < 1) return bad("Cin and Cout >= 1");
+  if (!W_dev || !out) return ck.bad("null pointer");
+  if (Cin < 1 || Cout < 1) return ck.bad("Cin and Cout >= 1");
   AggHead* h = nullptr;
   const int rc = fin(agghead_create_device(Cin, Cout, W_dev, bias_dev, (hipStream_t)stream, &h), "gdf_agghead_create_device");
   if (rc == GDF_OK) *out = (gdf_agghead)h;
   return rc;
 }
 int gdf_agghead_update(gdf_agghead h, const float* W_dev, void* stream) {
-  if (!h || !W_dev) { set_error("gdf_agghead_update: null pointer"); return GDF_ERR_ARG; }
+  if (!h || !W_dev) return OpCheck{"gdf_agghead_update"}.bad("null pointer");
   return fin(agghead_update((AggHead*)h, W_dev, (hipStream_t)stream), "gdf_agghead_update");
 }
 size_t gdf_agghead_wgrad_workspace(int B, int Cin, int Cout, int H, int W) {
@@ -697,16 +692,16 @@ size_t gdf_agghead_wgrad_workspace(int B, int Cin, int Cout, int H, int W) {
 }
 int gdf_agghead_wgrad(const gdf_agg_src* x, int B, const float* grad_out, int Cout, float* dW, int accumulate, void* ws, size_t ws_bytes,
                       void* stream) {
-  auto bad = [](const char* msg) { set_error(std::string("gdf_agghead_wgrad: ") + msg); return GDF_ERR_ARG; };
-  if (!x || !grad_out || !dW || !ws) return bad("null pointer");
-  if (!x->ptr) return bad("null feature pointer");
-  if (B < 0 || Cout < 1 || x->C < 1 || x->H < 1 || x->W < 1) return bad("B >= 0, Cout, C, H and W >= 1");
-  if ((long long)std::max(B, 1) * x->H * x->W >= (1ll << 31)) return bad("B * H * W >= 2^31; split the batch");
-  if ((uintptr_t)ws & 15) return bad("the workspace must be 16-byte aligned");
-  if (ws_bytes < gdf_agghead_wgrad_workspace(B, x->C, Cout, x->H, x->W)) return bad("workspace smaller than gdf_agghead_wgrad_workspace says");
+  const OpCheck ck{"gdf_agghead_wgrad"};
+  int rc;
+  if (!x || !grad_out || !dW || !ws) return ck.bad("null pointer");
+  if ((rc = ck.feat(x))) return rc;
+  if (B < 0 || Cout < 1 || x->C < 1 || x->H < 1 || x->W < 1) return ck.bad("B >= 0, Cout, C, H and W >= 1");
+  if ((long long)std::max(B, 1) * x->H * x->W >= (1ll << 31)) return ck.bad("B * H * W >= 2^31; split the batch");
+  if ((rc = ck.aligned(ws))) return rc;
+  if ((rc = ck.room(ws_bytes, gdf_agghead_wgrad_workspace(B, x->C, Cout, x->H, x->W), "gdf_agghead_wgrad_workspace"))) return rc;
   if (B == 0) return GDF_OK;
-  const AggSrc a{x->ptr, x->f32, x->sb, x->sc, x->sy, x->sx, x->C, x->H, x->W, 0};
-  return fin(launch_agghead_wgrad(a, B, grad_out, Cout, dW, accumulate, ws, (hipStream_t)stream), "gdf_agghead_wgrad");
+  return fin(launch_agghead_wgrad(to_src(*x), B, grad_out, Cout, dW, accumulate, ws, (hipStream_t)stream), "gdf_agghead_wgrad");
 }
 int gdf_op_avg_pool(const void* src, long sb, long sy, long sx, int B, int C, int H, int W, int r, void* out, void* stream) {
   return fin(launch_avg_pool((const half_t*)src, sb, sy, sx, B, C, H, W, r, (half_t*)out, (hipStream_t)stream), "avg_pool");

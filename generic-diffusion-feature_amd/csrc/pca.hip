@@ -29,16 +29,13 @@
 
 #include <algorithm>
 
-#include "kernels.h"
+#include "feat_common.h"
 
 namespace gdf {
 
 namespace {
 
 enum { PCA_T = 128, PCA_TP = 32, PCA_PS = 40, PCA_M = 8, PCA_LD = 65 };
-
-typedef _Float16 pca_f16x8 __attribute__((ext_vector_type(8)));
-typedef float pca_f32x16 __attribute__((ext_vector_type(16)));
 
 // vec: 16-byte loads along C are legal (sc == 1, C a multiple of the vector, every pixel 16-byte aligned)
 struct PcaSrc { const void* ptr; long sb, sc, sy, sx; int C, H, W, vec; };
@@ -136,7 +133,7 @@ __global__ __launch_bounds__(256) void pca_scale_kernel(const float* chmax, int 
   }
   if (threadIdx.x == 0) {
     m = red[0];
-    int e = 0;
+    int e = 0;                                          // split_shift's rule, clamped (written out: through the helper the branch became a select)
     if (m > 0.f && m < INFINITY) e = min(40, max(-40, 13 - ilogbf(m)));
     scale[g] = ldexpf(1.f, e);
   }
@@ -170,7 +167,7 @@ __global__ __launch_bounds__(256) void pca_cov_kernel(PcaSrc s, int joint, long 
   __syncthreads();
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 31, h = lane >> 5, wi = w & 1, wj = w >> 1;
-  pca_f32x16 acc[2][2];
+  f32x16 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -195,14 +192,14 @@ __global__ __launch_bounds__(256) void pca_cov_kernel(PcaSrc s, int joint, long 
     __syncthreads();
 #pragma unroll
     for (int kk = 0; kk < PCA_TP / 16; ++kk) {
-      pca_f16x8 ah[2], al[2], bh[2], bl[2];
+      f16x8 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int oa = (64 * wi + 32 * i + r) * PCA_PS + 16 * kk + 8 * h, ob = (64 * wj + 32 * i + r) * PCA_PS + 16 * kk + 8 * h;
-        ah[i] = *(const pca_f16x8*)(A + oa);
-        al[i] = *(const pca_f16x8*)(A + LO + oa);
-        bh[i] = *(const pca_f16x8*)(Bm + ob);
-        bl[i] = *(const pca_f16x8*)(Bm + LO + ob);
+        ah[i] = *(const f16x8*)(A + oa);
+        al[i] = *(const f16x8*)(A + LO + oa);
+        bh[i] = *(const f16x8*)(Bm + ob);
+        bl[i] = *(const f16x8*)(Bm + LO + ob);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -635,8 +632,6 @@ __global__ __launch_bounds__(1024) void pca_rgb_kernel(const float* proj, int B,
   }
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the sample ranges of the covariance: enough workgroups to fill the device, whole staging steps, and at most 8192 samples in one fp32
 // accumulation chain while n <= 64 * 8192 (S is capped at 64: beyond that the chain, and its rounding error, grow with n / 64)
 void pca_splits(int ntiles, long n, int& S, long& per) {
@@ -652,29 +647,23 @@ PcaWs pca_carve(void* base, int G, int C, long n) {
   int S;
   long per;
   pca_splits((int)ntiles, n, S, per);
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = p + off; off += up256(bytes); return r; };
+  Carver c(base);
   PcaWs ws;
-  ws.chmax = (float*)take((size_t)G * C * 4);
-  ws.scale = (float*)take((size_t)G * 4);
-  ws.part = (float*)take((size_t)G * S * ntiles * PCA_T * PCA_T * 4);
-  ws.cov = (float*)take((size_t)G * Cpad * Cpad * 4);
-  ws.Q = (float*)take((size_t)G * PCA_M * Cpad * 4);
-  ws.Z = (float*)take((size_t)G * PCA_M * Cpad * 4);
-  ws.Vr = (float*)take((size_t)G * PCA_M * Cpad * 4);
-  ws.lam = (float*)take((size_t)G * PCA_M * 4);
-  ws.done = (int*)take((size_t)G * 4);
-  ws.polish = (int*)take((size_t)G * 4);
-  ws.bytes = off;
+  ws.chmax = c.take<float>((size_t)G * C * 4);
+  ws.scale = c.take<float>((size_t)G * 4);
+  ws.part = c.take<float>((size_t)G * S * ntiles * PCA_T * PCA_T * 4);
+  ws.cov = c.take<float>((size_t)G * Cpad * Cpad * 4);
+  ws.Q = c.take<float>((size_t)G * PCA_M * Cpad * 4);
+  ws.Z = c.take<float>((size_t)G * PCA_M * Cpad * 4);
+  ws.Vr = c.take<float>((size_t)G * PCA_M * Cpad * 4);
+  ws.lam = c.take<float>((size_t)G * PCA_M * 4);
+  ws.done = c.take<int>((size_t)G * 4);
+  ws.polish = c.take<int>((size_t)G * 4);
+  ws.bytes = c.bytes();
   return ws;
 }
 
-PcaSrc pca_src(const AggSrc& f) {
-  const long vl = f.f32 ? 4 : 8;
-  const int vec = f.sc == 1 && !(f.C % vl) && !((uintptr_t)f.ptr & 15) && !(f.sb % vl) && !(f.sy % vl) && !(f.sx % vl);
-  return PcaSrc{f.ptr, f.sb, f.sc, f.sy, f.sx, f.C, f.H, f.W, vec};
-}
+PcaSrc pca_src(const AggSrc& f) { return PcaSrc{f.ptr, f.sb, f.sc, f.sy, f.sx, f.C, f.H, f.W, map_lanes_c(f) ? 1 : 0}; }
 
 void pca_ritz(const PcaWs& ws, int G, int Cpad, int k, int m, float tol, int first, int* info, hipStream_t s) {
   const dim3 g((unsigned)G), b(1024);

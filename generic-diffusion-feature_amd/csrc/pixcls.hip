@@ -20,23 +20,17 @@
 // Workgroups are numbered so that the M models of one pixel tile follow one another ON ONE XCD (they share the tile's x through that XCD's L2).
 // No atomics, fixed summation orders, stream-ordered, nothing read back, no allocation in a launch.
 #include <math.h>
-#include <string.h>
 
 #include <algorithm>
 #include <vector>
 
-#include "kernels.h"
+#include "feat_common.h"
 
 namespace gdf {
 
 namespace {
 
-typedef _Float16 pc_f16x8 __attribute__((ext_vector_type(8)));
-typedef float pc_f32x16 __attribute__((ext_vector_type(16)));
 typedef __fp16 pc_fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-typedef unsigned pc_u32x4 __attribute__((ext_vector_type(4)));
-typedef float pc_f32x4 __attribute__((ext_vector_type(4)));
-#define PC_LDS __attribute__((address_space(3)))
 
 enum {
   PC_BP = 128,           // pixels per workgroup
@@ -44,7 +38,6 @@ enum {
   PC_LDX = 160,          // halves per [channel] row of the x image: 128 pixels + 64 bytes, an odd multiple of 64 bytes (conflict-free transposed reads)
   PC_NT = 256,           // threads: four waves, wave w = pixel half (w & 1) x hidden half (w >> 1)
   PC_XIMG = PC_KT * PC_LDX * 2,      // bytes of one x image
-  PC_XCDS = 8,
 };
 
 // k of element e of the fragment of lane half lh within a 16-channel step: what ds_read_b64_tr_b16 hands out (rows 4 lh + e, then 8 + 4 lh + e - 4)
@@ -52,13 +45,9 @@ constexpr int pc_perm(int lh, int e) { return e < 4 ? 4 * lh + e : 8 + 4 * lh + 
 
 struct PcArgs {
   const void* x; long sb, sc, sy, sx; int C, H, W; long P;
-  const pc_u32x4* w1; const float *inv_s, *b1; const pc_u32x4* w2; const float *inv_s2, *b2, *w3, *b3;
+  const u32x4* w1; const float *inv_s, *b1; const u32x4* w2; const float *inv_s2, *b2, *w3, *b3;
   float* logits; int M, K, nkt; unsigned chunk; long total;
 };
-
-template <typename T> struct PcVec;
-template <> struct PcVec<_Float16> { typedef pc_f16x8 type; enum { V = 8 }; };
-template <> struct PcVec<float> { typedef pc_f32x4 type; enum { V = 4 }; };
 
 // T: the map's element type.  H1P / H2P: the hidden widths padded to (128, 32) or (256, 128) with zero weights.  CL: channels-last map (sc == 1,
 // C a multiple of the 16-byte vector, aligned pixels): 16-byte loads along C; otherwise one element per load with the map's own strides, lanes
@@ -71,15 +60,15 @@ __global__ __launch_bounds__(PC_NT) void pc_mlp_kernel(const PcArgs a) {
   constexpr int NBW = NRB / 2;                   // ... per wave
   constexpr int WT16 = NRB * 2 * 2 * 64;         // 16-byte chunks of one W1 tile: [k-step 2][row block][hi, lo][lane]
   constexpr int NWR = WT16 / PC_NT;              // ... per thread
-  constexpr int V = PcVec<T>::V;
+  constexpr int V = MapVec<T>::V;
   constexpr int NCH = PC_KT / V / 2;             // CL: 16-byte chunks per thread and tile
-  typedef typename PcVec<T>::type vt;
+  typedef typename MapVec<T>::type vt;
   extern __shared__ __attribute__((aligned(16))) char pc_smem[];
   char* sW = pc_smem;
   char* sX = pc_smem + WT16 * 16;
 
-  // (tile, model) of this workgroup: consecutive numbers on one XCD (workgroups go round-robin over the XCDs)
-  const long L = (long)(blockIdx.x % PC_XCDS) * a.chunk + blockIdx.x / PC_XCDS;
+  // (tile, model) of this workgroup: consecutive numbers on one XCD
+  const long L = xcd_slot(blockIdx.x, a.chunk);
   if (L >= a.total) return;                      // (whole workgroups, before any barrier)
   const int m = (int)(L % a.M);
   const long tile = L / a.M;
@@ -96,11 +85,11 @@ __global__ __launch_bounds__(PC_NT) void pc_mlp_kernel(const PcArgs a) {
     xoff = b * a.sb + y * a.sy + xx * a.sx;
   }
   const T* xp = (const T*)a.x + xoff;
-  const pc_u32x4* wp = a.w1 + (long)m * a.nkt * WT16;
+  const u32x4* wp = a.w1 + (long)m * a.nkt * WT16;
 
   T xe[CL ? 1 : 16];
   vt xv[CL ? NCH : 1];
-  pc_u32x4 wr[NWR];
+  u32x4 wr[NWR];
   auto load_tile = [&](int kt) {
     if constexpr (CL) {
 #pragma unroll
@@ -140,10 +129,10 @@ __global__ __launch_bounds__(PC_NT) void pc_mlp_kernel(const PcArgs a) {
       for (int i = 0; i < 16; ++i) put(kr + 2 * i, xe[i]);
     }
 #pragma unroll
-    for (int i = 0; i < NWR; ++i) *(pc_u32x4*)(sW + (t + PC_NT * i) * 16) = wr[i];
+    for (int i = 0; i < NWR; ++i) *(u32x4*)(sW + (t + PC_NT * i) * 16) = wr[i];
   };
 
-  pc_f32x16 acc[2][NBW];
+  f32x16 acc[2][NBW];
 #pragma unroll
   for (int pb = 0; pb < 2; ++pb)
 #pragma unroll
@@ -153,7 +142,7 @@ __global__ __launch_bounds__(PC_NT) void pc_mlp_kernel(const PcArgs a) {
 
   // transposed read: lane 4 q + p of a 16-lane group names row q, columns 4 p .. 4 p + 3 of a 4 x 16 block; the lane's two groups of a half
   // take pixel columns 0-15 and 16-31 of the 32-pixel block
-  PC_LDS const char* xl = (PC_LDS const char*)sX + ((4 * lh + (i16 >> 2)) * PC_LDX + (w & 1) * 64 + 16 * ((lane >> 4) & 1) + (i16 & 3) * 4) * 2;
+  GDF_LDS const char* xl = (GDF_LDS const char*)sX + ((4 * lh + (i16 >> 2)) * PC_LDX + (w & 1) * 64 + 16 * ((lane >> 4) & 1) + (i16 & 3) * 4) * 2;
   const char* wl = sW + ((w >> 1) * NBW * 2 * 64 + lane) * 16;
 
   load_tile(0);
@@ -164,21 +153,21 @@ __global__ __launch_bounds__(PC_NT) void pc_mlp_kernel(const PcArgs a) {
     if (kt + 1 < a.nkt) load_tile(kt + 1);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      pc_f16x8 xf[NIMG][2];
+      f16x8 xf[NIMG][2];
 #pragma unroll
       for (int im = 0; im < NIMG; ++im)
 #pragma unroll
         for (int pb = 0; pb < 2; ++pb) {
-          PC_LDS const char* p = xl + im * PC_XIMG + (16 * s * PC_LDX + pb * 32) * 2;
-          union { pc_fp16x4 q[2]; pc_f16x8 h; } u;
-          u.q[0] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((PC_LDS pc_fp16x4*)p);
-          u.q[1] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((PC_LDS pc_fp16x4*)(p + 8 * PC_LDX * 2));
+          GDF_LDS const char* p = xl + im * PC_XIMG + (16 * s * PC_LDX + pb * 32) * 2;
+          union { pc_fp16x4 q[2]; f16x8 h; } u;
+          u.q[0] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((GDF_LDS pc_fp16x4*)p);
+          u.q[1] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((GDF_LDS pc_fp16x4*)(p + 8 * PC_LDX * 2));
           xf[im][pb] = u.h;
         }
 #pragma unroll
       for (int cb = 0; cb < NBW; ++cb) {
         const char* q = wl + (s * NRB + cb) * 2 * 64 * 16;
-        const pc_f16x8 whi = *(const pc_f16x8*)q, wlo = *(const pc_f16x8*)(q + 64 * 16);
+        const f16x8 whi = *(const f16x8*)q, wlo = *(const f16x8*)(q + 64 * 16);
 #pragma unroll
         for (int pb = 0; pb < 2; ++pb) {
           acc[pb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo, xf[0][pb], acc[pb][cb], 0, 0, 0);
@@ -197,7 +186,7 @@ __global__ __launch_bounds__(PC_NT) void pc_mlp_kernel(const PcArgs a) {
   constexpr int T2 = H2P == 32 ? 1 : 2;          // layer-2 tile of a wave: T2 pixel blocks x T2 row blocks of 32
   constexpr int NJB = H2P / 32;
   const int pb2 = H2P == 32 ? w : (w & 1) * 2, jb2 = H2P == 32 ? 0 : (w >> 1) * 2;
-  pc_f32x16 acc2[T2][T2];
+  f32x16 acc2[T2][T2];
 #pragma unroll
   for (int i = 0; i < T2; ++i)
 #pragma unroll
@@ -205,8 +194,8 @@ __global__ __launch_bounds__(PC_NT) void pc_mlp_kernel(const PcArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc2[i][j][r] = 0.f;
   constexpr int HIMG = 128 * PC_LDX * 2;         // bytes of one hidden image
-  PC_LDS const char* hl = (PC_LDS const char*)pc_smem + ((4 * lh + (i16 >> 2)) * PC_LDX + pb2 * 32 + 16 * ((lane >> 4) & 1) + (i16 & 3) * 4) * 2;
-  const pc_u32x4* w2p = a.w2 + (long)m * (H1P / 16) * NJB * 2 * 64 + lane;
+  GDF_LDS const char* hl = (GDF_LDS const char*)pc_smem + ((4 * lh + (i16 >> 2)) * PC_LDX + pb2 * 32 + 16 * ((lane >> 4) & 1) + (i16 & 3) * 4) * 2;
+  const u32x4* w2p = a.w2 + (long)m * (H1P / 16) * NJB * 2 * 64 + lane;
 #pragma unroll
   for (int ch = 0; ch < NCHK; ++ch) {
     __syncthreads();                             // the staging tiles (the previous chunk) have been read
@@ -231,21 +220,21 @@ __global__ __launch_bounds__(PC_NT) void pc_mlp_kernel(const PcArgs a) {
     __syncthreads();
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
-      pc_f16x8 hf[2][T2];
+      f16x8 hf[2][T2];
 #pragma unroll
       for (int im = 0; im < 2; ++im)
 #pragma unroll
         for (int i = 0; i < T2; ++i) {
-          PC_LDS const char* p = hl + im * HIMG + (16 * s * PC_LDX + i * 32) * 2;
-          union { pc_fp16x4 q[2]; pc_f16x8 h; } u;
-          u.q[0] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((PC_LDS pc_fp16x4*)p);
-          u.q[1] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((PC_LDS pc_fp16x4*)(p + 8 * PC_LDX * 2));
+          GDF_LDS const char* p = hl + im * HIMG + (16 * s * PC_LDX + i * 32) * 2;
+          union { pc_fp16x4 q[2]; f16x8 h; } u;
+          u.q[0] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((GDF_LDS pc_fp16x4*)p);
+          u.q[1] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((GDF_LDS pc_fp16x4*)(p + 8 * PC_LDX * 2));
           hf[im][i] = u.h;
         }
 #pragma unroll
       for (int j = 0; j < T2; ++j) {
-        const pc_u32x4* q = w2p + (((long)(ch * 8 + s) * NJB + jb2 + j) * 2) * 64;
-        const pc_f16x8 whi = __builtin_bit_cast(pc_f16x8, q[0]), wlo = __builtin_bit_cast(pc_f16x8, q[64]);
+        const u32x4* q = w2p + (((long)(ch * 8 + s) * NJB + jb2 + j) * 2) * 64;
+        const f16x8 whi = __builtin_bit_cast(f16x8, q[0]), wlo = __builtin_bit_cast(f16x8, q[64]);
 #pragma unroll
         for (int i = 0; i < T2; ++i) {
           acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo, hf[0][i], acc2[i][j], 0, 0, 0);
@@ -335,23 +324,6 @@ __global__ __launch_bounds__(128) void pc_vote_kernel(const float* logits, int M
   }
 }
 
-size_t pc_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// fp32 -> fp16 bits, round to nearest even (|v| < 65504 here; subnormals included)
-uint16_t pc_half_bits(float v) {
-  uint32_t u;
-  memcpy(&u, &v, 4);
-  const uint32_t sign = (u >> 16) & 0x8000u;
-  u &= 0x7fffffffu;
-  if (u >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                  // overflow (not reached: rows are scaled below 2^14)
-  if (u < 0x38800000u) {                                                    // subnormal half or zero: v * 2^24 rounded to an integer
-    float a;
-    memcpy(&a, &u, 4);
-    return (uint16_t)(sign | (uint32_t)lrintf(a * 16777216.f));
-  }
-  const uint32_t r = u + 0xfffu + ((u >> 13) & 1u);
-  return (uint16_t)(sign | ((r - 0x38000000u) >> 13));
-}
 float pc_half_value(uint16_t h) {
   const int e = (h >> 10) & 31, f = h & 1023;
   const float v = e ? ldexpf((float)(f | 1024), e - 25) : ldexpf((float)f, -24);
@@ -374,10 +346,6 @@ hipError_t pc_launch_nets(const PixCls* pc, const PcArgs& a, unsigned grid, hipS
   return pc->H1P == 128 ? pc_launch<T, 128, 32, CL>(a, grid, s) : pc_launch<T, 256, 128, CL>(a, grid, s);
 }
 
-}  // namespace
-
-namespace {
-
 // One model's weight matrix src (rows x cols, row-major) as MFMA A-operand fragments: each row scaled by the power of two that puts its largest
 // magnitude into [2^13, 2^14) (so the low half stays clear of the fp16 subnormals), split into fp16 hi = fp16(v), lo = fp16(v - hi), and laid out
 // [16-column step][32-row block of RB][hi, lo][lane][8] with a lane's eight columns in the transposed LDS read's order (pc_perm).  dst holds
@@ -390,14 +358,14 @@ void pc_pack_pairs(const float* src, int rows, int cols, int RB, int steps, uint
     const float* row = src + (size_t)n * cols;
     float mx = 0.f;
     for (int c = 0; c < cols; ++c) mx = std::max(mx, fabsf(row[c]));
-    const int sh = (mx > 0.f && std::isfinite(mx)) ? 13 - ilogbf(mx) : 0;
+    const int sh = split_shift(mx);
     inv[n] = ldexpf(1.f, -sh);
     std::fill(hi.begin(), hi.end(), 0);
     std::fill(lo.begin(), lo.end(), 0);
     for (int c = 0; c < cols; ++c) {
       const float v = ldexpf(row[c], sh);
-      hi[c] = pc_half_bits(v);
-      lo[c] = pc_half_bits(v - pc_half_value(hi[c]));
+      hi[c] = half_bits(v);
+      lo[c] = half_bits(v - pc_half_value(hi[c]));
     }
     const int rb = n / 32, q = n % 32;
     for (int s = 0; s < steps; ++s)
@@ -412,6 +380,23 @@ void pc_pack_pairs(const float* src, int rows, int cols, int RB, int steps, uint
   }
 }
 
+// the image of an ensemble, on the host and on the device: [W1 pairs][1 / scale][b1][W2 pairs][1 / scale][b2][W3][b3]
+struct PcImage { uint16_t* w1; float *is, *b1; uint16_t* w2; float *is2, *b2, *w3, *b3; size_t bytes; };
+PcImage pc_image(void* base, size_t M, size_t w1n, size_t w2n, int H1P, int H2P, int K) {
+  Carver c(base);
+  PcImage i;
+  i.w1 = c.take<uint16_t>(M * w1n * 2);
+  i.is = c.take<float>(M * H1P * 4);
+  i.b1 = c.take<float>(M * H1P * 4);
+  i.w2 = c.take<uint16_t>(M * w2n * 2);
+  i.is2 = c.take<float>(M * H2P * 4);
+  i.b2 = c.take<float>(M * H2P * 4);
+  i.w3 = c.take<float>(M * K * H2P * 4);
+  i.b3 = c.take<float>(M * K * 4);
+  i.bytes = c.bytes();
+  return i;
+}
+
 }  // namespace
 
 hipError_t pixcls_create(int C, int M, int h1, int h2, int K, const float* W1, const float* b1, const float* W2, const float* b2,
@@ -420,13 +405,11 @@ hipError_t pixcls_create(int C, int M, int h1, int h2, int K, const float* W1, c
   const int H1P = large ? 256 : 128, H2P = large ? 128 : 32;
   const int nkt = (C + PC_KT - 1) / PC_KT, NRB = H1P / 32, NJB = H2P / 32;
   const size_t w1n = (size_t)nkt * 2 * NRB * 2 * 64 * 8, w2n = (size_t)(H1P / 16) * NJB * 2 * 64 * 8;          // halves per model
-  const size_t o_w1 = 0, o_is = pc_up256(M * w1n * 2), o_b1 = o_is + pc_up256((size_t)M * H1P * 4), o_w2 = o_b1 + pc_up256((size_t)M * H1P * 4);
-  const size_t o_is2 = o_w2 + pc_up256(M * w2n * 2), o_b2 = o_is2 + pc_up256((size_t)M * H2P * 4), o_w3 = o_b2 + pc_up256((size_t)M * H2P * 4);
-  const size_t o_b3 = o_w3 + pc_up256((size_t)M * K * H2P * 4), bytes = o_b3 + pc_up256((size_t)M * K * 4);
+  const size_t bytes = pc_image(nullptr, M, w1n, w2n, H1P, H2P, K).bytes;
   std::vector<char> host(bytes, 0);
-  uint16_t *pw = (uint16_t*)(host.data() + o_w1), *pw2 = (uint16_t*)(host.data() + o_w2);
-  float *is = (float*)(host.data() + o_is), *pb1 = (float*)(host.data() + o_b1), *is2 = (float*)(host.data() + o_is2);
-  float *pb2 = (float*)(host.data() + o_b2), *pw3 = (float*)(host.data() + o_w3), *pb3 = (float*)(host.data() + o_b3);
+  const PcImage hi = pc_image(host.data(), M, w1n, w2n, H1P, H2P, K);
+  uint16_t *pw = hi.w1, *pw2 = hi.w2;
+  float *is = hi.is, *pb1 = hi.b1, *is2 = hi.is2, *pb2 = hi.b2, *pw3 = hi.w3, *pb3 = hi.b3;
   for (int m = 0; m < M; ++m) {
     pc_pack_pairs(W1 + (size_t)m * h1 * C, h1, C, NRB, nkt * 2, pw + m * w1n, is + m * H1P);
     pc_pack_pairs(W2 + (size_t)m * h2 * h1, h2, h1, NJB, H1P / 16, pw2 + m * w2n, is2 + m * H2P);
@@ -442,9 +425,8 @@ hipError_t pixcls_create(int C, int M, int h1, int h2, int K, const float* W1, c
   if (e != hipSuccess) return e;
   e = hipMemcpy(dev, host.data(), bytes, hipMemcpyHostToDevice);
   if (e != hipSuccess) { (void)hipFree(dev); return e; }
-  char* d = (char*)dev;
-  *out = new PixCls{C, M, h1, h2, K, H1P, H2P, nkt, dev, (const void*)(d + o_w1), (const float*)(d + o_is), (const float*)(d + o_b1),
-                    (const void*)(d + o_w2), (const float*)(d + o_is2), (const float*)(d + o_b2), (const float*)(d + o_w3), (const float*)(d + o_b3)};
+  const PcImage di = pc_image(dev, M, w1n, w2n, H1P, H2P, K);
+  *out = new PixCls{C, M, h1, h2, K, H1P, H2P, nkt, dev, di.w1, di.is, di.b1, di.w2, di.is2, di.b2, di.w3, di.b3};
   return hipSuccess;
 }
 
@@ -454,7 +436,7 @@ void pixcls_destroy(PixCls* pc) {
   delete pc;
 }
 
-size_t pixcls_workspace(const PixCls* pc, long P) { return pc_up256((size_t)pc->M * (size_t)P * pc->K * 4); }
+size_t pixcls_workspace(const PixCls* pc, long P) { return up256((size_t)pc->M * (size_t)P * pc->K * 4); }
 
 hipError_t launch_pixcls(const PixCls* pc, const AggSrc& x, int B, long long* labels, float* js, unsigned char* model_labels, float* logits,
                          void* workspace, hipStream_t s) {
@@ -465,14 +447,13 @@ hipError_t launch_pixcls(const PixCls* pc, const AggSrc& x, int B, long long* la
   if (B == 0) return hipSuccess;
   float* lg = logits ? logits : (float*)workspace;
   const long tiles = (P + PC_BP - 1) / PC_BP, total = tiles * pc->M;
-  const unsigned chunk = (unsigned)((total + PC_XCDS - 1) / PC_XCDS);
-  const PcArgs a{x.ptr, x.sb, x.sc, x.sy, x.sx, x.C, x.H, x.W, P, (const pc_u32x4*)pc->w1, pc->inv_s, pc->b1, (const pc_u32x4*)pc->w2, pc->inv_s2, pc->b2, pc->w3, pc->b3,
+  const unsigned chunk = (unsigned)xcd_chunk(total);
+  const PcArgs a{x.ptr, x.sb, x.sc, x.sy, x.sx, x.C, x.H, x.W, P, (const u32x4*)pc->w1, pc->inv_s, pc->b1, (const u32x4*)pc->w2, pc->inv_s2, pc->b2, pc->w3, pc->b3,
                  lg, pc->M, pc->K, pc->nkt, chunk, total};
-  const long vl = x.f32 ? 4 : 8;
-  const bool cl = x.sc == 1 && !(x.C % vl) && !((uintptr_t)x.ptr & 15) && !(x.sb % vl) && !(x.sy % vl) && !(x.sx % vl);
+  const bool cl = map_lanes_c(x);
   hipError_t e;
-  if (x.f32) e = cl ? pc_launch_nets<float, true>(pc, a, chunk * PC_XCDS, s) : pc_launch_nets<float, false>(pc, a, chunk * PC_XCDS, s);
-  else e = cl ? pc_launch_nets<_Float16, true>(pc, a, chunk * PC_XCDS, s) : pc_launch_nets<_Float16, false>(pc, a, chunk * PC_XCDS, s);
+  if (x.f32) e = cl ? pc_launch_nets<float, true>(pc, a, chunk * XCDS, s) : pc_launch_nets<float, false>(pc, a, chunk * XCDS, s);
+  else e = cl ? pc_launch_nets<_Float16, true>(pc, a, chunk * XCDS, s) : pc_launch_nets<_Float16, false>(pc, a, chunk * XCDS, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(pc_vote_kernel, dim3((unsigned)((P + 127) / 128)), dim3(128), 0, s, lg, pc->M, pc->K, P, labels, js, model_labels);
   return hipGetLastError();

@@ -14,11 +14,9 @@
 //   step on a feature dict: F.interpolate(v, (128, 128), mode='bilinear') of every layer + torch.cat(dim=1)  -> aggregate_kernel
 #include <algorithm>
 
-#include "kernels.h"
+#include "feat_common.h"
 
 namespace gdf {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // PyTorch `nearest`: src = min(floor(dst * (in / out)), in - 1) with the scale held in fp32
 __device__ __forceinline__ int nearest_src(int dst, float scale, int in) {
@@ -77,15 +75,6 @@ enum { AGG_SLAB = 128, AGG_LD = 65 };
 // one source of the launch; `end` = running total of workgroups up to and including this source
 struct AggItem { const void* ptr; long sb, sc, sy, sx; int C, H, W, coff, f32, vec; unsigned end; };
 struct AggTable { AggItem it[AGG_MAX]; };
-
-// ATen's area_pixel_compute_source_index (align_corners = false) in separately rounded fp32 operations, and the taps of upsample_bilinear2d
-__device__ __forceinline__ void bilinear_src(int dst, float scale, int in, int& i0, int& i1, float& l1) {
-#pragma clang fp contract(off)
-  const float s = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-  i0 = min((int)s, in - 1);
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = s - (float)i0;
-}
 
 // Stage nw pixels x nc <= 64 channels of the two source rows r0 / r1 (each pointing at its (b, c0, y, x0) element), blended vertically in fp32,
 // into tile[pixel][channel].  vec: sc == 1 and every pixel 16-byte aligned -> 16 bytes per lane, channel-fastest (the hook layout).
@@ -208,8 +197,7 @@ hipError_t launch_aggregate(const AggSrc* srcs, int n, int B, void* out, int out
     total += (size_t)B * OH * ((e.C + 63) / 64);
     if (total >= (1ull << 31)) return hipErrorInvalidValue;
     slab = std::max(slab, std::min(e.W, (int)AGG_SLAB));
-    const long vl = e.f32 ? 4 : 8;
-    const int vec = e.sc == 1 && !((uintptr_t)e.ptr & 15) && !(e.sb % vl) && !(e.sy % vl) && !(e.sx % vl);
+    const int vec = map_pixels_aligned(e);            // (not map_lanes_c: agg_stage takes the partial group at the end of C element by element)
     t.it[k] = AggItem{e.ptr, e.sb, e.sc, e.sy, e.sx, e.C, e.H, e.W, e.coff, e.f32 ? 1 : 0, vec, (unsigned)total};
   }
   if (total == 0) return hipSuccess;
